@@ -5,13 +5,19 @@ front pair) + the grid + lapping-area knn (cam0 <-> cam1, Lowe 0.8) + SearchByPr
 5,000-point local map (th 6, nnratio 0.8).  One step = one pass over a batch of B frames whose
 images (and map points) are already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line with the headline figure (`value`,
+`ms_per_step`).  --full adds everything else the benchmark measures or checks, each leg with its own switch: the CPU
+baselines, the untimed oracle parity check of the last timed step, the isolated per-kernel roofline passes, the B=1
+latency chain, the 8 x 1920x1080 rig, LocalInertialBA, the pose optimisers, triangulation and the auxiliary legs.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 --gpus N > 1 without a torch.distributed environment: the script starts N ranks itself
 (torch.distributed.run, one process per GPU, before anything touches a GPU) and exits with their status.
 Every rank processes its own frames (frame-parallel replicas, no data-path collective: the path shards by
 frame) and rank 0 prints one JSON line with the whole-job throughput (max time over ranks).  At N > 1 the
-camera-sharded layouts run as extra legs: `cam_shard` (configs[2], 5 Hilti cameras over the ranks, one
+camera-sharded layouts run as extra legs of --full: `cam_shard` (configs[2], 5 Hilti cameras over the ranks, one
 RCCL all-gather of the keypoint / descriptor slabs, matching on rank 0) and `p1080` (configs[3], 8 Pinhole
 cameras 1920x1080 over the ranks).  At N = 1 `p1080` is the 8-camera batch on one GPU.
 """
@@ -1214,6 +1220,50 @@ def latency_leg(d_img, gr0, n_frames, dev, rig, stereo):
                              "p99_ms": round(float(np.percentile(lat0, 99)), 4)}}
 
 
+DUMP_FRAMES, DUMP_SEED, DUMP_MAX_BYTES = 8, 0, 64 << 20
+
+
+def dump_outputs(path, groups, Bg):
+    """--dump-outputs: what the last timed step left in the stream groups' device buffers, i.e. the arrays a caller of
+    the path reads back, as <path>/<name>.npy in float32.  The per-frame counts (n_kp, mono, n_matches) cover every
+    frame of the step; the per-keypoint and per-map-point arrays cover a fixed, seeded sample of DUMP_FRAMES frames
+    (frames.npy: their indices in the step), which keeps the dump well under DUMP_MAX_BYTES.  Slots past a camera's
+    keypoint count are padding, not outputs: they are stored as 0, or -1 for the index / mvuRight arrays.  The inputs are seeded, so two builds run with the same arguments write
+    comparable files."""
+    os.makedirs(path, exist_ok=True)
+    B = Bg * len(groups)
+    sel = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_FRAMES), replace=False))
+
+    def every(get):
+        return np.concatenate([get(gr).cpu().numpy() for gr in groups])
+
+    def rows(get):
+        return np.stack([get(groups[f // Bg])[f % Bg].cpu().numpy() for f in sel])
+
+    n_kp = every(lambda gr: gr["fb"].n_kp)
+    out = {"frames": sel, "n_kp": n_kp, "mono": every(lambda gr: gr["fb"].mono),
+           "n_matches": every(lambda gr: gr["fb"].n_matches)}
+    raw = rows(lambda gr: gr["fb"].kps)                                    # [S, C, cap, 6]: 5 floats + the octave
+    cap = raw.shape[2]
+    live = np.arange(cap)[None, None, :] < n_kp[sel][:, :, None]           # [S, C, cap]
+    kps = raw.view(np.float32).copy()
+    kps[..., 5] = raw[..., 5]
+    out["kps"] = np.where(live[..., None], kps, 0)
+    out["desc"] = np.where(live[..., None], rows(lambda gr: gr["fb"].desc), 0)
+    out["l2r"] = np.where(live[:, 0], rows(lambda gr: gr["fb"].l2r), -1)
+    out["r2l"] = np.where(live[:, 1], rows(lambda gr: gr["fb"].r2l), -1)
+    ur = rows(lambda gr: gr["uright"])                                     # [S, NB, cap]
+    out["uright"] = np.where(live[:, :ur.shape[1]], ur, -1)
+    for k in ("proj_x", "proj_y", "view_cos", "level", "in_view", "track_depth"):   # isInFrustum's track
+        out[k] = rows(lambda gr: getattr(gr["mps"], k))
+    out["kp_to_mp"] = rows(lambda gr: gr["fb"].kp_to_mp)
+    out = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} B exceeds {DUMP_MAX_BYTES} B"
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def _slab_mode():
     import torch.distributed as tdist
     return "host" if tdist.get_backend() == "gloo" else "device"
@@ -1229,7 +1279,7 @@ def _launch_ranks(n):
     return subprocess.run(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")).returncode
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -1238,8 +1288,15 @@ def main():
     ap.add_argument("--streams", type=int, default=3,
                     help="frame groups per GPU, each on its own HIP stream (latency-bound matcher stages of one "
                          "group overlap extraction of another)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg and check (CPU baselines, oracle parity of the last timed step, "
+                         "isolated per-kernel passes, B=1 latency, 1080p rig, LocalInertialBA, pose, triangulation, "
+                         "aux, and at N>1 the camera-sharded legs); without it the switches of those legs are ignored")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--stage-timing", type=int, default=1)
+    ap.add_argument("--stage-timing", type=int, default=1,
+                    help="per-stage HIP events recorded inside the timed steps (no run of their own)")
     ap.add_argument("--parity-check", type=int, default=1,
                     help="untimed oracle check of frames of the last timed step (--parity-frames)")
     ap.add_argument("--parity-frames", default="0:0,-1:-1",
@@ -1265,7 +1322,16 @@ def main():
     ap.add_argument("--latency-frames", type=int, default=200, help="B=1 sequential frames timed (0: skip)")
     ap.add_argument("--iso-reps", type=int, default=3,
                     help="isolated single-stream passes of one group for the per-kernel roofline (0: skip)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the headline
+        args.no_cpu_baseline = True
+        args.parity_check = args.iso_reps = args.latency_frames = args.p1080_frames = args.shard_frames = 0
+        args.lba_steps = args.pose_frames = args.tri_pairs = args.aux = 0
+    return args
+
+
+def main():
+    args = parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(_launch_ranks(args.gpus))   # before anything touches a GPU
@@ -1451,6 +1517,8 @@ def main():
     dt = job_seconds(time.perf_counter() - t0, dev)   # max over ranks
     assert all(gr["ex"].last_error() == 0 for gr in groups)
     n_matches = int(sum(gr["fb"].n_matches.sum().item() for gr in groups))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, groups, Bg)
     # untimed: the last timed step's outputs of two frames against the CPU oracle (checker only)
     parity = parity_post_run(parity_frames, groups, rig, cams_r, Rlr, tlr, sigma2, BF) \
         if args.parity_check and rank == 0 else None
@@ -1624,6 +1692,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(dt / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak",

@@ -2,7 +2,7 @@
 128 frames x 5 cameras per extract launch, the groups running concurrently on 3 HIP streams: extract -> grid ->
 lapping knn -> TriangulateMatches -> mvuRight -> isInFrustum -> SearchByProjection) run for 2 timed steps, then
 frames 0, 63 and 127 of EVERY group read back from the last step's device buffers and compared bit for bit with
-the CPU oracle (bench.py::parity_post_run: extraction, stereo pairs, mvuRight, isInFrustum track,
+the CPU oracle (bench.py --full, parity_post_run: extraction, stereo pairs, mvuRight, isInFrustum track,
 SearchByProjection assignments and counts).  Runs bench.py as a child process (no exec from this process)."""
 import json
 import os
@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.timeout(500)
 def test_bench_headline_shape_is_bit_exact():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
            "--lba-steps", "0", "--pose-frames", "0", "--tri-pairs", "0", "--aux", "0", "--p1080-frames", "0",
            "--latency-frames", "0", "--iso-reps", "0", "--stage-timing", "0", "--parity-frames", "*:0,*:63,*:127"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# One GPU call: GPU tests, the default bench, then the rocprof kernel-trace + PMC profile.
+# One GPU call: GPU tests, the whole bench (--full), then the rocprof kernel-trace + PMC profile.
 # Usage (on the box, from the repo root): bash tools/gpu_round.sh <tag> [skip-tests]
 set -euo pipefail
 TAG=${1:-r02}
@@ -11,7 +11,9 @@ if [ "${2:-}" != "skip-tests" ]; then
       > gpurun_out/gputests_$TAG.log 2>&1
   tail -3 gpurun_out/gputests_$TAG.log
 fi
-timeout -k 10 500 python -u bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
-tail -c 600 gpurun_out/bench_$TAG.json
+BOUT=${OMV_BENCH_OUT:-scratch}   # where the bench's result line goes
+mkdir -p $BOUT
+timeout -k 10 500 python -u bench.py --full > $BOUT/bench_$TAG.json 2> $BOUT/bench_$TAG.err
+tail -c 600 $BOUT/bench_$TAG.json
 bash tools/profile_gpu.sh $TAG
 bash tools/pmc_orb_bound.sh bound_$TAG

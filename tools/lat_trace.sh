@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $OUT -o run --output-format csv -- \
-    python3 $R/bench.py --frames 3 --streams 1 --steps 1 --warmup 1 --latency-frames 200 --no-cpu-baseline \
+    python3 $R/bench.py --full --frames 3 --streams 1 --steps 1 --warmup 1 --latency-frames 200 --no-cpu-baseline \
     --lba-steps 0 --pose-frames 0 --tri-pairs 0 --aux 0 --p1080-frames 0 --stage-timing 0 > $OUT/bench.json 2> $OUT/bench.err
 python3 - $OUT/run_kernel_stats.csv <<'PY'
 import csv, sys

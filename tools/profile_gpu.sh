@@ -16,7 +16,7 @@ cd /tmp && export TMPDIR=/tmp
 HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -d $OUT/trace -o run --output-format csv -- \
-    python3 $R/bench.py --no-cpu-baseline --steps 5 --warmup 1 --lba-steps 3 --pose-frames 256 --tri-pairs 64 \
+    python3 $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 1 --lba-steps 3 --pose-frames 256 --tri-pairs 64 \
     > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --pmc $C -T -d $OUT/pmc_orb_$C -o run --output-format csv -- \

@@ -12,7 +12,7 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method threa
     > gpurun_out/ql_tests.log 2>&1 || { tail -30 gpurun_out/ql_tests.log; exit 1; }
 tail -1 gpurun_out/ql_tests.log
 bash tools/lba_tl.sh
-timeout -k 10 300 python bench.py --no-cpu-baseline --steps 1 --warmup 1 --pose-frames 0 --tri-pairs 0 --aux 0 \
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 1 --warmup 1 --pose-frames 0 --tri-pairs 0 --aux 0 \
     --p1080-frames 0 --latency-frames 0 > gpurun_out/ql_bench.json 2> gpurun_out/ql_bench.err
 python3 -c "
 import json; d = json.loads(open('gpurun_out/ql_bench.json').read().strip().splitlines()[-1]); l = d['local_ba']

@@ -9,7 +9,7 @@ timeout -k 10 400 python -u -m pytest tests/test_orb_gpu.py tests/test_p1080_gpu
     --timeout 480 --timeout-method thread > gpurun_out/qo_tests.log 2>&1 || { tail -30 gpurun_out/qo_tests.log; exit 1; }
 tail -1 gpurun_out/qo_tests.log
 timeout -k 10 120 python tools/orb_once.py --frames 128 --reps 3 --timing
-timeout -k 10 300 python bench.py --no-cpu-baseline --lba-steps 0 --pose-frames 0 --tri-pairs 0 --aux 0 \
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --lba-steps 0 --pose-frames 0 --tri-pairs 0 --aux 0 \
     --p1080-frames 0 --latency-frames 0 > gpurun_out/qo_bench.json 2> gpurun_out/qo_bench.err
 python3 - <<'PY'
 import json

@@ -41,7 +41,7 @@ def main(src, tag, command=None):
     rows = list(csv.DictReader(open(os.path.join(src, "trace", "run_kernel_stats.csv"))))
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
     lines = [f"# rocprofv3 --kernel-trace --stats ({tag})", "",
-             "Command: `" + (command or "rocprofv3 --kernel-trace --stats -T -- python3 bench.py --no-cpu-baseline "
+             "Command: `" + (command or "rocprofv3 --kernel-trace --stats -T -- python3 bench.py --full --no-cpu-baseline "
                              "--steps 5 --warmup 1 --lba-steps 3 --pose-frames 256 --tri-pairs 64") + "` (MI355X, one GPU).", "",
              "| kernel | calls | total ms | avg us | min us | max us | share |", "|---|---|---|---|---|---|---|"]
     for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"])):
