@@ -16,25 +16,12 @@
 
 #include "../../include/omv.h"
 #include "omv_device.h"
+#include "omv_host.h"
 
 namespace {
 
-#define HIP_OK(x)                                                                    \
-    do {                                                                             \
-        hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) {                                                      \
-            fprintf(stderr, "omv: %s failed: %s\n", #x, hipGetErrorString(e_));      \
-            return OMV_ERR_HIP;                                                      \
-        }                                                                            \
-    } while (0)
-
 constexpr int kMaxSet = 16384;   // keys carry the feature index in 14 bits
 constexpr int kBuildThreads = 1024;
-
-__device__ __forceinline__ void load_desc(const uint8_t *p, uint64_t d[4]) {
-    const uint64_t *q = reinterpret_cast<const uint64_t *>(p);
-    d[0] = q[0], d[1] = q[1], d[2] = q[2], d[3] = q[3];
-}
 
 __global__ void __launch_bounds__(256) bow_descend_kernel(omv_vocab v, const uint8_t *desc, int cap, const int *n_desc,
                                                           int n_sets, int levelsup, int32_t *word, double *wval,
@@ -48,7 +35,7 @@ __global__ void __launch_bounds__(256) bow_descend_kernel(omv_vocab v, const uin
         return;
     }
     uint64_t f[4];
-    load_desc(desc + (size_t)g * 32, f);
+    omv::load_desc(desc + (size_t)g * 32, f);
     const int nid_level = v.L - levelsup;
     int nid = nid_level <= 0 ? 0 : -1;
     int final_id = 0, level = 0;
@@ -57,11 +44,11 @@ __global__ void __launch_bounds__(256) bow_descend_kernel(omv_vocab v, const uin
         const int c0 = v.child_start[final_id], c1 = v.child_start[final_id + 1];
         final_id = v.child_ids[c0];
         uint64_t d[4];
-        load_desc(v.desc + 32 * (size_t)final_id, d);
+        omv::load_desc(v.desc + 32 * (size_t)final_id, d);
         int best_d = omv::hamming256(f, d);
         for (int c = c0 + 1; c < c1; ++c) {
             const int id = v.child_ids[c];
-            load_desc(v.desc + 32 * (size_t)id, d);
+            omv::load_desc(v.desc + 32 * (size_t)id, d);
             const int dd = omv::hamming256(f, d);
             if (dd < best_d) best_d = dd, final_id = id;
         }

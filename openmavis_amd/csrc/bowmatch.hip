@@ -26,17 +26,9 @@
 
 #include "../../include/omv.h"
 #include "omv_device.h"
+#include "omv_host.h"
 
 namespace {
-
-#define HIP_OK(x)                                                                    \
-    do {                                                                             \
-        hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) {                                                      \
-            fprintf(stderr, "omv: %s failed: %s\n", #x, hipGetErrorString(e_));      \
-            return OMV_ERR_HIP;                                                      \
-        }                                                                            \
-    } while (0)
 
 constexpr int TH_LOW = 50, kHisto = 30;
 constexpr int kMaxKp = 16384;      // keypoints per view (LDS claim bitmap + rotation bins)

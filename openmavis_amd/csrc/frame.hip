@@ -12,17 +12,9 @@
 #include <cstdio>
 
 #include "../../include/omv.h"
+#include "omv_host.h"
 
 namespace {
-
-#define HIP_OK(x)                                                                    \
-    do {                                                                             \
-        hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) {                                                      \
-            fprintf(stderr, "omv: %s failed: %s\n", #x, hipGetErrorString(e_));      \
-            return OMV_ERR_HIP;                                                      \
-        }                                                                            \
-    } while (0)
 
 constexpr int kMaxBlocks = 8;
 

@@ -24,11 +24,8 @@
 
 #include "../../include/omv.h"
 #include "omv_device.h"
+#include "omv_host.h"
 
-#define HIP_OK(x)                                          \
-    do {                                                   \
-        if ((x) != hipSuccess) return OMV_ERR_HIP;         \
-    } while (0)
 #define OMV_OK_OR_RETURN(x)                                \
     do {                                                   \
         const omv_status s_ = (x);                         \

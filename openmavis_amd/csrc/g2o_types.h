@@ -78,6 +78,7 @@ __device__ __forceinline__ void tr3(const double *a, double *r) {
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) r[3 * i + j] = a[3 * j + i];
 }
+// double: the optimizer edges; imu.hip's hat3 is the float one of the preintegration
 __device__ __forceinline__ void hat3(const double *w, double *W) {
     W[0] = 0, W[1] = -w[2], W[2] = w[1], W[3] = w[2], W[4] = 0, W[5] = -w[0], W[6] = -w[1], W[7] = w[0], W[8] = 0;
 }
@@ -599,12 +600,6 @@ __device__ __forceinline__ double lane_f64(double x, int l) {
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Cyclic Jacobi eigen-decomposition of the symmetric N x N matrix A (row-major, LDS) over one wavefront:
 // A is driven to diag(w) in place, V (LDS, N x N) receives the eigenvectors (columns).  Per element the same
 // operations in the same order as the oracle's sym_eig (ba_oracle.cpp).  Every lane of the wave must call it.
@@ -612,7 +607,7 @@ template <int N>
 __device__ inline void sym_eig_wave(double *A, double *V, int lane) {
     static_assert(N <= 64, "one row per lane");
     for (int q = lane; q < N * N; q += 64) V[q] = (q / N == q % N) ? 1.0 : 0.0;
-    wave_lds_sync();
+    omv::wave_lds_sync();
     for (int sweep = 0; sweep < 100; ++sweep) {
         double off = 0, dg = 0;   // converged: off-diagonal mass below 1e-32 of the diagonal's
         for (int p = 0; p < N; ++p) {
@@ -627,19 +622,19 @@ __device__ inline void sym_eig_wave(double *A, double *V, int lane) {
                 const double th = (A[q * N + q] - A[p * N + p]) / (2 * apq);
                 const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1));
                 const double c = 1 / sqrt(t * t + 1), s = t * c;
-                wave_lds_sync();
+                omv::wave_lds_sync();
                 if (lane < N) {
                     const double akp = A[lane * N + p], akq = A[lane * N + q];
                     A[lane * N + p] = c * akp - s * akq, A[lane * N + q] = s * akp + c * akq;
                 }
-                wave_lds_sync();
+                omv::wave_lds_sync();
                 if (lane < N) {
                     const double apk = A[p * N + lane], aqk = A[q * N + lane];
                     A[p * N + lane] = c * apk - s * aqk, A[q * N + lane] = s * apk + c * aqk;
                     const double vkp = V[lane * N + p], vkq = V[lane * N + q];
                     V[lane * N + p] = c * vkp - s * vkq, V[lane * N + q] = s * vkp + c * vkq;
                 }
-                wave_lds_sync();
+                omv::wave_lds_sync();
             }
     }
 }
@@ -654,7 +649,7 @@ __device__ inline void sym_eig_wave_par(double *A, double *V, double *cs, int *p
     static_assert(N <= 64, "one row per lane");
     constexpr int NP = (N + 1) & ~1, HP = NP / 2;
     for (int q = lane; q < N * N; q += 64) V[q] = (q / N == q % N) ? 1.0 : 0.0;
-    wave_lds_sync();
+    omv::wave_lds_sync();
     for (int sweep = 0; sweep < 100; ++sweep) {
         double off = 0, dg = 0;   // converged: off-diagonal mass below 1e-32 of the diagonal's
         for (int e = lane; e < N * N; e += 64) {
@@ -683,7 +678,7 @@ __device__ inline void sym_eig_wave_par(double *A, double *V, double *cs, int *p
                 }
                 cs[2 * lane] = c, cs[2 * lane + 1] = sn, pq[2 * lane] = p, pq[2 * lane + 1] = qq;
             }
-            wave_lds_sync();
+            omv::wave_lds_sync();
             for (int tk = lane; tk < HP * N; tk += 64) {   // columns p, q of A and V
                 const int i = tk / N, k = tk - (tk / N) * N;
                 const int p = pq[2 * i], q = pq[2 * i + 1];
@@ -694,7 +689,7 @@ __device__ inline void sym_eig_wave_par(double *A, double *V, double *cs, int *p
                 const double vkp = V[k * N + p], vkq = V[k * N + q];
                 V[k * N + p] = c * vkp - sn * vkq, V[k * N + q] = sn * vkp + c * vkq;
             }
-            wave_lds_sync();
+            omv::wave_lds_sync();
             for (int tk = lane; tk < HP * N; tk += 64) {   // rows p, q of A
                 const int i = tk / N, k = tk - (tk / N) * N;
                 const int p = pq[2 * i], q = pq[2 * i + 1];
@@ -703,7 +698,7 @@ __device__ inline void sym_eig_wave_par(double *A, double *V, double *cs, int *p
                 const double apk = A[p * N + k], aqk = A[q * N + k];
                 A[p * N + k] = c * apk - sn * aqk, A[q * N + k] = sn * apk + c * aqk;
             }
-            wave_lds_sync();
+            omv::wave_lds_sync();
         }
     }
 }
@@ -734,7 +729,7 @@ __device__ inline bool ldl_nopiv_wave(const double *A, double shift, double *L, 
 #pragma unroll
         for (int j = 0; j < N; ++j) L[lane * N + j] = r[j];
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
     return pos;
 }
 
@@ -765,7 +760,7 @@ __device__ inline void ldl_inverse_wave(const double *L, double *X, int lane) {
 #pragma unroll
         for (int i = 0; i < N; ++i) X[i * N + lane] = y[i];
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
 }
 
 // Largest |diagonal| of the N x N A (wave-uniform).
@@ -797,7 +792,7 @@ __device__ __attribute__((noinline)) void pinv15_wave(double *A, double *V, doub
         }
         P[q] = s;
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
 }
 
 // EdgePriorPoseImu::computeError / linearizeOplus (G2oTypes.cc:758-785) at the vertex state (R, t, v, bg, ba)
@@ -838,36 +833,36 @@ __device__ inline void inertial_info9_wave(const float *C15, double *out, double
         const int r = q / 9, c = q % 9;
         A[q] = (double)C15[r * 15 + c], I[q] = r == c ? 1.0 : 0.0, V[q] = r == c ? 1.0 : 0.0;
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
     for (int c = 0; c < 9; ++c) {   // Gauss-Jordan, partial pivoting
         int p = c;
         for (int r = c + 1; r < 9; ++r)
             if (fabs(A[r * 9 + c]) > fabs(A[p * 9 + c])) p = r;
-        wave_lds_sync();
+        omv::wave_lds_sync();
         if (p != c && lane < 9) {
             double t = A[p * 9 + lane];
             A[p * 9 + lane] = A[c * 9 + lane], A[c * 9 + lane] = t;
             t = I[p * 9 + lane];
             I[p * 9 + lane] = I[c * 9 + lane], I[c * 9 + lane] = t;
         }
-        wave_lds_sync();
+        omv::wave_lds_sync();
         const double d = A[c * 9 + c];
-        wave_lds_sync();
+        omv::wave_lds_sync();
         if (lane < 9) A[c * 9 + lane] /= d, I[c * 9 + lane] /= d;
-        wave_lds_sync();
+        omv::wave_lds_sync();
         if (lane < 9 && lane != c && A[lane * 9 + c] != 0) {
             const double f = A[lane * 9 + c];
             for (int k = 0; k < 9; ++k) A[lane * 9 + k] -= f * A[c * 9 + k], I[lane * 9 + k] -= f * I[c * 9 + k];
         }
-        wave_lds_sync();
+        omv::wave_lds_sync();
     }
     for (int q = lane; q < 81; q += 64) {   // symmetrise: (I + I^T) / 2 in the upper-then-lower write order
         const int r = q / 9, c = q % 9;
         A[q] = r < c ? (I[r * 9 + c] + I[c * 9 + r]) / 2 : (r > c ? (I[c * 9 + r] + I[r * 9 + c]) / 2 : I[q]);
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
     for (int q = lane; q < 81; q += 64) I[q] = A[q];
-    wave_lds_sync();
+    omv::wave_lds_sync();
     if constexpr (kPar) {
         // every eigenvalue above the 1e-12 cut (I - tau I factors with positive pivots): the projection is I itself
         const double tau = 1e-12 + 1e-12 * max_abs_diag<9>(I, lane);
@@ -927,23 +922,23 @@ __device__ inline bool ldlt_pivot_solve_wave(double *A, const double *b, double 
                 A[k * N + k] = A[big * N + big], A[big * N + big] = u;
             }
         }
-        wave_lds_sync();
+        omv::wave_lds_sync();
         if (k > 0) {
             if (lane < k) t[lane] = A[lane * N + lane] * A[k * N + lane];
-            wave_lds_sync();
+            omv::wave_lds_sync();
             if (lane >= k && lane < N) {   // lane k: the pivot, lanes > k: the column below it
                 double s = 0;
                 for (int j = 0; j < k; ++j) s += A[lane * N + j] * t[j];
                 A[lane * N + k] -= s;
             }
-            wave_lds_sync();
+            omv::wave_lds_sync();
         }
         const double akk = A[k * N + k];
         const bool valid = fabs(akk) > 0.0;
         if (k == 0 && !valid) {
             sign = 0;
             if (lane < N) tr[lane] = lane;
-            wave_lds_sync();
+            omv::wave_lds_sync();
             break;
         }
         if (valid && lane > k && lane < N) A[lane * N + k] /= akk;
@@ -955,7 +950,7 @@ __device__ inline bool ldlt_pivot_solve_wave(double *A, const double *b, double 
             if (akk > 0) sign = 1;
             else if (akk < 0) sign = 2;
         }
-        wave_lds_sync();
+        omv::wave_lds_sync();
     }
     if (!(sign == 1 || sign == 0)) return false;
     // y = P b; L y' = y (column-oriented); D pseudo-inverse; L^T x = y'' (column-oriented, j descending)
@@ -967,18 +962,18 @@ __device__ inline bool ldlt_pivot_solve_wave(double *A, const double *b, double 
             y[k] = y[tr[k]], y[tr[k]] = u;
         }
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
     for (int j = 0; j < N; ++j) {
         const double yj = y[j];
         if (lane > j && lane < N) y[lane] -= A[lane * N + j] * yj;
-        wave_lds_sync();
+        omv::wave_lds_sync();
     }
     if (lane < N) y[lane] = fabs(A[lane * N + lane]) > 2.2250738585072014e-308 ? y[lane] / A[lane * N + lane] : 0.0;
-    wave_lds_sync();
+    omv::wave_lds_sync();
     for (int j = N - 1; j >= 0; --j) {
         const double yj = y[j];
         if (lane < j) y[lane] -= A[j * N + lane] * yj;
-        wave_lds_sync();
+        omv::wave_lds_sync();
     }
     if (lane == 0) {
         for (int k = N - 1; k >= 0; --k) {
@@ -987,7 +982,7 @@ __device__ inline bool ldlt_pivot_solve_wave(double *A, const double *b, double 
         }
         for (int i = 0; i < N; ++i) x[i] = y[i];
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
     return true;
 }
 

@@ -14,17 +14,9 @@
 
 #include "../../include/omv.h"
 #include "omv_device.h"
+#include "omv_host.h"
 
 namespace {
-
-#define HIP_OK(x)                                                                    \
-    do {                                                                             \
-        hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) {                                                      \
-            fprintf(stderr, "omv: %s failed: %s\n", #x, hipGetErrorString(e_));      \
-            return OMV_ERR_HIP;                                                      \
-        }                                                                            \
-    } while (0)
 
 // record offsets (include/omv.h OMV_PREINT_FLOATS layout)
 constexpr int kR = 0, kV = 9, kP = 12, kJRg = 15, kJVg = 24, kJVa = 33, kJPg = 42, kJPa = 51, kB = 60, kT = 66,
@@ -37,6 +29,7 @@ __device__ __forceinline__ void mul3(const float *a, const float *b, float *r) {
 __device__ __forceinline__ void mulv3(const float *a, const float *x, float *y) {
     for (int i = 0; i < 3; ++i) y[i] = a[3 * i] * x[0] + a[3 * i + 1] * x[1] + a[3 * i + 2] * x[2];
 }
+// float: the preintegration is single precision; g2o_types.h's hat3 is the double one of the optimizer edges
 __device__ __forceinline__ void hat3(const float *w, float *W) {
     W[0] = 0, W[1] = -w[2], W[2] = w[1], W[3] = w[2], W[4] = 0, W[5] = -w[0], W[6] = -w[1], W[7] = w[0], W[8] = 0;
 }
@@ -183,12 +176,6 @@ __device__ void step_scalar(float *s, float *avg, const float *meas, float *A, f
     }
 }
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // One wavefront per record.
 __global__ void __launch_bounds__(64) preint_kernel(float *rec, float *avg_io, const float *meas, const int32_t *start,
                                                     Calib cal) {
@@ -198,12 +185,12 @@ __global__ void __launch_bounds__(64) preint_kernel(float *rec, float *avg_io, c
     float *g = rec + (size_t)r * OMV_PREINT_FLOATS;
     for (int q = lane; q < OMV_PREINT_FLOATS; q += 64) s[q] = g[q];
     if (lane < 6) avg[lane] = avg_io ? avg_io[(size_t)r * 6 + lane] : 0.0f;
-    wave_sync();
+    omv::wave_lds_sync();
     const int m0 = start[r], m1 = start[r + 1];
     for (int m = m0; m < m1; ++m) {
         const float *ms = meas + (size_t)m * 7;
         if (lane == 0) step_scalar(s, avg, ms, A, B);
-        wave_sync();
+        omv::wave_lds_sync();
         // T = A C (9x15), U = B Nga (9x6)
         for (int q = lane; q < 135 + 54; q += 64) {
             if (q < 135) {
@@ -216,7 +203,7 @@ __global__ void __launch_bounds__(64) preint_kernel(float *rec, float *avg_io, c
                 U[q - 135] = B[q - 135] * cal.Nga[k];
             }
         }
-        wave_sync();
+        omv::wave_lds_sync();
         // C[0:9, 0:9] = T A^T + U B^T; diag C[9:15, 9:15] += dt^2 NgaWalk (disjoint elements)
         const float dt = ms[6];
         float cn[2];
@@ -227,11 +214,11 @@ __global__ void __launch_bounds__(64) preint_kernel(float *rec, float *avg_io, c
             for (int k = 0; k < 6; ++k) u += U[i * 6 + k] * B[l * 6 + k];
             cn[n] = t + u;
         }
-        wave_sync();
+        omv::wave_lds_sync();
         for (int q = lane, n = 0; q < 81; q += 64, ++n) s[kC + (q / 9) * 15 + q % 9] = cn[n];
         if (lane < 6) s[kC + (9 + lane) * 15 + 9 + lane] += (dt * dt) * cal.NgaWalk[lane];   // += a diagonal
         if (lane == 0) s[kT] += dt;
-        wave_sync();
+        omv::wave_lds_sync();
     }
     for (int q = lane; q < OMV_PREINT_FLOATS; q += 64) g[q] = s[q];
     if (avg_io && lane < 6) avg_io[(size_t)r * 6 + lane] = avg[lane];

@@ -43,21 +43,13 @@
 #include "../../include/omv.h"
 #include "g2o_types.h"
 #include "omv_device.h"
+#include "omv_host.h"
 
 namespace {
 
 using namespace omv_g2o;
 
 constexpr int kGrpEdges = 256;   // edges per buildSystem landmark group / pose chunk (one per thread)
-
-#define HIP_OK(x)                                                                    \
-    do {                                                                             \
-        hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) {                                                      \
-            fprintf(stderr, "omv: %s failed: %s\n", #x, hipGetErrorString(e_));      \
-            return OMV_ERR_HIP;                                                      \
-        }                                                                            \
-    } while (0)
 
 
 
@@ -1129,16 +1121,6 @@ __device__ __forceinline__ void wave_sync() {
     }
 }
 
-// 1 / x by v_rcp_f64 and two Newton steps (within an ulp of the IEEE quotient; the pivots are normal
-// numbers -- a zero / non-finite pivot is flagged by the caller)
-__device__ __forceinline__ double rcp_nr(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, r, 1.0);
-    r = fma(r, e, r);
-    e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-}
-
 // The reduced system is factored as a block LDL^T with 16x16 block pivots: A = L D L^T, L_ik = S_ik D_k^-1, D_k = S_kk
 // (each S the block as it stands when column k is eliminated).  Nothing but the blocks themselves and D_k^-1 is kept:
 // the diagonal slot of column k is overwritten by D_k^-1, the panels S_ik stay unscaled in place, and
@@ -1174,7 +1156,7 @@ __device__ __forceinline__ void sweep_pass(double cur[4], int q, int j) {
     constexpr int tk = K >> 2, qk = K & 3;
     const double p = readlane_f64(cur[tk], 16 * qk + K);
     const double mkj = __shfl(cur[tk], 16 * qk + j, 64);   // issued early: its latency hides behind the reciprocal
-    const double r = rcp_nr(p);
+    const double r = omv::rcp_nr(p);
     const double f = mkj * r;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {

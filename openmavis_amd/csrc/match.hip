@@ -28,7 +28,9 @@
 #include <vector>
 
 #include "../../include/omv.h"
+#include "omv_camera.h"
 #include "omv_device.h"
+#include "omv_host.h"
 
 namespace {
 
@@ -37,15 +39,6 @@ constexpr int kTH_HIGH = 100;
 constexpr int kTop = 16;   // candidates kept per (point, camera): rescans only when >14 are claimed
 constexpr int kMaxCams = 8;
 constexpr size_t kResolveLds = 150 * 1024;   // dynamic LDS of the resolve workgroup (set as its maximum)
-
-#define HIP_OK(x)                                                                    \
-    do {                                                                             \
-        hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) {                                                      \
-            fprintf(stderr, "omv: %s failed: %s\n", #x, hipGetErrorString(e_));      \
-            return OMV_ERR_HIP;                                                      \
-        }                                                                            \
-    } while (0)
 
 struct FrameArgs {
     int n_cams, kp_cap, nlevels;
@@ -231,11 +224,6 @@ struct TopSeq {
     }
 };
 
-__device__ __forceinline__ void load_desc(const uint8_t *p, uint64_t d[4]) {
-    const uint64_t *q = reinterpret_cast<const uint64_t *>(p);
-    d[0] = q[0], d[1] = q[1], d[2] = q[2], d[3] = q[3];
-}
-
 // Window of GetFeaturesInArea(x, y, r, level-1, level, cam), in the reference's iteration order;
 // keeps the kTop best unblocked candidates by (dist, order).
 template <class Blocked, class TopT>
@@ -268,7 +256,7 @@ __device__ void scan_window(const FrameArgs &f, int frame, int cam, float x, flo
             if (p + 1 < e) inext = ci[p + 1];
             const omv_kp k = kp[i];
             uint64_t d[4];
-            load_desc(dd + (size_t)i * 32, d);
+            omv::load_desc(dd + (size_t)i * 32, d);
             if (checkLevels) {
                 if (k.octave < minL) continue;
                 if (maxL >= 0 && k.octave > maxL) continue;
@@ -311,7 +299,7 @@ __device__ void scan_window_coop(const FrameArgs &f, int frame, int cam, float x
             const int i = ci[b + pos - acc];
             const omv_kp k = kp[i];
             uint64_t d[4];
-            load_desc(dd + (size_t)i * 32, d);
+            omv::load_desc(dd + (size_t)i * 32, d);
             if (checkLevels) {
                 if (k.octave < minL) continue;
                 if (maxL >= 0 && k.octave > maxL) continue;
@@ -445,7 +433,7 @@ __global__ void __launch_bounds__(256, 4) cand_kernel(FrameArgs f, MpArgs m, int
         std::conditional_t<G == 1, TopSeq, Top> t;
         t.reset();
         uint64_t dmp[4];
-        load_desc(m.desc + (size_t)fm * 32, dmp);
+        omv::load_desc(m.desc + (size_t)fm * 32, dmp);
         const float r = window_radius(f, m, bc, c, th, th != 1.0f);
         const uint8_t *occ = occ_init ? occ_init + (size_t)frame * C * f.kp_cap : nullptr;
         if constexpr (G == 1) {
@@ -638,7 +626,7 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
         const size_t fm = (size_t)frame * M + i, bc = fm * C + cam;
         TopSeq t;
         uint64_t dmp[4];
-        load_desc(m.desc + fm * 32, dmp);
+        omv::load_desc(m.desc + fm * 32, dmp);
         const float r = window_radius(f, m, bc, cam, th, th != 1.0f);
         scan_window_lds(f, m.proj_x[bc], m.proj_y[bc], r, m.level[bc] - 1, m.level[bc], dmp, scs, sxy, smeta, sdesc, t);
         store_record(&recs[bc], t);
@@ -682,13 +670,8 @@ struct ResolveArgs {
     int lds_k2m;         // the frame's assignment is kept in LDS (else updated in global memory)
 };
 
-// Each domain wave issues only wave-private LDS traffic on its own slots between its rounds; a wavefront-scope
-// fence orders the wave's own LDS operations (no barrier: the other waves run their own rounds).
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// Between its rounds each domain wave of the resolve kernels issues only wave-private LDS traffic on its own slots,
+// so omv::wave_lds_sync orders it (no workgroup barrier: the other waves run their own rounds).
 
 __device__ __forceinline__ bool bit_of(const uint32_t *bits, int s) { return (bits[s >> 5] >> (s & 31)) & 1u; }
 
@@ -783,7 +766,7 @@ __device__ __forceinline__ uint2 rescan_window_wave(const ResolveArgs &a, int fr
     const MpArgs &m = a.m;
     const size_t bc = fm * f.n_cams + c;
     uint64_t dmp[4];
-    load_desc(m.desc + fm * 32, dmp);
+    omv::load_desc(m.desc + fm * 32, dmp);
     const float x = m.proj_x[bc], y = m.proj_y[bc], r = window_radius(f, m, bc, c, a.th, a.th != 1.0f);
     const int minL = lvl - 1, maxL = lvl;
     Top2 t;
@@ -826,7 +809,7 @@ __device__ __forceinline__ uint2 rescan_window_wave(const ResolveArgs &a, int fr
             const int i = ci[p];
             const omv_kp k = kp[i];
             uint64_t d[4];
-            load_desc(dd + (size_t)i * 32, d);
+            omv::load_desc(dd + (size_t)i * 32, d);
             if (checkLevels) {
                 if (k.octave < minL) continue;
                 if (maxL >= 0 && k.octave > maxL) continue;
@@ -1016,7 +999,7 @@ __device__ __forceinline__ void run_domain(const ResolveArgs &a, const ResolveSh
             tail += __popcll(bm);
             fscan += 64;
         }
-        wave_sync();
+        omv::wave_lds_sync();
     };
     // register prefetch of a block's records (lane l: member point l of the block)
     RegRec cur[NC], nxt[NC];
@@ -1113,7 +1096,7 @@ __device__ __forceinline__ void run_domain(const ResolveArgs &a, const ResolveSh
                 for (int q = 0; q < 2 * NC; ++q)
                     if (v.claim[q] >= 0) atomicMin(&sh.owner[v.claim[q]], keyA);
             }
-            wave_sync();
+            omv::wave_lds_sync();
             bool conflict = false;
             if (active && lane > start) {
                 conflict = v.fallback;   // a full rescan saw the whole window: only safe at the batch head
@@ -1139,7 +1122,7 @@ __device__ __forceinline__ void run_domain(const ResolveArgs &a, const ResolveSh
                 for (int q = 0; q < 2 * NC; ++q)
                     if (v.claim[q] >= 0) atomicMin(&sh.owner[v.claim[q]], keyB);
             }
-            wave_sync();
+            omv::wave_lds_sync();
             if (committed) {
 #pragma unroll
                 for (int q = 0; q < 2 * NC; ++q) {
@@ -1161,7 +1144,7 @@ __device__ __forceinline__ void run_domain(const ResolveArgs &a, const ResolveSh
             }
             phase -= 2;
             start = j0;
-            wave_sync();
+            omv::wave_lds_sync();
             OMV_TP(3);
 #ifdef OMV_RESOLVE_PROFILE
             ++nrounds;
@@ -1275,14 +1258,14 @@ __global__ void __launch_bounds__(256) knn2_kernel(KnnArgs a, int n_pairs) {
     const int qi = blockIdx.x * QB + threadIdx.x / G;
     if (blockIdx.x * QB >= max(nq, 0)) return;   // block-uniform
     uint64_t dq[4] = {0, 0, 0, 0};
-    if (qi < nq) load_desc(a.q + pair * a.q_stride + (size_t)(qo + qi) * 32, dq);
+    if (qi < nq) omv::load_desc(a.q + pair * a.q_stride + (size_t)(qo + qi) * 32, dq);
     // keys (distance << 32 | index): "none" = (INT_MAX, -1) sorts last
     uint64_t k0 = ~0ull >> 1, k1 = ~0ull >> 1;
     int d0 = INT_MAX, d1 = INT_MAX, i0 = -1, i1 = -1;
     for (int b = 0; b < nt; b += 256) {
         __syncthreads();
         const int j = b + threadIdx.x;
-        if (j < nt) load_desc(a.t + pair * a.t_stride + (size_t)(to + j) * 32, tile[threadIdx.x]);
+        if (j < nt) omv::load_desc(a.t + pair * a.t_stride + (size_t)(to + j) * 32, tile[threadIdx.x]);
         __syncthreads();
         const int e = min(256, nt - b);
         for (int k = g; k < e; k += G) {
@@ -1398,18 +1381,7 @@ __global__ void __launch_bounds__(256) frustum_kernel(const omv_frame_pose *pose
         if (Pc[2] >= 0.0f) {
             const float *k = rig.cam[c];
             float u, v;
-            if (rig.model[c] == OMV_CAM_PINHOLE) {   // Pinhole::project(Vector3f) (Pinhole.cpp:26-32)
-                u = k[0] * Pc[0] / Pc[2] + k[2];
-                v = k[1] * Pc[1] / Pc[2] + k[3];
-            } else {                                 // KannalaBrandt8::project(Vector3f)
-                const float x2y2 = Pc[0] * Pc[0] + Pc[1] * Pc[1];
-                const float theta = omv::glibc_atan2f(omv::sqrtf_cr(x2y2), Pc[2]);
-                const float psi = omv::glibc_atan2f(Pc[1], Pc[0]);
-                const float t2 = theta * theta, t3 = theta * t2, t5 = t3 * t2, t7 = t5 * t2, t9 = t7 * t2;
-                const float r = theta + k[4] * t3 + k[5] * t5 + k[6] * t7 + k[7] * t9;
-                u = (float)((double)(k[0] * r) * cos((double)psi) + (double)k[2]);
-                v = (float)((double)(k[1] * r) * sin((double)psi) + (double)k[3]);
-            }
+            omv::cam_project_f(rig.model[c], k, Pc, u, v);
             if (!(u < rig.min_x || u > rig.max_x || v < rig.min_y || v > rig.max_y)) {
                 const float maxD = 1.2f * maxd, minD = 0.8f * mind;
                 const float PO[3] = {P[0] - twc[c][0], P[1] - twc[c][1], P[2] - twc[c][2]};
@@ -1471,27 +1443,6 @@ __device__ __forceinline__ void se3_apply(const omv_se3f &T, const float *p, flo
     quat_rotate(T.q, p, r);
     for (int i = 0; i < 3; ++i) r[i] = r[i] + T.t[i];
 }
-// KannalaBrandt8::project(const Eigen::Vector3f&) (KannalaBrandt8.cpp:48-67)
-__device__ __forceinline__ void kb8_project_f(const float *k, const float *X, float &u, float &v) {
-    const float x2y2 = X[0] * X[0] + X[1] * X[1];
-    const float theta = omv::glibc_atan2f(omv::sqrtf_cr(x2y2), X[2]);
-    const float psi = omv::glibc_atan2f(X[1], X[0]);
-    const float t2 = theta * theta, t3 = theta * t2, t5 = t3 * t2, t7 = t5 * t2, t9 = t7 * t2;
-    const float r = theta + k[4] * t3 + k[5] * t5 + k[6] * t7 + k[7] * t9;
-    u = (float)((double)(k[0] * r) * cos((double)psi) + (double)k[2]);
-    v = (float)((double)(k[1] * r) * sin((double)psi) + (double)k[3]);
-}
-// GeometricCamera::project(const Eigen::Vector3f&) by the block's camera type: KannalaBrandt8, or
-// Pinhole::project (Pinhole.cpp:26-32: fx * x / z + cx in float, left to right)
-__device__ __forceinline__ void cam_project_f(int model, const float *k, const float *X, float &u, float &v) {
-    if (model == OMV_CAM_PINHOLE) {
-        u = k[0] * X[0] / X[2] + k[2];
-        v = k[1] * X[1] / X[2] + k[3];
-    } else {
-        kb8_project_f(k, X, u, v);
-    }
-}
-
 // Window of last slot s in block c of frame `frame`: false if the point is skipped entirely.
 __device__ bool lf_window(const FrameArgs &f, const LastArgs &L, const LfGeo &G, const omv_se3f &Tcw,
                           const omv_se3f &Tlw, int frame, int s, int c, float &x, float &y, float &r, int &minL,
@@ -1503,13 +1454,13 @@ __device__ bool lf_window(const FrameArgs &f, const LastArgs &L, const LfGeo &G,
     const float invzc = (float)(1.0 / (double)x3[2]);
     if (invzc < 0) return false;
     float u, v;
-    cam_project_f(f.model[0], G.cam0, x3, u, v);   // CurrentFrame.mpCamera->project (ORBmatcher.cc:2022)
+    omv::cam_project_f(f.model[0], G.cam0, x3, u, v);   // CurrentFrame.mpCamera->project (ORBmatcher.cc:2022)
     if (u < f.min_x || u > f.max_x || v < f.min_y || v > f.max_y) return false;
     x = u, y = v;
     if (c == 1) {
         float xr[3];
         se3_apply(G.Trl, x3, xr);
-        cam_project_f(f.model[0], G.cam0, xr, x, y);   // the same camera on Trl * x3Dc (:2134)
+        omv::cam_project_f(f.model[0], G.cam0, xr, x, y);   // the same camera on Trl * x3Dc (:2134)
     }
     // bForward / bBackward from tlc = Tlw * twc, twc = -(q^-1 t)
     const omv_se3f inv{{-Tcw.q[0], -Tcw.q[1], -Tcw.q[2], Tcw.q[3]}, {0, 0, 0}};
@@ -1541,7 +1492,7 @@ __global__ void __launch_bounds__(256) lf_cand_kernel(FrameArgs f, LastArgs L, L
     int minL, maxL;
     if (lf_window(f, L, G, Tcw[frame], Tlw[frame], frame, s, c, x, y, r, minL, maxL)) {
         uint64_t dmp[4];
-        load_desc(L.desc + (size_t)fs * 32, dmp);
+        omv::load_desc(L.desc + (size_t)fs * 32, dmp);
         const uint8_t *occ = occ_init ? occ_init + (size_t)frame * C * f.kp_cap : nullptr;
         scan_window(f, frame, c, x, y, r, minL, maxL, dmp, [&](int slot) { return occ && occ[slot]; }, t);
     }
@@ -1590,7 +1541,7 @@ __global__ void __launch_bounds__(64) lf_resolve_kernel(LfResolveArgs a) {
         bits[w] = v;
     }
     for (int s = lane; s < S; s += 64) owner[s] = INT_MAX;
-    wave_sync();
+    omv::wave_lds_sync();
     int32_t *k2m = a.kp_to_mp + (size_t)frame * S;
     int2 *push = a.pushes + (size_t)frame * a.L.S * C;
     int total = 0, npush = 0;
@@ -1626,7 +1577,7 @@ __global__ void __launch_bounds__(64) lf_resolve_kernel(LfResolveArgs a) {
                             int minL, maxL;
                             lf_window(f, a.L, a.G, a.Tcw[frame], a.Tlw[frame], frame, s, c, x, y, rr, minL, maxL);
                             uint64_t dmp[4];
-                            load_desc(a.L.desc + fs * 32, dmp);
+                            omv::load_desc(a.L.desc + fs * 32, dmp);
                             TopSeq t;
                             scan_window(f, frame, c, x, y, rr, minL, maxL, dmp,
                                         [&](int slot) { return bit_of(bits, slot); }, t);
@@ -1647,16 +1598,16 @@ __global__ void __launch_bounds__(64) lf_resolve_kernel(LfResolveArgs a) {
             }
             if (obs)
                 for (int q = 0; q < nclaim; ++q) atomicMin(&owner[claim[q]], lane);
-            wave_sync();
+            omv::wave_lds_sync();
             bool conflict = false;
             if (active && lane > start) {
                 conflict = fallback;   // a rescan saw the whole window: only safe at the batch head
                 for (int q = 0; q < nclaim && !conflict; ++q) conflict = owner[claim[q]] < lane;
             }
-            wave_sync();
+            omv::wave_lds_sync();
             if (obs)
                 for (int q = 0; q < nclaim; ++q) owner[claim[q]] = 64;
-            wave_sync();
+            omv::wave_lds_sync();
             uint64_t cm = __ballot(conflict);
             const uint64_t um = __ballot(active && unblock);
             if (um) {
@@ -1681,7 +1632,7 @@ __global__ void __launch_bounds__(64) lf_resolve_kernel(LfResolveArgs a) {
             }
             npush += ptot;
             total += ptot;
-            wave_sync();
+            omv::wave_lds_sync();
             if (committed)
                 for (int q = 0; q < nclaim; ++q) {
                     const int slot = claim[q];
@@ -1690,11 +1641,11 @@ __global__ void __launch_bounds__(64) lf_resolve_kernel(LfResolveArgs a) {
                     if (obs) atomicOr(&bits[slot >> 5], 1u << (slot & 31));
                     else atomicAnd(&bits[slot >> 5], ~(1u << (slot & 31)));
                 }
-            wave_sync();
+            omv::wave_lds_sync();
             if (committed)
                 for (int q = 0; q < nclaim; ++q) owner[claim[q]] = 64;
             start = j0;
-            wave_sync();
+            omv::wave_lds_sync();
             (void)lt;
         }
     }
@@ -1828,7 +1779,7 @@ __global__ void __launch_bounds__(256) kf_cand_kernel(KfArgs a) {
         se3_apply(J.Tcw, P, Pc);
         if (mode != OMV_KF_SBP_FRAME && Pc[2] < 0.0f) break;   // depth must be positive
         float u, v;
-        cam_project_f(a.f.model[cam], a.cams[cam], Pc, u, v);   // pCamera / GetCamera(camId) (:1536, :1710, :2443)
+        omv::cam_project_f(a.f.model[cam], a.cams[cam], Pc, u, v);   // pCamera / GetCamera(camId) (:1536, :1710, :2443)
         if (mode == OMV_KF_SBP_FRAME) {   // CurrentFrame.mnMinX .. mnMaxX, inclusive
             if (u < a.f.min_x || u > a.f.max_x || v < a.f.min_y || v > a.f.max_y) break;
         } else if (!(u >= a.f.min_x && u < a.f.max_x && v >= a.f.min_y && v < a.f.max_y)) {   // KeyFrame::IsInImage
@@ -1851,7 +1802,7 @@ __global__ void __launch_bounds__(256) kf_cand_kernel(KfArgs a) {
         int minL, maxL;
         kf_levels(mode, pred, minL, maxL);
         uint64_t dmp[4];
-        load_desc(a.mps.desc + (size_t)mp * 32, dmp);
+        omv::load_desc(a.mps.desc + (size_t)mp * 32, dmp);
         const int32_t *cl = claim ? a.kp_match + (size_t)kf * C * cap : nullptr;
         const omv_kp *kk = a.f.kps + (size_t)kf * C * cap;
         const float *urow = a.uright ? a.uright + (size_t)kf * cap : nullptr;
@@ -1911,7 +1862,7 @@ __global__ void __launch_bounds__(64) kf_resolve_kernel(KfArgs a) {
         }
         claimed[w] = bits;
     }
-    wave_sync();
+    omv::wave_lds_sync();
     const bool ori = a.mode == OMV_KF_SBP_FRAME && a.check_ori;
     for (int j = 0; j < a.n_jobs; ++j) {
         const omv_kf_search_job &J = a.jobs[j];
@@ -1920,7 +1871,7 @@ __global__ void __launch_bounds__(64) kf_resolve_kernel(KfArgs a) {
         const omv_kp *kk = a.f.kps + (size_t)kf * S;
         int nm = 0;
         if (lane < 30) hist[lane] = 0;
-        wave_sync();
+        omv::wave_lds_sync();
         for (int e = J.mp_start; e < J.mp_start + J.mp_count; ++e) {
             const int cnt = a.counts[e];
             int idx = -1, dist = 0;
@@ -1938,7 +1889,7 @@ __global__ void __launch_bounds__(64) kf_resolve_kernel(KfArgs a) {
                         int minL, maxL;
                         kf_levels(a.mode, __float_as_int(g.w), minL, maxL);
                         uint64_t dmp[4];
-                        load_desc(a.mps.desc + (size_t)a.mp_list[e] * 32, dmp);
+                        omv::load_desc(a.mps.desc + (size_t)a.mp_list[e] * 32, dmp);
                         TopSeq t;
                         scan_window(a.f, kf, cam, g.x, g.y, g.z, minL, maxL, dmp,
                                     [&](int slot) { return bit_of(claimed, slot); }, t);
@@ -1960,7 +1911,7 @@ __global__ void __launch_bounds__(64) kf_resolve_kernel(KfArgs a) {
                 }
             }
             nm += ok ? 1 : 0;
-            wave_sync();
+            omv::wave_lds_sync();
         }
         if (ori) {   // ComputeThreeMaxima (:2537-2573), then un-claim the matches outside the top bins
             if (lane == 0) {
@@ -1986,7 +1937,7 @@ __global__ void __launch_bounds__(64) kf_resolve_kernel(KfArgs a) {
                 }
             }
             nm = __shfl(nm, 0, 64);
-            wave_sync();
+            omv::wave_lds_sync();
         }
         if (lane == 0) a.n_matches[j] = nm;
     }
@@ -2062,7 +2013,7 @@ __global__ void __launch_bounds__(256) sbs3_cand_kernel(Sim3Args a) {
         pred = pred < 0 ? 0 : (pred >= a.n_levels ? a.n_levels - 1 : pred);
         const float radius = a.th * a.f.scale[pred];
         uint64_t dmp[4];
-        load_desc(a.mps.desc + (size_t)mp * 32, dmp);
+        omv::load_desc(a.mps.desc + (size_t)mp * 32, dmp);
         TopSeq t;
         scan_window(a.f, tgt, 0, u, v, radius, pred - 1, pred, dmp, [](int) { return false; }, t);
         if (t.n > 0 && t.dist(0) <= kTH_HIGH) best = t.idx(0);   // block 0: the N-index is the block index
@@ -2171,7 +2122,7 @@ __device__ __forceinline__ void init_window_scan(const FrameArgs &f, const int32
         if (k.octave != 0) continue;   // levels [0, 0]
         if (!(fabsf(k.x - x) < r && fabsf(k.y - y) < r)) continue;
         uint64_t d2[4];
-        load_desc(ds2 + (size_t)i2 * 32, d2);
+        omv::load_desc(ds2 + (size_t)i2 * 32, d2);
         const int dist = omv::hamming256(d1, d2);
         if (mdist && mdist[i2] <= dist) continue;
         const uint32_t key = ((uint32_t)dist << 16) | (uint32_t)pos;   // unique: distinct window positions
@@ -2211,7 +2162,7 @@ __global__ void __launch_bounds__(256) init_spec_kernel(InitArgs a) {
     if (k1.octave == 0) {
         const float *prev = a.prev + ((size_t)pr * cap + i1) * 2;
         uint64_t d1[4];
-        load_desc(f.desc + (fc1 * cap + i1) * 32, d1);
+        omv::load_desc(f.desc + (fc1 * cap + i1) * 32, d1);
         init_window_scan<kInitSpec>(f, f.cell_start + fc2 * (kCells + 1), f.cell_idx + fc2 * cap, f.kps + fc2 * cap,
                                     f.desc + fc2 * cap * 32, d1, prev[0], prev[1], (float)a.window, nullptr, lane, k, id);
     }
@@ -2252,7 +2203,7 @@ __global__ void __launch_bounds__(64) init_kernel(InitArgs a) {
     auto stage = [&](int i0) {
         const int m = min(kInitChunk, n1 - i0) * 4;
         for (int q = lane; q < m; q += 64) sbuf[q] = spec[4 * i0 + q];
-        wave_sync();
+        omv::wave_lds_sync();
     };
     // lane t < kInitSpec holds key t and its F2 index; the checks against the claims are one LDS load per lane
     const uint32_t *sb = reinterpret_cast<const uint32_t *>(sbuf);
@@ -2290,7 +2241,7 @@ __global__ void __launch_bounds__(64) init_kernel(InitArgs a) {
         const int found = __popcll(ok);
         if (found < 2 && (uint32_t)__builtin_amdgcn_readlane((int)mykey, kInitSpec - 1) != kNoKey) {   // filtered scan
             uint64_t d1[4];
-            load_desc(ds1 + (size_t)i1 * 32, d1);
+            omv::load_desc(ds1 + (size_t)i1 * 32, d1);
             init_window_scan<2>(f, cs, ci, kp2, ds2, d1, prev[2 * i1], prev[2 * i1 + 1], r, mdist, lane, g, bi);
             if (g[0] != kNoKey) old = m21[bi[0]];
         }
@@ -2304,7 +2255,7 @@ __global__ void __launch_bounds__(64) init_kernel(InitArgs a) {
                 m12[i1] = bestIdx2, m21[bestIdx2] = i1, mdist[bestIdx2] = bestDist, acc2[i1] = bestIdx2;
             }
         }
-        wave_sync();   // the claim state before the next F1 keypoint (one wavefront, LDS only)
+        omv::wave_lds_sync();   // the claim state before the next F1 keypoint (one wavefront, LDS only)
     }
     if (a.check_ori) {   // ComputeThreeMaxima, then every push outside the top bins that is still matched
         // the rotation histogram of every accept (each F1 keypoint is accepted at most once, so its bin is a

@@ -100,7 +100,30 @@ __device__ __forceinline__ int reflect101(int p, int n) {
 __device__ __forceinline__ int hamming256(const uint64_t *a, const uint64_t *b) {
     return __popcll(a[0] ^ b[0]) + __popcll(a[1] ^ b[1]) + __popcll(a[2] ^ b[2]) + __popcll(a[3] ^ b[3]);
 }
+// A 32-byte descriptor (8-byte aligned) as 4 x u64.
+__device__ __forceinline__ void load_desc(const uint8_t *p, uint64_t d[4]) {
+    const uint64_t *q = reinterpret_cast<const uint64_t *>(p);
+    d[0] = q[0], d[1] = q[1], d[2] = q[2], d[3] = q[3];
+}
 
+// Wave-synchronous step over LDS: other lanes read what this wave just wrote.  A wavefront's LDS operations complete
+// in order, so a wavefront-scope fence (it only has to stop the compiler) and no workgroup barrier: the other waves
+// run their own rounds on their own slots.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// 1 / x by v_rcp_f64 and two Newton steps (within an ulp of the IEEE quotient on normal numbers; a zero / non-finite
+// argument is the caller's to flag)
+__device__ __forceinline__ double rcp_nr(double x) {
+    double r = __builtin_amdgcn_rcp(x);
+    double e = __builtin_fma(-x, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    e = __builtin_fma(-x, r, 1.0);
+    return __builtin_fma(r, e, r);
+}
 
 // glibc atan2f (fdlibm e_atan2f.c / s_atanf.c), float, no contraction.  KannalaBrandt8::project
 // computes theta / psi with atan2f (KannalaBrandt8.cpp:30-31, :50-51); this restatement is

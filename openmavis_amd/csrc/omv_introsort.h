@@ -187,6 +187,7 @@ OMV_HD inline void libstdcxx_sort(SortItem *arr, int n, int *stack) {
 // and the (rare) heapsort fallback run on lane 0.
 // block_final_insertion_sort: __final_insertion_sort is a stable insertion sort of the whole range, i.e.
 // item i goes to rank #{j : (k1, k2, j) < (k1_i, k2_i, i)}; every thread of the block ranks its items.
+// omv_device.h's wave_lds_sync, restated: this header stands alone (tests/test_native_cpu.py compiles it for the host)
 __device__ __forceinline__ void sort_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

@@ -32,6 +32,7 @@
 
 #include "../../include/omv.h"
 #include "omv_device.h"
+#include "omv_host.h"
 #include "omv_introsort.h"
 
 namespace {
@@ -1176,13 +1177,6 @@ constexpr int kDescDw = kHCols * kHStride > kRawRows * kRawDw ? kHCols * kHStrid
 typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte access, dword-aligned
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void wave_lds_sync() {
-    // other lanes read what this wave just wrote: a wave's LDS operations complete in order; keep the compiler's too
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 __global__ void __launch_bounds__(256) describe_kernel(Geom g, DescArgs a, int n_blocks) {
@@ -1253,7 +1247,7 @@ __global__ void __launch_bounds__(256) describe_kernel(Geom g, DescArgs a, int n
             raw[i] = v;
         }
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
     // intensity centroid: lane = (disc row vr = lane >> 1, half h = lane & 1) = bytes cx-15+16h .. +15 of row
     // cy-15+vr (raw row 6 + vr, raw byte po + 6 + 16h) as four dot4 items over five LDS dwords; lanes 62, 63 and
     // the bytes outside the disc have zero masks
@@ -1322,7 +1316,7 @@ __global__ void __launch_bounds__(256) describe_kernel(Geom g, DescArgs a, int n
             for (int t = 0; t < 3; ++t)
                 av[rt][t] = *reinterpret_cast<const uint64_t *>(rawb + (16 * rt + (lane & 15)) * (4 * kRawDw) + 16 * t +
                                                                 8 * (lane >> 4));
-        wave_lds_sync();   // every lane's patch reads before any sum overwrites the patch
+        omv::wave_lds_sync();   // every lane's patch reads before any sum overwrites the patch
 #pragma unroll
         for (int rt = 0; rt < 3; ++rt) {
 #pragma unroll
@@ -1342,7 +1336,7 @@ __global__ void __launch_bounds__(256) describe_kernel(Geom g, DescArgs a, int n
     float sn, cs;
     omv::glibc_sincosf(angle * (float)(3.14159265358979323846 / 180.f), &sn, &cs);
     const float fa = cs, fb = sn;
-    wave_lds_sync();   // the horizontal sums of every lane are in LDS
+    omv::wave_lds_sync();   // the horizontal sums of every lane are in LDS
     // the blurred pixel at (cx + dx, cy + dy), |dx|, |dy| <= 18: column dx + 18, sum rows R0 = dy + 18 .. R0 + 6
     // = the four pair dwords from R0 >> 1, realigned by a half when R0 is odd
     auto blurred = [&](int dx, int dy) -> uint32_t {
@@ -1387,15 +1381,6 @@ __global__ void __launch_bounds__(256) describe_kernel(Geom g, DescArgs a, int n
 }
 
 // ---------------------------------------------------------------------------------------------
-#define HIP_OK(x)                                                                    \
-    do {                                                                             \
-        hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) {                                                      \
-            fprintf(stderr, "omv: %s failed: %s\n", #x, hipGetErrorString(e_));      \
-            return OMV_ERR_HIP;                                                      \
-        }                                                                            \
-    } while (0)
-
 inline int host_round_even(float v) { return (int)std::nearbyint(v); }
 
 // Test hook: the octree's device sort (wave_introsort_loop + block_final_insertion_sort) on one array.

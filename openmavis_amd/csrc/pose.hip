@@ -40,19 +40,11 @@
 #include "../../include/omv.h"
 #include "g2o_types.h"
 #include "omv_device.h"
+#include "omv_host.h"
 
 namespace {
 
 using namespace omv_g2o;
-
-#define HIP_OK(x)                                                                    \
-    do {                                                                             \
-        hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) {                                                      \
-            fprintf(stderr, "omv: %s failed: %s\n", #x, hipGetErrorString(e_));      \
-            return OMV_ERR_HIP;                                                      \
-        }                                                                            \
-    } while (0)
 
 constexpr int kPoseThreads = 256;
 constexpr int kPoseWaves = kPoseThreads / 64;
@@ -115,7 +107,7 @@ __global__ void __launch_bounds__(64) pose_constraint_kernel(const double *Hin, 
         const double v = r >= c ? hi[q] : hi[c * 15 + r];
         A[q] = (v + v) / 2;
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
     // Every eigenvalue above 1e-12 (A - tau I factors with positive pivots, tau = 1e-12 plus a margin for the
     // factorisation's rounding): the projection is A itself (V diag(w) V^T = A up to rounding)
     const double tau = 1e-12 + 1e-12 * max_abs_diag<15>(A, lane);
@@ -545,7 +537,7 @@ __global__ void __launch_bounds__(kPoseThreads, 2) pose_opt_kernel(Rig rig, Pose
                         for (int q = 0; q < N; ++q) xs[q] = xt[q];
                     s_ok = ok ? 1 : 0;
                 }
-                wave_lds_sync();
+                omv::wave_lds_sync();
                 // VertexPose::oplusImpl -> ImuCamPose::Update (G2oTypes.cc:211-235): lane 0 the frame (with its
                 // cameras), lane 1 the previous frame (LastFrame; its cameras are not read)
                 if (tid == 0 || (kLF && tid == 1)) {
@@ -843,7 +835,7 @@ __device__ __attribute__((noinline)) bool lat_exchange(gu64 *fb, int phase, uint
     for (int m = 0; m < L; ++m) s = m < np ? s + val[m] : s;
     s += __shfl_xor(s, 32, 64);
     if (h == 0 && q < n) out[q] = s;
-    wave_lds_sync();
+    omv::wave_lds_sync();
 #ifdef OMV_POSE_PROFILE
     if (g == 0 && lane == 0) {
         const unsigned long long tx2 = wall_clock64();
@@ -865,54 +857,6 @@ __device__ __attribute__((noinline)) bool lat_exchange(gu64 *fb, int phase, uint
 //   solve       y = P b, L y' = y, y'' = D^+ y', L^T x = y'', x = P^T (same per-element subtraction order as Eigen's
 //               triangular solves; the factor differs from Eigen's by rounding: right-looking, fused multiply-adds)
 // x: LDS out (written only on success); pick / Lm: LDS scratch [N] / [N * N].  Returns isPositive().
-// 1 / x by v_rcp_f64 and two Newton steps (the LBA's reciprocal: exact on sampled arguments, a few ulp at worst).
-__device__ __forceinline__ double rcp_nr(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    double e = __builtin_fma(-x, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-x, r, 1.0);
-    return __builtin_fma(r, e, r);
-}
-
-// Eigen's pick order of the N x N symmetric H into pick[] (one wavefront); false on a NaN diagonal.
-template <int N>
-__device__ __forceinline__ bool ldlt_pick_order(const double *H, int *pick, int lane) {
-    static_assert(N <= 32, "rows on lanes 0..31");
-    const bool in = lane < N;
-    const double dv = in ? fabs(H[lane * (N + 1)]) : 0.0;
-    int gt = 0, eq = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const double o = fabs(H[j * (N + 1)]);
-        gt += o > dv ? 1 : 0;
-        eq += o == dv ? 1 : 0;
-    }
-    if (__ballot(in && !(dv == dv))) return false;
-    if (!__ballot(in && eq > 1)) {
-        if (in) pick[gt] = lane;
-    } else {
-        int pos = lane;
-        bool picked = false;
-        for (int k = 0; k < N; ++k) {
-            uint64_t cand = __ballot(in && !picked && gt <= k && k < gt + eq);
-            int e = __builtin_ctzll(cand);
-            if (cand & (cand - 1)) {
-                int bp = __builtin_amdgcn_readlane(pos, e);
-                for (uint64_t m = cand & (cand - 1); m; m &= m - 1) {
-                    const int c = __builtin_ctzll(m), pc = __builtin_amdgcn_readlane(pos, c);
-                    if (pc < bp) bp = pc, e = c;
-                }
-            }
-            const int xk = __builtin_ctzll(__ballot(in && pos == k));
-            const int pe = __builtin_amdgcn_readlane(pos, e);
-            if (lane == xk) pos = pe;
-            if (lane == e) pos = k, picked = true;
-            if (lane == 0) pick[k] = e;
-        }
-    }
-    return true;
-}
-
 template <int N>
 __device__ __forceinline__ bool ldlt_pick_solve(const double *H, const double *b, double *x, int *pick, double *Lm, int lane) {
     static_assert(N <= 32, "rows on lanes 0..31");
@@ -948,7 +892,7 @@ __device__ __forceinline__ bool ldlt_pick_solve(const double *H, const double *b
             if (lane == 0) pick[k] = e;
         }
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
     const int pi = in ? pick[lane] : 0;
     int pj[N];   // the pick order in registers first, then every row read back to back (H symmetric: column pi of row pj)
 #pragma unroll
@@ -958,7 +902,7 @@ __device__ __forceinline__ bool ldlt_pick_solve(const double *H, const double *b
     for (int j = 0; j < N; ++j) r[j] = in ? H[pj[j] * N + pi] : 0.0;
     if (!(lane_f64(r[0], 0) != 0.0)) {   // largest |diagonal| zero: Eigen stops with ZeroSign; the solve gives x = 0
         if (in) x[lane] = 0.0;
-        wave_lds_sync();
+        omv::wave_lds_sync();
         return true;
     }
     // One basic block for the whole factorisation (no data-dependent branches) so the pivot chain of step k + 1 can
@@ -971,7 +915,7 @@ __device__ __forceinline__ bool ldlt_pick_solve(const double *H, const double *b
         const double d = lane_f64(r[k], k);
         dmine = lane == k ? d : dmine;
         const bool nz = fabs(d) > 0.0;
-        const double inv = nz ? rcp_nr(d) : 0.0;
+        const double inv = nz ? omv::rcp_nr(d) : 0.0;
         const bool below = lane > k;
         const double l = below ? r[k] * inv : 0.0;
 #pragma unroll
@@ -990,7 +934,7 @@ __device__ __forceinline__ bool ldlt_pick_solve(const double *H, const double *b
     if (in)
 #pragma unroll
         for (int j = 0; j < N; ++j) Lm[lane * N + j] = r[j];
-    wave_lds_sync();
+    omv::wave_lds_sync();
 #pragma unroll
     for (int j = 0; j < N; ++j) r[j] = in ? Lm[j * N + lane] : 0.0;   // r[j] = L_j,lane
 #pragma unroll
@@ -999,216 +943,7 @@ __device__ __forceinline__ bool ldlt_pick_solve(const double *H, const double *b
         if (lane < j) y = __builtin_fma(-r[j], xj, y);
     }
     if (in) x[pi] = y;
-    wave_lds_sync();
-    return true;
-}
-
-// The same solve by the whole workgroup (NT threads), for the latency kernel where the other waves would idle: the
-// pick order on wave 0 as ldlt_pick_solve; the factorisation of P H P^T element-parallel on its lower triangle (thread
-// t owns elements t, t + NT, ... in registers), one workgroup barrier per pivot step: the owners of column k publish
-// it to LDS (two buffers by step parity, so a step needs no second barrier), every thread reads D_k and its rows'
-// entries and applies a_ij -= (a_ik / D_k) a_jk (a zero pivot: no update, column left unscaled, as ldlt_pick_solve);
-// then the triangular solves on wave 0 from the factor staged in Lm.  isPositive() = no negative pivot.  The
-// factor's rounding differs from ldlt_pick_solve's in the update's operand (lower-triangle column entries for both
-// factors) only.  Called by all NT threads; x written on success.  col: LDS scratch [2 * N]; flag: LDS int.
-template <int N, int NT>
-__device__ __forceinline__ bool ldlt_elem_solve(const double *H, const double *b, double *x, int *pick, double *Lm,
-                                                double *col, int *flag, int tid) {
-    constexpr int T = N * (N + 1) / 2, PER = (T + NT - 1) / NT;
-    const int lane = tid & 63;
-    if (tid < 64) {
-        const bool okp = ldlt_pick_order<N>(H, pick, lane);
-        if (lane == 0) *flag = okp ? 0 : 1;
-    }
-    __syncthreads();
-    if (*flag) return false;   // a NaN diagonal (uniform)
-    int ei[PER], ej[PER];
-    double a[PER];
-#pragma unroll
-    for (int p = 0; p < PER; ++p) {
-        const int e = tid + p * NT;
-        // row i of the packed lower triangle: i (i + 1) / 2 <= e
-        int i = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-        i += (i + 1) * (i + 2) / 2 <= e ? 1 : 0;
-        i -= i * (i + 1) / 2 > e ? 1 : 0;
-        const int j = e - i * (i + 1) / 2;
-        ei[p] = e < T ? i : N, ej[p] = e < T ? j : N;
-        a[p] = e < T ? H[pick[i] * N + pick[j]] : 0.0;
-    }
-    if (!(H[pick[0] * (N + 1)] != 0.0)) {   // largest |diagonal| zero: x = 0
-        if (tid < N) x[tid] = 0.0;
-        __syncthreads();
-        return true;
-    }
-    int sign = 0;
-    for (int k = 0; k < N; ++k) {
-        double *c = col + (k & 1) * N;
-#pragma unroll
-        for (int p = 0; p < PER; ++p)
-            if (ej[p] == k) c[ei[p]] = a[p];
-        __syncthreads();
-        const double d = c[k];
-        const bool nz = fabs(d) > 0.0;
-        const double inv = nz ? rcp_nr(d) : 0.0;
-        sign |= (d > 0 ? 1 : 0) | (d < 0 ? 2 : 0);
-#pragma unroll
-        for (int p = 0; p < PER; ++p) {
-            if (ej[p] > k && ej[p] < N) a[p] = __builtin_fma(-(c[ei[p]] * inv), c[ej[p]], a[p]);
-            else if (ej[p] == k && ei[p] > k && nz) a[p] = a[p] * inv;
-        }
-    }
-    if (sign & 2) return false;   // uniform: every thread saw every pivot
-#pragma unroll
-    for (int p = 0; p < PER; ++p)
-        if (ei[p] < N) Lm[ei[p] * N + ej[p]] = a[p];
-    __syncthreads();
-    if (tid < 64) {
-        const bool in = lane < N;
-        const int pi = in ? pick[lane] : 0;
-        double r[N];
-#pragma unroll
-        for (int j = 0; j < N; ++j) r[j] = (in && j <= lane) ? Lm[lane * N + j] : 0.0;   // row lane of L, D on the diagonal
-        const double dmine = in ? Lm[lane * (N + 1)] : 0.0;
-        double y = in ? b[pi] : 0.0;
-#pragma unroll
-        for (int k = 0; k + 1 < N; ++k) {
-            const double yk = lane_f64(y, k);
-            if (lane > k) y = __builtin_fma(-r[k], yk, y);
-        }
-        y = fabs(dmine) > 2.2250738585072014e-308 ? y / dmine : 0.0;
-#pragma unroll
-        for (int j = 0; j < N; ++j) r[j] = (in && j > lane) ? Lm[j * N + lane] : 0.0;   // r[j] = L_j,lane
-#pragma unroll
-        for (int j = N - 1; j >= 1; --j) {
-            const double xj = lane_f64(y, j);
-            if (lane < j) y = __builtin_fma(-r[j], xj, y);
-        }
-        if (in) x[pi] = y;
-    }
-    __syncthreads();
-    return true;
-}
-
-// The same solve with the factorisation spread over the whole wavefront: the NP x NP padded matrix (NP = 16 or 32) is
-// held P = 64 / NP lanes per row (lane = row + NP * s holds columns s, s + P, ...: R = NP / P registers), so a step's
-// trailing update is R FMAs per lane instead of N.  Step k: the lanes holding column k publish it to LDS (one store),
-// every lane reads its row's entry (the multiplier) and the entries of its own columns (the pivot row, by symmetry the
-// pivot column) and updates; the triangular solves run row-per-lane from the factor staged in LDS.  Pick order, zero
-// pivots, isPositive() and the D pseudo-inverse as ldlt_pick_solve.  cb: LDS scratch [NP].
-template <int N>
-__device__ __forceinline__ bool ldlt_pick_solve_wide(const double *H, const double *b, double *x, int *pick, double *Lm,
-                                                     double *cb, int lane) {
-    constexpr int NP = N <= 16 ? 16 : 32, P = 64 / NP, R = NP / P;
-    static_assert(N <= 32, "at most 32 states");
-    const bool in = lane < N;
-    const double dv = in ? fabs(H[lane * (N + 1)]) : 0.0;
-    int gt = 0, eq = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const double o = fabs(H[j * (N + 1)]);
-        gt += o > dv ? 1 : 0;
-        eq += o == dv ? 1 : 0;
-    }
-    if (__ballot(in && !(dv == dv))) return false;   // a NaN diagonal: no factorisation
-    if (!__ballot(in && eq > 1)) {
-        if (in) pick[gt] = lane;
-    } else {   // selection with positional swaps, lanes = elements (pos = current position)
-        int pos = lane;
-        bool picked = false;
-        for (int k = 0; k < N; ++k) {
-            uint64_t cand = __ballot(in && !picked && gt <= k && k < gt + eq);
-            int e = __builtin_ctzll(cand);
-            if (cand & (cand - 1)) {   // several equal magnitudes: the lowest current position
-                int bp = __builtin_amdgcn_readlane(pos, e);
-                for (uint64_t m = cand & (cand - 1); m; m &= m - 1) {
-                    const int c = __builtin_ctzll(m), pc = __builtin_amdgcn_readlane(pos, c);
-                    if (pc < bp) bp = pc, e = c;
-                }
-            }
-            const int xk = __builtin_ctzll(__ballot(in && pos == k));
-            const int pe = __builtin_amdgcn_readlane(pos, e);
-            if (lane == xk) pos = pe;
-            if (lane == e) pos = k, picked = true;
-            if (lane == 0) pick[k] = e;
-        }
-    }
-    wave_lds_sync();
-    const int row = lane & (NP - 1), sub = lane / NP;
-    const bool rin = row < N;
-    const int pr = rin ? pick[row] : 0;
-    double r[R];
-#pragma unroll
-    for (int m = 0; m < R; ++m) {
-        const int j = sub + P * m;
-        r[m] = (rin && j < N) ? H[pr * N + pick[j < N ? j : 0]] : 0.0;
-    }
-    if (!(lane_f64(r[0], 0) != 0.0)) {   // largest |diagonal| zero: Eigen stops with ZeroSign; the solve gives x = 0
-        if (in) x[lane] = 0.0;
-        wave_lds_sync();
-        return true;
-    }
-    int sign = 0;   // 0 ZeroSign, 1 PositiveSemiDef, 2 NegativeSemiDef, 3 Indefinite
-    double dmine = 0.0;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        constexpr int dummy = 0;
-        (void)dummy;
-        const int ck = k % P, mk = k / P;
-        if (sub == ck) cb[row] = r[mk];   // column k (= row k) of the current matrix, rows >= N publish 0
-        wave_lds_sync();
-        const double d = cb[k];
-        if (row == k) dmine = d;
-        if (fabs(d) > 0.0) {
-            const double inv = 1.0 / d;
-            const double l = row > k ? cb[row] * inv : 0.0;
-            const int m0 = (k + 1) / P;
-#pragma unroll
-            for (int m = m0; m < R; ++m) {
-                const int j = sub + P * m;
-                const double lj = (m == m0 && j <= k) ? 0.0 : l;   // the boundary register: columns <= k are L's
-                r[m] = __builtin_fma(-lj, cb[j], r[m]);
-            }
-            if (sub == ck && row > k) r[mk] = l;
-        }
-        wave_lds_sync();   // cb is rewritten by the next step
-        if (sign == 1) {
-            if (d < 0) sign = 3;
-        } else if (sign == 2) {
-            if (d > 0) sign = 3;
-        } else if (sign == 0) {
-            if (d > 0) sign = 1;
-            else if (d < 0) sign = 2;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    if (rin)
-#pragma unroll
-        for (int m = 0; m < R; ++m) {
-            const int j = sub + P * m;
-            if (j < N) Lm[row * N + j] = r[m];
-        }
-    wave_lds_sync();
-    // row-per-lane triangular solves (lane = position i < N)
-    double Lr[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) Lr[j] = in ? Lm[lane * N + j] : 0.0;   // row i of L (j < i)
-    const int pi = in ? pick[lane] : 0;
-    double y = in ? b[pi] : 0.0;
-#pragma unroll
-    for (int k = 0; k + 1 < N; ++k) {
-        const double yk = lane_f64(y, k);
-        y = __builtin_fma(-(lane > k ? Lr[k] : 0.0), yk, y);
-    }
-    y = fabs(dmine) > 2.2250738585072014e-308 ? y / dmine : 0.0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) Lr[j] = in ? Lm[j * N + lane] : 0.0;   // column i of L: L_j,i (j > i)
-#pragma unroll
-    for (int j = N - 1; j >= 1; --j) {
-        const double xj = lane_f64(y, j);
-        y = __builtin_fma(-(lane < j ? Lr[j] : 0.0), xj, y);
-    }
-    if (in) x[pi] = y;
-    wave_lds_sync();
+    omv::wave_lds_sync();
     return true;
 }
 
@@ -1302,7 +1037,7 @@ __device__ __forceinline__ void imu_error_jac_uniform(const State &s, const Imu 
     }
     if (lane == 0)
         for (int q = 0; q < 9; ++q) e9o[q] = e[q];
-    wave_lds_sync();
+    omv::wave_lds_sync();
 }
 
 // Fixed-order sum of the edge waves' partials (wave 0 first).
@@ -1604,7 +1339,7 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
             LAT_T(ti0);
 #endif
             for (int q = lane; q < 216; q += 64) J[q] = 0.0;
-            wave_lds_sync();
+            omv::wave_lds_sync();
 #ifdef OMV_POSE_PROFILE
             LAT_T(ti1);
             if (lane == 0) prof_iw[0] += ti1 - ti0;
@@ -1615,7 +1350,7 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
             if (lane == 0) prof_iw[1] += ti2 - ti1;
 #endif
         }
-        wave_lds_sync();
+        omv::wave_lds_sync();
         }
         if (!(part & 2)) return;
 #ifdef OMV_POSE_PROFILE
@@ -1639,7 +1374,7 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
         if (kLF && lane == 0) prof_iw[2] += ti4 - ti3;
 #endif
         if (!sys) return;
-        wave_lds_sync();
+        omv::wave_lds_sync();
         // bI = J^T om9 here; the quadratic form J^T Info J is summed entry by entry where the system is assembled
         // (all waves), off this wave's path
         if (lane < NI) {
@@ -1653,7 +1388,7 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
     auto prior_wave = [&](bool sys) __attribute__((always_inline)) {
         if constexpr (kLF) {
             if (lane == 0) prior_error_jac(sPr, sRwb, stwb, svel, sbg, sba, eP, JPr);
-            wave_lds_sync();
+            omv::wave_lds_sync();
             for (int q = lane; q < 240; q += 64) {
                 if (q < 225) {
                     const int k = q / 15, j = q % 15;
@@ -1668,7 +1403,7 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
                 }
             }
             if (!sys) return;
-            wave_lds_sync();
+            omv::wave_lds_sync();
             double chi2p = 0, r0, w1p;
             for (int k = 0; k < 15; ++k) chi2p += eP[k] * OeP[k];
             huber(chi2p, 5.0, 25.0, r0, w1p);
@@ -1823,7 +1558,7 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
                         }
                     }
                     if (lane == 0) s_ok = ok ? 1 : 0;
-                    wave_lds_sync();
+                    omv::wave_lds_sync();
                     // VertexPose::oplusImpl -> ImuCamPose::Update (G2oTypes.cc:211-235): lane 0 the frame, lane 1 the
                     // previous frame (LastFrame); then lane c the frame's camera c
                     if (lane == 0 || (kLF && lane == 1)) {
@@ -1840,7 +1575,7 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
                         for (int q = 0; q < 3; ++q)
                             svel[3 * v + q] += xv[6 + q], sbg[3 * v + q] += xv[9 + q], sba[3 * v + q] += xv[12 + q];
                     }
-                    wave_lds_sync();
+                    omv::wave_lds_sync();
                     if (lane < C) {
                         const int c = lane;
                         double Rbw[9], tbw[3], Rc[9], tc[3];
@@ -2581,7 +2316,7 @@ __global__ void __launch_bounds__(kPoThreads) pose_only_kernel(PoseOnlyRig Parg,
                 do {
                     if (tid < 64) {
                         if (lane < 36) Ad[lane] = Hs[lane] + ((lane % 7 == 0) ? lambda_s : 0.0);
-                        wave_lds_sync();
+                        omv::wave_lds_sync();
                         const bool ok = ldlt_pick_solve<6>(Ad, gs, xs, pick, Lm, lane);
                         if (lane == 0) {
                             ok_s = ok ? 1 : 0;

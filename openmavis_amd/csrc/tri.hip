@@ -35,18 +35,11 @@
 #include <cstring>
 
 #include "../../include/omv.h"
+#include "omv_camera.h"
 #include "omv_device.h"
+#include "omv_host.h"
 
 namespace {
-
-#define HIP_OK(x)                                                                    \
-    do {                                                                             \
-        hipError_t e_ = (x);                                                         \
-        if (e_ != hipSuccess) {                                                      \
-            fprintf(stderr, "omv: %s failed: %s\n", #x, hipGetErrorString(e_));      \
-            return OMV_ERR_HIP;                                                      \
-        }                                                                            \
-    } while (0)
 
 constexpr int kTriLow = 50;          // ORBmatcher::TH_LOW
 constexpr int kHisto = 30;           // HISTO_LENGTH
@@ -57,59 +50,6 @@ constexpr int kSeg = kTriThreads;    // keyframe-1 nodes intersected per segment
 constexpr int kPerThread = 4;        // consecutive candidates per thread per tile
 constexpr int kTile = kTriThreads * kPerThread;
 constexpr int kVal = 4096;           // compacted candidates per replay batch
-
-// KannalaBrandt8::project(const Eigen::Vector3f&): cos / sin of the promoted float (C double functions)
-__device__ void kb8_project_f(const float *k, const float *X, float &u, float &v) {
-    const float x2y2 = X[0] * X[0] + X[1] * X[1];
-    const float theta = omv::glibc_atan2f(omv::sqrtf_cr(x2y2), X[2]);
-    const float psi = omv::glibc_atan2f(X[1], X[0]);
-    const float t2 = theta * theta, t3 = theta * t2, t5 = t3 * t2, t7 = t5 * t2, t9 = t7 * t2;
-    const float r = theta + k[4] * t3 + k[5] * t5 + k[6] * t7 + k[7] * t9;
-    u = (float)((double)(k[0] * r) * cos((double)psi) + (double)k[2]);
-    v = (float)((double)(k[1] * r) * sin((double)psi) + (double)k[3]);
-}
-
-// KannalaBrandt8::unproject (precision 1e-6, <= 10 Newton steps, scale = std::tan(theta) / theta_d)
-__device__ void kb8_unproject_f(const float *k, float px, float py, float *ray) {
-    const float pwx = (px - k[2]) / k[0], pwy = (py - k[3]) / k[1];
-    float scale = 1.f;
-    float theta_d = omv::sqrtf_cr(pwx * pwx + pwy * pwy);
-    theta_d = fminf(fmaxf((float)(-3.14159265358979323846 / 2.f), theta_d), (float)(3.14159265358979323846 / 2.f));
-    if ((double)theta_d > 1e-8) {
-        float theta = theta_d;
-        for (int j = 0; j < 10; j++) {
-            const float theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2,
-                        theta8 = theta4 * theta4;
-            const float k0_theta2 = k[4] * theta2, k1_theta4 = k[5] * theta4;
-            const float k2_theta6 = k[6] * theta6, k3_theta8 = k[7] * theta8;
-            const float theta_fix = (theta * (1 + k0_theta2 + k1_theta4 + k2_theta6 + k3_theta8) - theta_d) /
-                                    (1 + 3 * k0_theta2 + 5 * k1_theta4 + 7 * k2_theta6 + 9 * k3_theta8);
-            theta = theta - theta_fix;
-            if (fabsf(theta_fix) < 1e-6f) break;
-        }
-        scale = omv::glibc_tanf(theta) / theta_d;
-    }
-    ray[0] = pwx * scale, ray[1] = pwy * scale, ray[2] = 1.f;
-}
-
-// Pinhole::unprojectEig / project(const Eigen::Vector3f&) (Pinhole.cpp:26-32, :40-45): float, left to right
-__device__ __forceinline__ void pinhole_unproject_f(const float *k, float px, float py, float *ray) {
-    ray[0] = (px - k[2]) / k[0], ray[1] = (py - k[3]) / k[1], ray[2] = 1.f;
-}
-__device__ __forceinline__ void pinhole_project_f(const float *k, const float *X, float &u, float &v) {
-    u = k[0] * X[0] / X[2] + k[2];
-    v = k[1] * X[1] / X[2] + k[3];
-}
-// GeometricCamera::unprojectEig / project, dispatched on the camera type (the virtual calls of
-// KannalaBrandt8::TriangulateMatches on pCamera2, KannalaBrandt8.cpp:330, :382)
-__device__ __forceinline__ void cam_unproject_f(int model, const float *k, float px, float py, float *ray) {
-    if (model == OMV_CAM_PINHOLE) pinhole_unproject_f(k, px, py, ray);
-    else kb8_unproject_f(k, px, py, ray);
-}
-__device__ __forceinline__ void cam_project_f(int model, const float *k, const float *X, float &u, float &v) {
-    if (model == OMV_CAM_PINHOLE) pinhole_project_f(k, X, u, v);
-    else kb8_project_f(k, X, u, v);
-}
 
 // Eigen Matrix3f::inverse() (Eigen/src/LU/InverseImpl.h, compute_inverse<..., 3>): the cofactors of column 0,
 // det = their dot product with column 0, result(i, j) = cofactor(j, i) * (1 / det).  Row-major m / r.
@@ -245,8 +185,8 @@ __device__ float triangulate_matches(const float *cam1, const float *cam2, const
                                      const float *R12, const float *t12, float sigmaLevel, float unc,
                                      float *p3D = nullptr, int model2 = OMV_CAM_KB8) {
     float r1[3], r2[3], r21[3];
-    kb8_unproject_f(cam1, kp1.x, kp1.y, r1);
-    cam_unproject_f(model2, cam2, kp2.x, kp2.y, r2);
+    omv::kb8_unproject_f(cam1, kp1.x, kp1.y, r1);
+    omv::cam_unproject_f(model2, cam2, kp2.x, kp2.y, r2);
     for (int i = 0; i < 3; ++i) r21[i] = R12[3 * i] * r2[0] + R12[3 * i + 1] * r2[1] + R12[3 * i + 2] * r2[2];
     const float dot = r1[0] * r21[0] + r1[1] * r21[1] + r1[2] * r21[2];
     const float n1 = omv::sqrtf_cr(r1[0] * r1[0] + r1[1] * r1[1] + r1[2] * r1[2]);
@@ -275,13 +215,13 @@ __device__ float triangulate_matches(const float *cam1, const float *cam2, const
     const float z2 = R21[6] * x3D[0] + R21[7] * x3D[1] + R21[8] * x3D[2] + t2[2];
     if (z2 <= 0) return -3;
     float u1, v1;
-    kb8_project_f(cam1, x3D, u1, v1);
+    omv::kb8_project_f(cam1, x3D, u1, v1);
     const float ex1 = u1 - kp1.x, ey1 = v1 - kp1.y;
     if ((double)(ex1 * ex1 + ey1 * ey1) > 5.991 * (double)sigmaLevel) return -4;
     float x3D2[3];
     for (int i = 0; i < 3; ++i) x3D2[i] = R21[3 * i] * x3D[0] + R21[3 * i + 1] * x3D[1] + R21[3 * i + 2] * x3D[2] + t2[i];
     float u2, v2;
-    cam_project_f(model2, cam2, x3D2, u2, v2);
+    omv::cam_project_f(model2, cam2, x3D2, u2, v2);
     const float ex2 = u2 - kp2.x, ey2 = v2 - kp2.y;
     if ((double)(ex2 * ex2 + ey2 * ey2) > 5.991 * (double)unc) return -5;
     if (p3D) p3D[0] = x3D[0], p3D[1] = x3D[1], p3D[2] = x3D[2];
@@ -1120,16 +1060,16 @@ __global__ void stereo_tri_kernel(StereoTriArgs A) {
 
 // Parity hook: the camera-model pieces for one input (out: ray1[3] ray2[3] V[16] z p3D[3]).
 __global__ void tri_debug_kernel(TriCams C, omv_kp kp1, omv_kp kp2, const float *Rt, float sigma, float unc, float *out) {
-    kb8_unproject_f(C.cam[0], kp1.x, kp1.y, out);
-    kb8_unproject_f(C.cam[1], kp2.x, kp2.y, out + 3);
+    omv::kb8_unproject_f(C.cam[0], kp1.x, kp1.y, out);
+    omv::kb8_unproject_f(C.cam[1], kp2.x, kp2.y, out + 3);
     float A[16];
     for (int i = 0; i < 16; ++i) A[i] = Rt[12 + i];
     jacobi_svd4_v(A, out + 6);
     out[22] = triangulate_matches(C.cam[0], C.cam[1], kp1, kp2, Rt, Rt + 9, sigma, unc, out + 23);
     // intermediates of the triangulation of (kp1, kp2): x3D[3] and its projection uv1[2] -> out[26..30]
     float r1[3], r2[3], R21[9], t2[3], V[16];
-    kb8_unproject_f(C.cam[0], kp1.x, kp1.y, r1);
-    kb8_unproject_f(C.cam[1], kp2.x, kp2.y, r2);
+    omv::kb8_unproject_f(C.cam[0], kp1.x, kp1.y, r1);
+    omv::kb8_unproject_f(C.cam[1], kp2.x, kp2.y, r2);
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) R21[3 * i + j] = Rt[3 * j + i];
     for (int i = 0; i < 3; ++i) t2[i] = -R21[3 * i] * Rt[9] + -R21[3 * i + 1] * Rt[10] + -R21[3 * i + 2] * Rt[11];
@@ -1145,7 +1085,7 @@ __global__ void tri_debug_kernel(TriCams C, omv_kp kp1, omv_kp kp2, const float 
     float x3D[3];
     for (int i = 0; i < 3; ++i) x3D[i] = V[4 * i + 3] / V[15];
     float u1, v1;
-    kb8_project_f(C.cam[0], x3D, u1, v1);
+    omv::kb8_project_f(C.cam[0], x3D, u1, v1);
     out[26] = x3D[0], out[27] = x3D[1], out[28] = x3D[2], out[29] = u1, out[30] = v1;
 }
 
@@ -1237,8 +1177,8 @@ __device__ int cnmp_match(const CnmpArgs &a, const omv_cnmp_kf &K1, const omv_cn
     const float Rwc1[9] = {T1[0], T1[4], T1[8], T1[1], T1[5], T1[9], T1[2], T1[6], T1[10]};
     const float Rwc2[9] = {T2[0], T2[4], T2[8], T2[1], T2[5], T2[9], T2[2], T2[6], T2[10]};
     float xn1[3], xn2[3], ray1[3], ray2[3];
-    cam_unproject_f(a.C.model[c1], a.C.cam[c1], kp1.x, kp1.y, xn1);
-    cam_unproject_f(a.C.model[c2], a.C.cam[c2], kp2.x, kp2.y, xn2);
+    omv::cam_unproject_f(a.C.model[c1], a.C.cam[c1], kp1.x, kp1.y, xn1);
+    omv::cam_unproject_f(a.C.model[c2], a.C.cam[c2], kp2.x, kp2.y, xn2);
     for (int r = 0; r < 3; ++r) ray1[r] = Rwc1[3 * r] * xn1[0] + Rwc1[3 * r + 1] * xn1[1] + Rwc1[3 * r + 2] * xn1[2];
     for (int r = 0; r < 3; ++r) ray2[r] = Rwc2[3 * r] * xn2[0] + Rwc2[3 * r + 1] * xn2[1] + Rwc2[3 * r + 2] * xn2[2];
     const float cosParallaxRays = cnmp_dot3(ray1, ray2) / (cnmp_norm3(ray1) * cnmp_norm3(ray2));
@@ -1285,7 +1225,7 @@ __device__ int cnmp_match(const CnmpArgs &a, const omv_cnmp_kf &K1, const omv_cn
     if (!bStereo1) {
         const float X[3] = {x1, y1, z1};
         float u, v;
-        cam_project_f(a.C.model[c1], a.C.cam[c1], X, u, v);
+        omv::cam_project_f(a.C.model[c1], a.C.cam[c1], X, u, v);
         const float errX1 = u - kp1.x, errY1 = v - kp1.y;
         if ((double)(errX1 * errX1 + errY1 * errY1) > 5.991 * (double)sigmaSquare1) return 0;
     } else {
@@ -1300,7 +1240,7 @@ __device__ int cnmp_match(const CnmpArgs &a, const omv_cnmp_kf &K1, const omv_cn
     if (!bStereo2) {
         const float X[3] = {x2, y2, z2};
         float u, v;
-        cam_project_f(a.C.model[c2], a.C.cam[c2], X, u, v);
+        omv::cam_project_f(a.C.model[c2], a.C.cam[c2], X, u, v);
         const float errX2 = u - kp2.x, errY2 = v - kp2.y;
         if ((double)(errX2 * errX2 + errY2 * errY2) > 5.991 * (double)sigmaSquare2) return 0;
     } else {

@@ -3,6 +3,7 @@
 // kernel's LastKeyFrame / LastFrame systems).  Same solution up to rounding; cycles per solve with clock64.
 //   hipcc --offload-arch=gfx950 -O3 -I include tools/micro/ldlt24_bench.hip -o tools/micro/ldlt24_bench
 #include "../../openmavis_amd/csrc/pose.hip"
+#include "ldlt_pick.h"
 
 namespace {
 
@@ -12,8 +13,8 @@ template <int N>
 __device__ __forceinline__ bool ldlt_lds_solve(const double *H, const double *b, double *x, int *pick, double *Lm,
                                                double *prow, int lane) {
     const bool in = lane < N;
-    if (!ldlt_pick_order<N>(H, pick, lane)) return false;
-    wave_lds_sync();
+    if (!micro_pick_order<N>(H, pick, lane)) return false;
+    omv::wave_lds_sync();
     const int pi = in ? pick[lane] : 0;
     int pj[N];
 #pragma unroll
@@ -23,7 +24,7 @@ __device__ __forceinline__ bool ldlt_lds_solve(const double *H, const double *b,
     for (int j = 0; j < N; ++j) r[j] = in ? H[pj[j] * N + pi] : 0.0;
     if (!(lane_f64(r[0], 0) != 0.0)) {
         if (in) x[lane] = 0.0;
-        wave_lds_sync();
+        omv::wave_lds_sync();
         return true;
     }
     int sign = 0;
@@ -35,11 +36,11 @@ __device__ __forceinline__ bool ldlt_lds_solve(const double *H, const double *b,
 #pragma unroll
             for (int j = k; j < N; ++j) pr[j] = r[j];
         }
-        wave_lds_sync();
+        omv::wave_lds_sync();
         const double d = pr[k];
         dmine = lane == k ? d : dmine;
         const bool nz = fabs(d) > 0.0;
-        const double inv = nz ? rcp_nr(d) : 0.0;
+        const double inv = nz ? omv::rcp_nr(d) : 0.0;
         const bool below = lane > k;
         const double l = below ? r[k] * inv : 0.0;
 #pragma unroll
@@ -58,7 +59,7 @@ __device__ __forceinline__ bool ldlt_lds_solve(const double *H, const double *b,
     if (in)
 #pragma unroll
         for (int j = 0; j < N; ++j) Lm[lane * N + j] = r[j];
-    wave_lds_sync();
+    omv::wave_lds_sync();
 #pragma unroll
     for (int j = 0; j < N; ++j) r[j] = in ? Lm[j * N + lane] : 0.0;
 #pragma unroll
@@ -67,7 +68,7 @@ __device__ __forceinline__ bool ldlt_lds_solve(const double *H, const double *b,
         if (lane < j) y = __builtin_fma(-r[j], xj, y);
     }
     if (in) x[pi] = y;
-    wave_lds_sync();
+    omv::wave_lds_sync();
     return true;
 }
 
@@ -78,13 +79,13 @@ __global__ void __launch_bounds__(64) bench(const double *Hs, const double *bs, 
     const int lane = threadIdx.x;
     for (int q = lane; q < N * N; q += 64) H[q] = Hs[(size_t)blockIdx.x * N * N + q];
     if (lane < N) b[lane] = bs[(size_t)blockIdx.x * N + lane];
-    wave_lds_sync();
+    omv::wave_lds_sync();
     long long t0 = clock64();
     for (int r = 0; r < reps; ++r) {
         if (V == 0) ldlt_pick_solve<N>(H, b, x, pick, Lm, lane);
         else ldlt_lds_solve<N>(H, b, x, pick, Lm, prow, lane);
         if (lane < N) b[lane] += 1e-300 * x[lane];   // a dependence between repetitions
-        wave_lds_sync();
+        omv::wave_lds_sync();
     }
     long long t1 = clock64();
     if (lane < N) xs[(size_t)blockIdx.x * N + lane] = x[lane];

@@ -2,6 +2,7 @@
 // backward), one wavefront, clock64 stamps between the phases (the phases copied from pose.hip's ldlt_pick_solve).
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I include tools/micro/ldlt24_phase.hip -o /tmp/ldlt24_phase
 #include "../../openmavis_amd/csrc/pose.hip"
+#include "ldlt_pick.h"
 
 namespace {
 template <int N>
@@ -9,8 +10,8 @@ __device__ __forceinline__ void phased(const double *H, const double *b, double 
                                        long long *t) {
     const bool in = lane < N;
     t[0] = clock64();
-    ldlt_pick_order<N>(H, pick, lane);
-    wave_lds_sync();
+    micro_pick_order<N>(H, pick, lane);
+    omv::wave_lds_sync();
     t[1] = clock64();
     const int pi = in ? pick[lane] : 0;
     int pj[N];
@@ -28,7 +29,7 @@ __device__ __forceinline__ void phased(const double *H, const double *b, double 
         const double d = lane_f64(r[k], k);
         dmine = lane == k ? d : dmine;
         const bool nz = fabs(d) > 0.0;
-        const double inv = nz ? rcp_nr(d) : 0.0;
+        const double inv = nz ? omv::rcp_nr(d) : 0.0;
         const bool below = lane > k;
         const double l = below ? r[k] * inv : 0.0;
 #pragma unroll
@@ -49,7 +50,7 @@ __device__ __forceinline__ void phased(const double *H, const double *b, double 
     if (in)
 #pragma unroll
         for (int j = 0; j < N; ++j) Lm[lane * N + j] = r[j];
-    wave_lds_sync();
+    omv::wave_lds_sync();
 #pragma unroll
     for (int j = 0; j < N; ++j) r[j] = in ? Lm[j * N + lane] : 0.0;
     t[5] = clock64();
@@ -59,7 +60,7 @@ __device__ __forceinline__ void phased(const double *H, const double *b, double 
         if (lane < j) y = __builtin_fma(-r[j], xj, y);
     }
     if (in) x[pi] = y;
-    wave_lds_sync();
+    omv::wave_lds_sync();
     t[6] = clock64();
 }
 
@@ -70,14 +71,14 @@ __global__ void __launch_bounds__(64) bench(const double *Hs, const double *bs, 
     const int lane = threadIdx.x;
     for (int q = lane; q < N * N; q += 64) H[q] = Hs[(size_t)blockIdx.x * N * N + q];
     if (lane < N) b[lane] = bs[(size_t)blockIdx.x * N + lane];
-    wave_lds_sync();
+    omv::wave_lds_sync();
     long long acc[6] = {0, 0, 0, 0, 0, 0};
     for (int r = 0; r < reps; ++r) {
         long long t[7];
         phased<N>(H, b, x, pick, Lm, lane, t);
         for (int q = 0; q < 6; ++q) acc[q] += t[q + 1] - t[q];
         if (lane < N) b[lane] += 1e-300 * x[lane];
-        wave_lds_sync();
+        omv::wave_lds_sync();
     }
     if (lane < N) xs[(size_t)blockIdx.x * N + lane] = x[lane];
     if (lane == 0)

@@ -5,6 +5,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I include tools/micro/ldlt24_v2.hip -o /tmp/ldlt24_v2
 #include <cstring>
 #include "../../openmavis_amd/csrc/pose.hip"
+#include "ldlt_pick.h"
 
 namespace {
 template <int N>
@@ -12,8 +13,8 @@ __device__ __forceinline__ bool ldlt_v2(const double *H, const double *b, double
     constexpr int S = (N + 2) & ~1;   // stride of the transposed factor (even: 16-byte rows)
     double *Lt = Lm, *rowbuf = Lm + S * N;   // Lt[k * S + i] = L_ik (i > k); rowbuf: two pivot-row buffers of S
     const bool in = lane < N;
-    if (!ldlt_pick_order<N>(H, pick, lane)) return false;
-    wave_lds_sync();
+    if (!micro_pick_order<N>(H, pick, lane)) return false;
+    omv::wave_lds_sync();
     const int pi = in ? pick[lane] : 0;
     int pj[N];
 #pragma unroll
@@ -23,7 +24,7 @@ __device__ __forceinline__ bool ldlt_v2(const double *H, const double *b, double
     for (int j = 0; j < N; ++j) r[j] = in ? H[pj[j] * N + pi] : 0.0;
     if (!(lane_f64(r[0], 0) != 0.0)) {
         if (in) x[lane] = 0.0;
-        wave_lds_sync();
+        omv::wave_lds_sync();
         return true;
     }
     int sign = 0;
@@ -33,7 +34,7 @@ __device__ __forceinline__ bool ldlt_v2(const double *H, const double *b, double
         const double d = lane_f64(r[k], k);
         dmine = lane == k ? d : dmine;
         const bool nz = fabs(d) > 0.0;
-        const double inv = nz ? rcp_nr(d) : 0.0;
+        const double inv = nz ? omv::rcp_nr(d) : 0.0;
         const bool below = lane > k;
         const double l = below ? r[k] * inv : 0.0;
 #pragma unroll
@@ -50,7 +51,7 @@ __device__ __forceinline__ bool ldlt_v2(const double *H, const double *b, double
         if (lane > k) y = __builtin_fma(-r[k], yk, y);
     }
     y = fabs(dmine) > 2.2250738585072014e-308 ? y / dmine : 0.0;
-    wave_lds_sync();
+    omv::wave_lds_sync();
 #pragma unroll
     for (int j = 0; j < N; ++j) r[j] = (in && j > lane) ? Lt[lane * S + j] : 0.0;   // r[j] = L_j,lane
 #pragma unroll
@@ -59,7 +60,7 @@ __device__ __forceinline__ bool ldlt_v2(const double *H, const double *b, double
         if (lane < j) y = __builtin_fma(-r[j], xj, y);
     }
     if (in) x[pi] = y;
-    wave_lds_sync();
+    omv::wave_lds_sync();
     return true;
 }
 
@@ -70,13 +71,13 @@ __global__ void __launch_bounds__(64) bench(const double *Hs, const double *bs, 
     const int lane = threadIdx.x;
     for (int q = lane; q < N * N; q += 64) H[q] = Hs[(size_t)blockIdx.x * N * N + q];
     if (lane < N) b[lane] = bs[(size_t)blockIdx.x * N + lane];
-    wave_lds_sync();
+    omv::wave_lds_sync();
     long long t0 = clock64();
     for (int r = 0; r < reps; ++r) {
         if (V == 0) ldlt_pick_solve<N>(H, b, x, pick, Lm, lane);
         else ldlt_v2<N>(H, b, x, pick, Lm, lane);
         if (lane < N) b[lane] += 1e-300 * x[lane];
-        wave_lds_sync();
+        omv::wave_lds_sync();
     }
     long long t1 = clock64();
     if (lane < N) xs[(size_t)blockIdx.x * N + lane] = x[lane];

@@ -42,7 +42,7 @@ __device__ __forceinline__ bool ldlt_stage(const double *H, const double *b, dou
             if (lane == 0) pick[k] = e;
         }
     }
-    wave_lds_sync();
+    omv::wave_lds_sync();
     if (stage == 1) return true;
     const int pi = in ? pick[lane] : 0;
     double r[N];
@@ -50,7 +50,7 @@ __device__ __forceinline__ bool ldlt_stage(const double *H, const double *b, dou
     for (int j = 0; j < N; ++j) r[j] = in ? H[pi * N + pick[j]] : 0.0;
     if (!(lane_f64(r[0], 0) != 0.0)) {   // largest |diagonal| zero: Eigen stops with ZeroSign; the solve gives x = 0
         if (in) x[lane] = 0.0;
-        wave_lds_sync();
+        omv::wave_lds_sync();
         return true;
     }
     if (stage == 2) { if (in) x[lane] = r[N - 1]; return true; }
@@ -89,7 +89,7 @@ __device__ __forceinline__ bool ldlt_stage(const double *H, const double *b, dou
     if (in)
 #pragma unroll
         for (int j = 0; j < N; ++j) Lm[lane * N + j] = r[j];
-    wave_lds_sync();
+    omv::wave_lds_sync();
 #pragma unroll
     for (int j = 0; j < N; ++j) r[j] = in ? Lm[j * N + lane] : 0.0;   // r[j] = L_j,lane
 #pragma unroll
@@ -98,7 +98,7 @@ __device__ __forceinline__ bool ldlt_stage(const double *H, const double *b, dou
         if (lane < j) y = __builtin_fma(-r[j], xj, y);
     }
     if (in) x[pi] = y;
-    wave_lds_sync();
+    omv::wave_lds_sync();
     return true;
 }
 
@@ -106,7 +106,7 @@ __device__ __forceinline__ bool ldlt_stage(const double *H, const double *b, dou
 template <int N>
 __global__ void __launch_bounds__(64) ldlt_bench(const double *Hin, const double *bin, double *xout, int reps,
                                                  unsigned long long *ticks, int stage) {
-    __shared__ double H[N * N], b[N], x[N], Lm[N * N], cb[32];
+    __shared__ double H[N * N], b[N], x[N], Lm[N * N];
     __shared__ int pick[N];
     const int lane = threadIdx.x;
     for (int q = lane; q < N * N; q += 64) H[q] = Hin[q];
@@ -115,32 +115,12 @@ __global__ void __launch_bounds__(64) ldlt_bench(const double *Hin, const double
     const unsigned long long t0 = wall_clock64();
     bool ok = true;
     for (int r = 0; r < reps; ++r) {
-        ok &= stage == 9 ? ldlt_pick_solve_wide<N>(H, b, x, pick, Lm, cb, lane) : stage ? ldlt_stage<N>(H, b, x, pick, Lm, lane, stage) : ldlt_pick_solve<N>(H, b, x, pick, Lm, lane);
+        ok &= stage ? ldlt_stage<N>(H, b, x, pick, Lm, lane, stage) : ldlt_pick_solve<N>(H, b, x, pick, Lm, lane);
         asm volatile("" ::: "memory");
     }
     const unsigned long long t1 = wall_clock64();
     if (lane < N) xout[lane] = ok ? x[lane] : -1.0;
     if (lane == 0) ticks[0] = t1 - t0;
-}
-
-template <int N>
-__global__ void __launch_bounds__(256) ldlt_elem_bench(const double *Hin, const double *bin, double *xout, int reps,
-                                                      unsigned long long *ticks) {
-    __shared__ double H[N * N], b[N], x[N], Lm[N * N], col[2 * N];
-    __shared__ int pick[N], flag;
-    const int tid = threadIdx.x;
-    for (int q = tid; q < N * N; q += 256) H[q] = Hin[q];
-    if (tid < N) b[tid] = bin[tid];
-    __syncthreads();
-    const unsigned long long t0 = wall_clock64();
-    bool ok = true;
-    for (int r = 0; r < reps; ++r) {
-        ok &= ldlt_elem_solve<N, 256>(H, b, x, pick, Lm, col, &flag, tid);
-        asm volatile("" ::: "memory");
-    }
-    const unsigned long long t1 = wall_clock64();
-    if (tid < N) xout[tid] = ok ? x[tid] : -1.0;
-    if (tid == 0) ticks[0] = t1 - t0;
 }
 
 __global__ void __launch_bounds__(256) edge_bench(Rig rig_in, const float *xw, const double *obs, int reps,
@@ -216,38 +196,6 @@ int main() {
         ldlt_bench<30><<<1, 64>>>(dH, db, dx, reps, dt, 0);
         (void)hipMemcpy(&t, dt, 8, hipMemcpyDeviceToHost);
         if (pass) printf("ldlt_pick_solve<30>: %.3f us per solve\n", t / 100.0 / reps);
-        std::vector<double> xa(30), xb(30);
-        (void)hipMemcpy(xa.data(), dx, 30 * 8, hipMemcpyDeviceToHost);
-        ldlt_bench<30><<<1, 64>>>(dH, db, dx, reps, dt, 9);
-        (void)hipMemcpy(&t, dt, 8, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(xb.data(), dx, 30 * 8, hipMemcpyDeviceToHost);
-        double md = 0, mx = 0;
-        for (int i = 0; i < 30; ++i) md = std::max(md, std::fabs(xa[i] - xb[i])), mx = std::max(mx, std::fabs(xa[i]));
-        if (pass) printf("ldlt_pick_solve_wide<30>: %.3f us per solve (max |dx| %.3g of %.3g)\n", t / 100.0 / reps, md, mx);
-        (void)hipMemcpy(dH, H15.data(), 225 * 8, hipMemcpyHostToDevice);
-        (void)hipMemcpy(db, b15.data(), 15 * 8, hipMemcpyHostToDevice);
-        ldlt_bench<15><<<1, 64>>>(dH, db, dx, reps, dt, 0);
-        (void)hipMemcpy(xa.data(), dx, 15 * 8, hipMemcpyDeviceToHost);
-        ldlt_bench<15><<<1, 64>>>(dH, db, dx, reps, dt, 9);
-        (void)hipMemcpy(&t, dt, 8, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(xb.data(), dx, 15 * 8, hipMemcpyDeviceToHost);
-        md = 0, mx = 0;
-        for (int i = 0; i < 15; ++i) md = std::max(md, std::fabs(xa[i] - xb[i])), mx = std::max(mx, std::fabs(xa[i]));
-        if (pass) printf("ldlt_pick_solve_wide<15>: %.3f us per solve (max |dx| %.3g of %.3g)\n", t / 100.0 / reps, md, mx);
-        for (int n : {15, 30}) {
-            (void)hipMemcpy(dH, n == 15 ? H15.data() : H30.data(), n * n * 8, hipMemcpyHostToDevice);
-            (void)hipMemcpy(db, n == 15 ? b15.data() : b30.data(), n * 8, hipMemcpyHostToDevice);
-            if (n == 15) ldlt_bench<15><<<1, 64>>>(dH, db, dx, reps, dt, 0);
-            else ldlt_bench<30><<<1, 64>>>(dH, db, dx, reps, dt, 0);
-            (void)hipMemcpy(xa.data(), dx, n * 8, hipMemcpyDeviceToHost);
-            if (n == 15) ldlt_elem_bench<15><<<1, 256>>>(dH, db, dx, reps, dt);
-            else ldlt_elem_bench<30><<<1, 256>>>(dH, db, dx, reps, dt);
-            (void)hipMemcpy(&t, dt, 8, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(xb.data(), dx, n * 8, hipMemcpyDeviceToHost);
-            md = 0, mx = 0;
-            for (int i = 0; i < n; ++i) md = std::max(md, std::fabs(xa[i] - xb[i])), mx = std::max(mx, std::fabs(xa[i]));
-            if (pass) printf("ldlt_elem_solve<%d, 256>: %.3f us per solve (max |dx| %.3g of %.3g)\n", n, t / 100.0 / reps, md, mx);
-        }
         (void)hipMemcpy(dH, H15.data(), 225 * 8, hipMemcpyHostToDevice);
         (void)hipMemcpy(db, b15.data(), 15 * 8, hipMemcpyHostToDevice);
         // ties on the diagonal: the replayed pick order
