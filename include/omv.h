@@ -987,6 +987,38 @@ omv_status omv_local_mapping_create_new_map_points(omv_matcher *m, const omv_cnm
                                                    float scale_factor, int32_t *n_matches, int32_t *side1_state,
                                                    void *stream);
 
+/* ---- Test hooks (no reference counterpart): the device linear-algebra routines on plain device arrays ----
+ * Each launches the product's own instantiation of the routine, one workgroup per problem (`batch` problems, on
+ * `stream`, not synchronised).  Every pointer is device memory. */
+
+/* The pivoted LDL^T solves of the pose kernels.  routine 0: ldlt_pick_solve<n>, n in {6, 9, 24}; `order` receives the
+ * pick order (position -> row).  routine 1: ldlt_pivot_solve_wave<n>, n in {15, 30}; `order` receives the
+ * transpositions.  H [batch][n * n] row-major, b [batch][n]; x [batch][n] and order [batch][n] are in / out: the caller
+ * pre-fills them, what the routine does not write comes back unchanged; ok [batch]: the routine's result (isPositive). */
+omv_status omv_selftest_ldlt(int routine, int n, int batch, const double *H, const double *b, double *x, int32_t *order,
+                             int32_t *ok, void *stream);
+/* pinv15_wave: A [batch][225] -> P [batch][225]; path [batch]: 1 when the routine's entry predicate (both LDL^T
+ * factorisations with positive pivots, evaluated by the hook on the same input) selects the inverse, 0 the Jacobi
+ * eigen-decomposition. */
+omv_status omv_selftest_pinv15(int batch, const double *A, double *P, int32_t *path, void *stream);
+/* inertial_info9_wave<par != 0>: the float covariance C [batch][15 * 15] -> info [batch][81]; path [batch]: 0 the
+ * factorisation shortcut (par only: the result is the symmetrised inverse itself, no rotation applied), 1 the
+ * eigen-decomposition with every eigenvalue kept, 2 with at least one eigenvalue below 1e-12 zeroed. */
+omv_status omv_selftest_inertial_info9(int par, int batch, const float *C, double *info, int32_t *path, void *stream);
+/* inv16 of the reduced system's solver (the LDS instantiation): D [batch][256], 16 x 16 blocks in the solver's layout
+ * (entry (r, c) at 16 r + (c ^ r)), only the lower triangle read -> Dinv [batch][256], the full inverse in the same
+ * layout; bad [batch]: the routine's flag (a zero or non-finite pivot). */
+omv_status omv_selftest_inv16(int batch, const double *D, double *Dinv, int32_t *bad, void *stream);
+/* One reduced-system solve on a handle after omv_lba_set_problem, at the current state: errors, build, assemble and
+ * the block LDL^T once, through the optimiser's own launches, with the damping `lambda` (> 0: the padding pivots are
+ * lambda) and the robust kernels of the problem (`o` is validated only: no option changes them).  Host outputs, n =
+ * 16 n_opt: S [n * n] the reduced system scattered dense in keyframe order (row 16 k + r; the stored lower blocks
+ * mirrored, padding rows included), rhs [n] = b - the Schur right-hand side, x [n] the solution, fail the solver's
+ * flag, plan [plan_cap >= 4 + n_opt]: storage mode (1 every block in LDS, 2 hybrid LDS / global, 0 global), n_slots,
+ * n_lds, n_lev, then the columns per level.  Synchronous. */
+omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda, double *S, double *rhs, double *x,
+                               int32_t *fail, int32_t *plan, int plan_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -325,6 +325,12 @@ SIGNATURES = {
     "omv_local_mapping_create_new_map_points": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I,
                                                      ctypes.c_float, ctypes.c_float, _VP, _VP, _VP]),
     "omv_mappoint_normal_depth": (_I, [_I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "omv_selftest_ldlt": (_I, [_I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "omv_selftest_pinv15": (_I, [_I, _VP, _VP, _VP, _VP]),
+    "omv_selftest_inertial_info9": (_I, [_I, _I, _VP, _VP, _VP, _VP]),
+    "omv_selftest_inv16": (_I, [_I, _VP, _VP, _VP, _VP]),
+    "omv_lba_debug_solve": (_I, [_VP, ctypes.POINTER(LbaOpts), ctypes.c_double, _VP, _VP, _VP, ctypes.POINTER(_I),
+                                 _VP, _I]),
 }
 
 _lib = None

@@ -887,11 +887,15 @@ __device__ inline void inertial_info9_wave(const float *C15, double *out, double
 
 // Eigen::LDLT<MatrixXd> (lower, diagonal pivoting; ldlt_inplace::unblocked) + LDLT::_solve_impl with the
 // D pseudo-inverse below DBL_MIN, spread over one wavefront (lane = row); per element the same operations
-// in the same order as the oracle's ldlt_pivot_solve.  Returns isPositive().  A (N x N,
+// in the same order as the oracle's ldlt_pivot_solve.  Returns isPositive(), and false with x untouched for a NaN on
+// the diagonal.  A (N x N,
 // row-major), b, x and the scratch t[2N] live in LDS; every lane of the wave must call it.
 template <int N>
 __device__ inline bool ldlt_pivot_solve_wave(double *A, const double *b, double *x, double *t, int *tr, int lane) {
     static_assert(N <= 64, "one row per lane");
+    // a NaN diagonal: no factorisation (as ldlt_pick_solve; the pivot search below compares magnitudes, and a NaN
+    // compares false both ways, so the lanes would leave it with different pivots)
+    if (__ballot(lane < N && !(A[lane * N + lane] == A[lane * N + lane]))) return false;
     int sign = 0;
     for (int k = 0; k < N; ++k) {
         // largest |diagonal| in the trailing corner, first index on ties (Eigen maxCoeff)

@@ -3081,3 +3081,71 @@ omv_status omv_lba_stage_ms(omv_lba *h, double *ms4, int *trials) {
 }
 
 }  // extern "C"
+
+// ---- test hooks: the solver's 16x16 inverse alone, and one reduced-system solve read back ---------------------
+__global__ void __launch_bounds__(64) selftest_inv16_kernel(const double *D, double *Dinv, int32_t *bad) {
+    __shared__ double Ds[256];
+    __shared__ int flag;
+    const int p = blockIdx.x, lane = threadIdx.x;
+    for (int q = lane; q < 256; q += 64) Ds[q] = D[(size_t)p * 256 + q];
+    if (lane == 0) flag = 0;
+    wave_sync<0>();
+    inv16<0>(Ds, lane, &flag);
+    for (int q = lane; q < 256; q += 64) Dinv[(size_t)p * 256 + q] = Ds[q];
+    if (lane == 0) bad[p] = flag;
+}
+
+extern "C" {
+
+omv_status omv_selftest_inv16(int batch, const double *D, double *Dinv, int32_t *bad, void *stream) {
+    if (batch < 0 || (batch > 0 && (!D || !Dinv || !bad))) return OMV_ERR_ARG;
+    if (batch == 0) return OMV_OK;
+    selftest_inv16_kernel<<<batch, 64, 0, (hipStream_t)stream>>>(D, Dinv, bad);
+    HIP_OK(hipGetLastError());
+    return OMV_OK;
+}
+
+omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda, double *S, double *rhs, double *x,
+                               int32_t *fail, int32_t *plan, int plan_cap) {
+    if (!h || !o || !S || !rhs || !x || !fail || !plan || !(lambda > 0.0) || !std::isfinite(lambda)) return OMV_ERR_ARG;
+    const BlockPat &B = h->BP;
+    const int nb = B.nb, n = 16 * nb;
+    if (nb <= 0 || h->world != 1 || !h->d_S || plan_cap < 4 + B.n_lev) return OMV_ERR_ARG;
+    const State &A = h->st[h->cur];
+    omv_status rs;
+    if ((rs = lba_errors(h, A)) != OMV_OK) return rs;
+    if ((rs = launch_build(h, A, A, nullptr, lambda)) != OMV_OK) return rs;
+    if ((rs = launch_assemble(h, lambda, nullptr)) != OMV_OK) return rs;
+    launch_ldlt(h, nullptr);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(h->stream));
+    std::vector<double> blocks((size_t)B.n_slots * 256), bb(n), coef(n);
+    std::vector<int> kr(B.n_slots), kc(B.n_slots), lev(B.n_lev + 1);
+    HIP_OK(hipMemcpy(blocks.data(), h->d_S, blocks.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(bb.data(), h->d_bb, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(coef.data(), h->d_coef, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(x, h->d_x, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(kr.data(), B.slot_kr, kr.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(kc.data(), B.slot_kc, kc.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(lev.data(), B.lev_start, lev.size() * sizeof(int), hipMemcpyDeviceToHost));
+    int f = 0;
+    HIP_OK(hipMemcpy(&f, h->d_fail, sizeof(int), hipMemcpyDeviceToHost));
+    *fail = f;
+    std::fill(S, S + (size_t)n * n, 0.0);
+    for (int t = 0; t < B.n_slots; ++t) {
+        const bool diag = kr[t] == kc[t];
+        for (int r = 0; r < 16; ++r)
+            for (int c = 0; c < 16; ++c) {
+                if (diag && c > r) continue;   // a diagonal block stores its lower triangle
+                const double v = blocks[(size_t)t * 256 + sw16(r, c)];
+                S[(size_t)(16 * kr[t] + r) * n + 16 * kc[t] + c] = v;
+                S[(size_t)(16 * kc[t] + c) * n + 16 * kr[t] + r] = v;
+            }
+    }
+    for (int q = 0; q < n; ++q) rhs[q] = bb[q] - coef[q];
+    plan[0] = h->use_lds, plan[1] = B.n_slots, plan[2] = B.n_lds, plan[3] = B.n_lev;
+    for (int l = 0; l < B.n_lev; ++l) plan[4 + l] = lev[l + 1] - lev[l];
+    return OMV_OK;
+}
+
+}  // extern "C"

@@ -2676,3 +2676,97 @@ omv_status omv_pose_constraint(int n, const double *H_in, double *H_out, void *s
 }
 
 }  // extern "C"
+
+// ---- test hooks (omv_selftest_*): the one-wavefront linear algebra on plain device arrays, one wavefront per problem ----
+namespace {
+
+template <int N, bool kPick>
+__global__ void __launch_bounds__(64) selftest_ldlt_kernel(const double *H, const double *b, double *x, int32_t *order,
+                                                           int32_t *ok) {
+    __shared__ double Hs[N * N], bs[N], xs[N], Ls[kPick ? N * N : 2 * N];
+    __shared__ int ord[N];
+    const int p = blockIdx.x, lane = threadIdx.x;
+    for (int q = lane; q < N * N; q += 64) Hs[q] = H[(size_t)p * N * N + q];
+    if (lane < N) bs[lane] = b[p * N + lane], xs[lane] = x[p * N + lane], ord[lane] = order[p * N + lane];
+    omv::wave_lds_sync();
+    bool r;
+    if constexpr (kPick) r = ldlt_pick_solve<N>(Hs, bs, xs, ord, Ls, lane);
+    else r = ldlt_pivot_solve_wave<N>(Hs, bs, xs, Ls, ord, lane);
+    omv::wave_lds_sync();
+    if (lane < N) x[p * N + lane] = xs[lane], order[p * N + lane] = ord[lane];
+    if (lane == 0) ok[p] = r ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(64) selftest_pinv15_kernel(const double *A, double *P, int32_t *path) {
+    __shared__ double As[225], Vs[225], Ps[225], cs[16];
+    __shared__ int pq[16];
+    const int p = blockIdx.x, lane = threadIdx.x;
+    for (int q = lane; q < 225; q += 64) As[q] = A[(size_t)p * 225 + q];
+    omv::wave_lds_sync();
+    // pinv15_wave's entry predicate (it leaves A untouched)
+    const double tau = 1e-6 + 1e-12 * max_abs_diag<15>(As, lane);
+    const bool fast = ldl_nopiv_wave<15>(As, tau, nullptr, lane) && ldl_nopiv_wave<15>(As, 0.0, Vs, lane);
+    pinv15_wave(As, Vs, Ps, cs, pq, lane);
+    omv::wave_lds_sync();
+    for (int q = lane; q < 225; q += 64) P[(size_t)p * 225 + q] = Ps[q];
+    if (lane == 0) path[p] = fast ? 1 : 0;
+}
+
+template <bool kPar>
+__global__ void __launch_bounds__(64) selftest_info9_kernel(const float *C, double *info, int32_t *path) {
+    __shared__ double sm[243 + 10 + 5], out[81];
+    const int p = blockIdx.x, lane = threadIdx.x;
+    inertial_info9_wave<kPar>(C + (size_t)p * 225, out, sm, lane);
+    omv::wave_lds_sync();
+    // sm + 81: the symmetrised inverse, untouched by the shortcut and diagonalised by the eigen-decomposition (whose
+    // eigenvectors are sm + 162, the identity before the first rotation)
+    bool same = true, clamp = false;
+    for (int q = lane; q < 81; q += 64) {
+        const int r = q / 9, c = q % 9;
+        same = same && __builtin_bit_cast(uint64_t, out[q]) == __builtin_bit_cast(uint64_t, sm[81 + q]) &&
+               sm[162 + q] == (r == c ? 1.0 : 0.0);
+        clamp = clamp || (r == c && sm[81 + q] < 1e-12);
+    }
+    const bool all_same = __ballot(!same) == 0, any_clamp = __ballot(clamp) != 0;
+    for (int q = lane; q < 81; q += 64) info[(size_t)p * 81 + q] = out[q];
+    if (lane == 0) path[p] = kPar && all_same ? 0 : any_clamp ? 2 : 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+omv_status omv_selftest_ldlt(int routine, int n, int batch, const double *H, const double *b, double *x, int32_t *order,
+                             int32_t *ok, void *stream) {
+    if (batch < 0 || (batch > 0 && (!H || !b || !x || !order || !ok))) return OMV_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int key = routine == 0 || routine == 1 ? 100 * routine + n : -1;
+    if (key != 6 && key != 9 && key != 24 && key != 115 && key != 130) return OMV_ERR_ARG;
+    if (batch == 0) return OMV_OK;
+    if (key == 6) selftest_ldlt_kernel<6, true><<<batch, 64, 0, st>>>(H, b, x, order, ok);
+    else if (key == 9) selftest_ldlt_kernel<9, true><<<batch, 64, 0, st>>>(H, b, x, order, ok);
+    else if (key == 24) selftest_ldlt_kernel<24, true><<<batch, 64, 0, st>>>(H, b, x, order, ok);
+    else if (key == 115) selftest_ldlt_kernel<15, false><<<batch, 64, 0, st>>>(H, b, x, order, ok);
+    else selftest_ldlt_kernel<30, false><<<batch, 64, 0, st>>>(H, b, x, order, ok);
+    HIP_OK(hipGetLastError());
+    return OMV_OK;
+}
+
+omv_status omv_selftest_pinv15(int batch, const double *A, double *P, int32_t *path, void *stream) {
+    if (batch < 0 || (batch > 0 && (!A || !P || !path))) return OMV_ERR_ARG;
+    if (batch == 0) return OMV_OK;
+    selftest_pinv15_kernel<<<batch, 64, 0, (hipStream_t)stream>>>(A, P, path);
+    HIP_OK(hipGetLastError());
+    return OMV_OK;
+}
+
+omv_status omv_selftest_inertial_info9(int par, int batch, const float *C, double *info, int32_t *path, void *stream) {
+    if (batch < 0 || (batch > 0 && (!C || !info || !path))) return OMV_ERR_ARG;
+    if (batch == 0) return OMV_OK;
+    if (par) selftest_info9_kernel<true><<<batch, 64, 0, (hipStream_t)stream>>>(C, info, path);
+    else selftest_info9_kernel<false><<<batch, 64, 0, (hipStream_t)stream>>>(C, info, path);
+    HIP_OK(hipGetLastError());
+    return OMV_OK;
+}
+
+}  // extern "C"

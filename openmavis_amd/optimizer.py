@@ -115,6 +115,25 @@ class LocalInertialBA:
                    "omv_lba_evaluate_stereo")
         return dict(mono_err=me, mono_jx=jx, mono_jp=jp, imu_err=ie, stereo_err=se, stereo_jx=sx, stereo_jp=sp)
 
+    def debug_solve(self, lambda_):
+        """One reduced-system solve at the uploaded state with damping `lambda_` (omv_lba_debug_solve; a test hook):
+        S [n][n] dense in keyframe order (n = 16 n_opt, padding rows included), rhs [n], x [n], the fail flag and the
+        solver's plan: mode (1 all blocks in LDS, 2 hybrid, 0 global), n_slots, n_lds, n_lev, cols (per level)."""
+        if self._s is None:
+            raise _lib.OmvError("LocalInertialBA.debug_solve: no problem set")
+        o = _lib.LbaOpts(10, 1e0, 10, 0)   # validated only: no option changes the robust kernels
+        nb = int(self._s.n_opt)
+        n = 16 * nb
+        S, rhs, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
+        plan = np.full(4 + nb, -1, np.int32)
+        fail = ctypes.c_int(-1)
+        _lib.check(self._lib.omv_lba_debug_solve(self._h, ctypes.byref(o), ctypes.c_double(lambda_), _lib.ptr(S),
+                                                 _lib.ptr(rhs), _lib.ptr(x), ctypes.byref(fail), _lib.ptr(plan),
+                                                 len(plan)), "omv_lba_debug_solve")
+        n_lev = int(plan[3])
+        return dict(S=S, rhs=rhs, x=x, fail=fail.value, mode=int(plan[0]), n_slots=int(plan[1]), n_lds=int(plan[2]),
+                    n_lev=n_lev, cols=[int(v) for v in plan[4:4 + n_lev]])
+
     def shard(self):
         """(caller indices of the landmarks this rank owns, number of its visual edges)."""
         n_p, n_e = ctypes.c_int32(0), ctypes.c_int32(0)
