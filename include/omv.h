@@ -987,6 +987,67 @@ omv_status omv_local_mapping_create_new_map_points(omv_matcher *m, const omv_cnm
                                                    float scale_factor, int32_t *n_matches, int32_t *side1_state,
                                                    void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h): the Horn RANSAC of LoopClosing::DetectCommonRegionsFromBoW
+ * (src/LoopClosing.cc:812-832), between SearchByBoW and SearchByProjection / SearchBySim3.  One handle holds n_jobs
+ * independent solvers (one per candidate pair); the phases are the reference's: constructor + SetRansacParameters
+ * (omv_sim3_solver_set), iterate / find (omv_sim3_solver_iterate), the GetEstimated* accessors (omv_sim3_solver_best).
+ * Arithmetic: float in the reference's order except ComputeSim3's eigenvector step (a Jacobi in double in place of
+ * Eigen::EigenSolver<Matrix4f> + atan2 + SO3f::exp: the same rotation, not the same bits).
+ * ---------------------------------------------------------------------------------------------- */
+#define OMV_SIM3_NO_MORE 1    /* flags bit 0: bNoMore   */
+#define OMV_SIM3_CONVERGE 2   /* flags bit 1: bConverge */
+typedef struct omv_sim3_solver omv_sim3_solver;
+
+/* max_jobs solvers, max_corr_total correspondences over all of them, max_hyp hypotheses per omv_sim3_solver_iterate. */
+omv_status omv_sim3_solver_create(int max_jobs, int max_corr_total, int max_hyp, omv_sim3_solver **out);
+omv_status omv_sim3_solver_destroy(omv_sim3_solver *h);
+
+/* The constructor's numeric part (:119-179) and SetRansacParameters(prob, min_inliers[j], max_its) (:184-207) for every
+ * job; resets the carried state (mnIterations = 0, mnBestInliers = 0).  Every pointer is HOST memory.  Job j owns the
+ * correspondences corr_start[j] .. corr_start[j+1]-1 (corr_start[0] = 0), in the order the constructor pushes them:
+ *   Xw1, Xw2    [n][3] pMP1 / pMP2->GetWorldPos()            sigma2_1, sigma2_2  [n] mvLevelSigma2[kp.octave] per side
+ *   index1      [n] mvnIndices1 (i1 in vpMatched12), each < mN1[j] = vpMatched12.size()
+ *   pose1/2     [n_jobs][12] Riw row-major then tiw: pKF->GetRotation / GetTranslation(cameraID)
+ *   cam1/2      [n_jobs][8] fx fy cx cy k0..k3, model1/2 [n_jobs] OMV_CAM_KB8 / OMV_CAM_PINHOLE, fix_scale [n_jobs]
+ * The thresholds keep the reference's quirk: mvnMaxError1/2 are std::vector<size_t>, so 9.210 * sigma2 is truncated to
+ * an unsigned integer.  ransac_max_its_out [n_jobs] (or NULL) receives mRansacMaxIts.  A job with fewer
+ * correspondences than min_inliers (iterate's entry test), or fewer than three (the reference is undefined there), is
+ * born with bNoMore and does no work.  OMV_ERR_ARG: an unknown camera model, a negative size, an index1 outside
+ * [0, mN1); OMV_ERR_CAPACITY: more jobs / correspondences than the handle's.  Synchronises `stream`. */
+omv_status omv_sim3_solver_set(omv_sim3_solver *h, int n_jobs, const int32_t *corr_start, const float *Xw1,
+                               const float *Xw2, const float *sigma2_1, const float *sigma2_2, const int32_t *index1,
+                               const int32_t *mN1, const float *pose1, const float *pose2, const float *cam1,
+                               const float *cam2, const int32_t *model1, const int32_t *model2, const int32_t *fix_scale,
+                               double prob, const int32_t *min_inliers, int max_its, int32_t *ransac_max_its_out,
+                               void *stream);
+
+/* iterate(nIterations, bNoMore, vbInliers, nInliers, bConverge) (:273-346) for every job, asynchronous on `stream`;
+ * every pointer is DEVICE memory.  draws [n_jobs][n_iterations][3]: for hypothesis k of the call the three values
+ * DUtils::Random::RandomInt(0, size-1) returns, draw i in [0, N-1-i] (out-of-range values are clamped).  A job runs
+ * min(n_iterations, mRansacMaxIts - mnIterations) hypotheses, stops at the first one the reference returns from, and
+ * is skipped once it has converged or is exhausted (its outputs are repeated).  Draws after a convergence are unused:
+ * a caller that mirrors rand() draws them all the same, so its rand() sequence runs ahead of the reference's.
+ *   T12_out [n_jobs][16] row-major: mBestT12 (the converged hypothesis, else the best so far -- the reference's
+ *           5-argument iterate returns an uninitialised matrix when no hypothesis of the chunk reached the carried best;
+ *           identity before any hypothesis).  The 4-argument iterate / find return identity unless bConverge.
+ *   n_inliers_out [n_jobs]; inliers_out: vbInliers, job j's mN1[j] bytes at sum(mN1[0..j-1]);
+ *   flags_out [n_jobs]: OMV_SIM3_NO_MORE | OMV_SIM3_CONVERGE.  n_iterations <= max_hyp (OMV_ERR_CAPACITY). */
+omv_status omv_sim3_solver_iterate(omv_sim3_solver *h, int n_iterations, const int32_t *draws, float *T12_out,
+                                   int32_t *n_inliers_out, uint8_t *inliers_out, int32_t *flags_out, void *stream);
+
+/* GetEstimatedRotation / Translation / Scale of job `job` (mBestRotation row-major, mBestTranslation, mBestScale), with
+ * mnBestInliers and mnIterations; host outputs, any may be NULL.  Synchronises `stream`. */
+omv_status omv_sim3_solver_best(omv_sim3_solver *h, int job, float *R, float *t, float *scale, int32_t *n_best,
+                                int32_t *iterations, void *stream);
+
+/* Test hook: the hypotheses job `job` evaluated in the last omv_sim3_solver_iterate call, host outputs (any but n_hyp
+ * may be NULL): n_hyp = H, idx [H][3] the sampled correspondences, R [H][9], t [H][3], scale [H], T12 / T21 [H][16],
+ * count [H] mnInliersi, mask_words [H][ceil(N / 64)] mvbInliersi (bit i of word i / 64).  Synchronous. */
+omv_status omv_sim3_solver_debug(omv_sim3_solver *h, int job, int32_t *n_hyp, int32_t *idx, float *R, float *t,
+                                 float *scale, float *T12, float *T21, int32_t *count, uint64_t *mask_words,
+                                 void *stream);
+
 /* ---- Test hooks (no reference counterpart): the device linear-algebra routines on plain device arrays ----
  * Each launches the product's own instantiation of the routine, one workgroup per problem (`batch` problems, on
  * `stream`, not synchronised).  Every pointer is device memory. */

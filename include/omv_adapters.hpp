@@ -28,6 +28,9 @@
 //   MapPointRefresh         MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth over a batch of points
 //   SearchInNeighborsFuse   LocalMapping::SearchInNeighbors' fuse sequence (src/LocalMapping.cc:837-889): the final
 //                           graph and the edit log (AddObservation / Replace) to replay on the reference's objects
+//   Sim3Solver              Sim3Solver (src/Sim3Solver.cc) at LoopClosing::DetectCommonRegionsFromBoW's call site
+//                           (src/LoopClosing.cc:812-832): constructor, SetRansacParameters, both iterate overloads,
+//                           find, GetEstimated*; the samples drawn with std::rand() in RandomInt's formula
 //
 // Errors: every omv_status != OMV_OK throws omv_adapt::Error (the adapters' callers are C++).
 #ifndef OMV_ADAPTERS_HPP
@@ -39,6 +42,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -1302,6 +1306,116 @@ class LocalInertialBAWindow {
     int rank_ = 0, world_ = 1;
     omv_allreduce_fn ar_ = nullptr;
     void *ar_ctx_ = nullptr;
+};
+
+// ---- Sim3Solver --------------------------------------------------------------------------------------------
+// The constructor's output (:119-179), flattened by the caller from the reference's objects after its camera-pair
+// vote: per kept correspondence the two world positions, the two level sigma2 and i1; the chosen cameras' poses and
+// intrinsics.
+struct Sim3SolverInput {
+    std::vector<float> Xw1, Xw2;             // [N][3] pMP1 / pMP2->GetWorldPos()
+    std::vector<float> sigma2_1, sigma2_2;   // [N] pKF->mvLevelSigma2[kp.octave]
+    std::vector<int32_t> index1;             // [N] mvnIndices1
+    int mN1 = 0;                             // vpMatched12.size()
+    float pose1[12] = {}, pose2[12] = {};    // GetRotation(cameraID) row-major, GetTranslation(cameraID)
+    float cam1[8] = {}, cam2[8] = {};        // fx fy cx cy k0..k3
+    int model1 = OMV_CAM_KB8, model2 = OMV_CAM_KB8;
+    bool fix_scale = false;
+};
+
+// One solver (one job of the batched handle) with the reference's call shape.  Matrices are row-major float arrays.
+// The draws of a call are made up front with std::rand() in DUtils::Random::RandomInt's formula, three per hypothesis
+// the call may run; the reference stops drawing at a convergence, so after one the rand() stream is further along here.
+class Sim3Solver {
+  public:
+    explicit Sim3Solver(const Sim3SolverInput &in, int max_iterations = 300, hipStream_t stream = nullptr)
+        : in_(in), st_(stream), max_hyp_(std::max(1, max_iterations)) {
+        check(omv_sim3_solver_create(1, (int)in_.index1.size(), max_hyp_, &h_), "omv_sim3_solver_create");
+        d_T12_.resize(16), d_n_.resize(1), d_flags_.resize(1), d_inl_.resize(std::max(1, in_.mN1));
+        SetRansacParameters();   // the constructor's last line (:181)
+    }
+    Sim3Solver(const Sim3Solver &) = delete;
+    Sim3Solver &operator=(const Sim3Solver &) = delete;
+    ~Sim3Solver() {
+        if (h_) (void)omv_sim3_solver_destroy(h_);
+    }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        if (maxIterations > max_hyp_) throw Error("Sim3Solver: maxIterations above the constructor's max_iterations");
+        const int32_t corr_start[2] = {0, (int32_t)in_.index1.size()};
+        const int32_t mn1 = in_.mN1, m1 = in_.model1, m2 = in_.model2, fs = in_.fix_scale ? 1 : 0, mi = minInliers;
+        check(omv_sim3_solver_set(h_, 1, corr_start, in_.Xw1.data(), in_.Xw2.data(), in_.sigma2_1.data(),
+                                  in_.sigma2_2.data(), in_.index1.data(), &mn1, in_.pose1, in_.pose2, in_.cam1, in_.cam2,
+                                  &m1, &m2, &fs, probability, &mi, maxIterations, &max_its_, st_),
+              "omv_sim3_solver_set");
+    }
+
+    // iterate(nIterations, bNoMore, vbInliers, nInliers, bConverge): T12 [16].  Where the reference returns an
+    // uninitialised matrix (no hypothesis of the chunk reached the carried best) this returns the carried mBestT12.
+    std::array<float, 16> iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers,
+                                  bool &bConverge) {
+        const int n_it = std::min(nIterations, max_hyp_);
+        const int N = (int)in_.index1.size();
+        std::vector<int32_t> draws((size_t)3 * std::max(n_it, 1));
+        for (int k = 0; k < n_it; k++)
+            for (int i = 0; i < 3; i++) draws[3 * k + i] = RandomInt(0, std::max(N - i, 1) - 1);
+        d_draws_.upload(draws.data(), draws.size(), st_);
+        check(omv_sim3_solver_iterate(h_, n_it, d_draws_.p, d_T12_.p, d_n_.p, d_inl_.p, d_flags_.p, st_),
+              "omv_sim3_solver_iterate");
+        std::array<float, 16> T12;
+        int32_t n = 0, flags = 0;
+        std::vector<uint8_t> inl(std::max(1, in_.mN1));
+        d_T12_.download(T12.data(), 16, st_), d_n_.download(&n, 1, st_), d_flags_.download(&flags, 1, st_);
+        d_inl_.download(inl.data(), inl.size(), st_);
+        hip_check(hipStreamSynchronize(st_), "hipStreamSynchronize");
+        bNoMore = (flags & OMV_SIM3_NO_MORE) != 0, bConverge = (flags & OMV_SIM3_CONVERGE) != 0, nInliers = n;
+        vbInliers.assign(in_.mN1, false);
+        for (int i = 0; i < in_.mN1; i++) vbInliers[i] = inl[i] != 0;
+        return T12;
+    }
+    // iterate(nIterations, bNoMore, vbInliers, nInliers): identity unless the call converged
+    std::array<float, 16> iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers) {
+        bool conv = false;
+        const std::array<float, 16> T12 = iterate(nIterations, bNoMore, vbInliers, nInliers, conv);
+        return conv ? T12 : std::array<float, 16>{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    }
+    std::array<float, 16> find(std::vector<bool> &vbInliers12, int &nInliers) {
+        bool flag = false;
+        return iterate(max_its_, flag, vbInliers12, nInliers);
+    }
+
+    std::array<float, 9> GetEstimatedRotation() {
+        std::array<float, 9> R;
+        check(omv_sim3_solver_best(h_, 0, R.data(), nullptr, nullptr, nullptr, nullptr, st_), "omv_sim3_solver_best");
+        return R;
+    }
+    std::array<float, 3> GetEstimatedTranslation() {
+        std::array<float, 3> t;
+        check(omv_sim3_solver_best(h_, 0, nullptr, t.data(), nullptr, nullptr, nullptr, st_), "omv_sim3_solver_best");
+        return t;
+    }
+    float GetEstimatedScale() {
+        float s = 1.f;
+        check(omv_sim3_solver_best(h_, 0, nullptr, nullptr, &s, nullptr, nullptr, st_), "omv_sim3_solver_best");
+        return s;
+    }
+    int ransac_max_its() const { return max_its_; }
+
+    // DUtils::Random::RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp:47-50)
+    static int RandomInt(int min, int max) {
+        const int d = max - min + 1;
+        return int(((double)std::rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+    }
+
+  private:
+    Sim3SolverInput in_;
+    hipStream_t st_;
+    int max_hyp_;
+    int32_t max_its_ = 1;
+    omv_sim3_solver *h_ = nullptr;
+    DeviceArray<int32_t> d_draws_, d_n_, d_flags_;
+    DeviceArray<float> d_T12_;
+    DeviceArray<uint8_t> d_inl_;
 };
 
 }  // namespace omv_adapt

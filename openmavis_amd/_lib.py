@@ -331,6 +331,12 @@ SIGNATURES = {
     "omv_selftest_inv16": (_I, [_I, _VP, _VP, _VP, _VP]),
     "omv_lba_debug_solve": (_I, [_VP, ctypes.POINTER(LbaOpts), ctypes.c_double, _VP, _VP, _VP, ctypes.POINTER(_I),
                                  _VP, _I]),
+    "omv_sim3_solver_create": (_I, [_I, _I, _I, ctypes.POINTER(_VP)]),
+    "omv_sim3_solver_destroy": (_I, [_VP]),
+    "omv_sim3_solver_set": (_I, [_VP, _I] + [_VP] * 14 + [ctypes.c_double, _VP, _I, _VP, _VP]),
+    "omv_sim3_solver_iterate": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "omv_sim3_solver_best": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "omv_sim3_solver_debug": (_I, [_VP, _I] + [_VP] * 10),
 }
 
 _lib = None

@@ -17,7 +17,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("OMV_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["orb_extract.hip", "match.hip", "lba.hip", "pose.hip", "tri.hip", "frame.hip", "imu.hip", "bow.hip", "bowmatch.hip",
-               "mappoint.hip", "fuse.hip"]
+               "mappoint.hip", "fuse.hip", "sim3.hip"]
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
              f"--offload-arch={ARCH}", "-Wno-unused-result"]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
@@ -78,31 +78,35 @@ def build_oracle(verbose=True):
 
 CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "omv_consumer.cpp")
 CONSUMER_BIN = os.path.join(PKG, "bin", "omv_consumer")
+SIM3_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "sim3_solver_consumer.cpp")
+SIM3_CONSUMER_BIN = os.path.join(PKG, "bin", "sim3_solver_consumer")
 
 
-def build_consumer(verbose=True):
-    """tests/cpp/omv_consumer.cpp: a plain C++ (g++) consumer of include/omv.h + include/omv_adapters.hpp, linked
-    against libomv_hip.so and the HIP runtime only (test infrastructure for the C++ integration path)."""
-    deps = [CONSUMER_SRC, os.path.join(ROOT, "include", "omv.h"), os.path.join(ROOT, "include", "omv_adapters.hpp"), LIB]
-    if not os.path.exists(CONSUMER_SRC) or not _newer(CONSUMER_BIN, deps):
-        return CONSUMER_BIN
-    os.makedirs(os.path.dirname(CONSUMER_BIN), exist_ok=True)
+def build_consumer(verbose=True, src=CONSUMER_SRC, out=CONSUMER_BIN):
+    """tests/cpp/omv_consumer.cpp (or `src`, e.g. sim3_solver_consumer.cpp): a plain C++ (g++) consumer of include/omv.h
+    + include/omv_adapters.hpp, linked against libomv_hip.so and the HIP runtime only (test infrastructure for the C++
+    integration path)."""
+    deps = [src, os.path.join(ROOT, "include", "omv.h"), os.path.join(ROOT, "include", "omv_adapters.hpp"), LIB]
+    if not os.path.exists(src) or not _newer(out, deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__",
-           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(rocm, "include"), CONSUMER_SRC,
-           "-o", CONSUMER_BIN + ".tmp", "-L", PKG, "-lomv_hip", "-Wl,-rpath,$ORIGIN/..",
+           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(rocm, "include"), src,
+           "-o", out + ".tmp", "-L", PKG, "-lomv_hip", "-Wl,-rpath,$ORIGIN/..",
            "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-lrccl", "-Wl,-rpath," + os.path.join(rocm, "lib")]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)
-    os.replace(CONSUMER_BIN + ".tmp", CONSUMER_BIN)
-    return CONSUMER_BIN
+    os.replace(out + ".tmp", out)
+    return out
 
 
 def build_all(force=False, verbose=True):
     build_oracle(verbose)
     lib = build_hip(force, verbose)
     build_consumer(verbose)
+    build_consumer(verbose, SIM3_CONSUMER_SRC, SIM3_CONSUMER_BIN)
     return lib
 
 
