@@ -271,8 +271,13 @@ __host__ inline int xcd_grid(int n_logical) { return (n_logical + 7) & ~7; }
 // v_mul_u32_u24 (full rate) for operands the caller knows are < 2^24: HIP's __umul24 masks its operands and the
 // backend then emits v_and + v_mul_lo_u32 (quarter rate) unless it can prove the mask redundant.
 extern "C" __device__ __attribute__((const)) uint32_t omv_llvm_mul_u24(uint32_t, uint32_t) __asm("llvm.amdgcn.mul.u24.i32");
+extern "C" __device__ __attribute__((const)) uint32_t omv_llvm_mulhi_u24(uint32_t, uint32_t) __asm("llvm.amdgcn.mulhi.u24");
 namespace omv {
 __device__ __forceinline__ int mul_u24(int a, int b) { return (int)omv_llvm_mul_u24((uint32_t)a, (uint32_t)b); }
+// v_mul_hi_u32_u24 (full rate): bits 32..47 of the product of two operands the caller knows are < 2^24.  With
+// b < 2^16 and s < 2^16, mulhi_u24(b << 8, s << 8) == (b * s) >> 16 exactly: the product b s 2^16 is < 2^48, so
+// nothing is lost above, and its low 16 bits are zero, so the shift by 32 drops the same bits as b s >> 16.
+__device__ __forceinline__ uint32_t mulhi_u24(uint32_t a, uint32_t b) { return omv_llvm_mulhi_u24(a, b); }
 
 // Test knobs of a matcher handle (OMV_BOW_TOP, OMV_TRI_SLICES, OMV_TRI_ECAP, OMV_TRI_WALK, OMV_CAND, OMV_CAND_PW),
 // read once by omv_matcher_create (not per call); -1 / 0: unset.  Defined in match.hip for the other matcher

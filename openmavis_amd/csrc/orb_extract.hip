@@ -107,13 +107,21 @@ struct XTab {
 
 // One output quad (dx = 4q .. 4q+3) of a resize row: pixel pair p = j >> 1 reads the two source dwords at dword
 // index a[p] of the staged row; sel[j] is the v_perm selector that lays (src[sx0], src[sx1]) of pixel j out as a
-// u16 pair, cf[j] = (a0, a1) as a u16 pair, so h = v_dot2_u32_u16(perm, cf) = src[sx0] a0 + src[sx1] a1 exactly.
+// u16 pair, cf[j] = (16 a0, 16 a1) as a u16 pair (a <= 2048, so 16 a fits), so H = v_dot2_u32_u16(perm, cf) =
+// 16 (src[sx0] a0 + src[sx1] a1) exactly, < 2^24.
 struct __attribute__((aligned(16))) XQuad {
     int a[2];
     uint32_t sel[4], cf[4];
     int pad[2];
 };
-static_assert(sizeof(XQuad) == 48, "XQuad LDS addressing");
+static_assert(sizeof(XQuad) == 48, "XQuad: three 16-byte loads");
+
+// One output row of the quad path as a workgroup stages it in LDS: the byte offsets of its two source rows inside
+// the staged source block, and its coefficients as b << 8 (omv::mulhi_u24's operand form; 0 <= b <= 2048).
+struct __attribute__((aligned(16))) YRow {
+    int o0, o1;
+    uint32_t b0, b1;
+};
 
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ const uint8_t *level_base(const Geom &g, const uint8_t *images, size_t img_stride,
@@ -130,15 +138,110 @@ __device__ __forceinline__ const uint8_t *level_base(const Geom &g, const uint8_
 // K1 --------------------------------------------------------------------------------------------
 // One workgroup per (block of kPyrBlock output rows, image) of level l: the source rows of level l-1
 // the block reads (y.sx0 of its first row .. y.sx1 of its last, ~1.2 kPyrBlock + 2) are staged in LDS
-// once with 16-byte loads, together with the level's x table; each thread then computes 4 adjacent
-// output pixels per step and stores them as one dword (level pitches are 16-byte aligned).
+// once with 16-byte loads.  Quad path (every level of the usual scale factors): the block is dealt out strip-major
+// as (strip of kPyrStrip rows, output quad column) tasks, so a wave's lanes mostly share a strip and with it the
+// rows and the reuse branches of pyr_strip; the column's table entry comes straight from memory into registers.
+// Generic path: the level's x table is staged too, and each thread computes 4 adjacent output pixels per step.
+// Either way a quad is stored as one dword (level pitches are 16-byte aligned).
 constexpr int kPyrBlock = 16;
+constexpr size_t kPyrLdsHold = 24 * 1024;   // omv_orb_create: a quad-path level holds its LDS request up to here (occupancy cap)
 
 // cv::resize's vertical pass on the horizontal sums: (b0 (h0 >> 4) >> 16) + (b1 (h1 >> 4) >> 16) + 2 >> 2.  The
 // coefficients are < 2^12 and h >> 4 < 2^15 (both non-negative), so the products are 24-bit multiplies at full rate
 // (an int multiply is v_mul_lo_u32, a quarter-rate instruction: 8 of them per output quad).
 __device__ __forceinline__ int vmix(int b0, int b1, int h0, int h1) {
     return ((omv::mul_u24(b0, h0 >> 4) >> 16) + (omv::mul_u24(b1, h1 >> 4) >> 16) + 2) >> 2;
+}
+
+// The quad path's inner routine, shared by pyr_resize_kernel and pyr_chain_kernel: one thread forms output quad
+// column X over n <= kPyrStrip consecutive output rows (ys[0 .. n), staged in LDS) from the source rows staged at
+// `rows`, and hands each row's four pixels to emit(packed).
+//   * the column's table entry, its two LDS column bases and the y entry's row offsets are formed once per strip /
+//     per row, not per quad;
+//   * the masked horizontal sums (H & ~0xff = (h >> 4) << 8, omv::mulhi_u24's operand form) of the last two source
+//     rows stay in registers: a source row is summed only when it is neither of them (at scale 1.2 consecutive
+//     output rows share a source row four times out of five).  hA / hB always hold rows o0 / o1 of the row just
+//     emitted, whatever the tables say (repeated, skipped or clamped rows); no staged row has offset -1, so the
+//     first row of a strip sums both;
+//   * a pixel is (mulhi(b0, hA) + mulhi(b1, hB) + 2) >> 2: cv::resize's (b0 (h0 >> 4) >> 16) + (b1 (h1 >> 4) >> 16)
+//     + 2 >> 2 with one instruction per product (omv::mulhi_u24) and no shifts.
+constexpr int kPyrStrip = 8;
+
+__device__ __forceinline__ void pyr_hsums(uint32_t h[4], const XQuad &X, const char *c0, const char *c1, int o) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    const uint32_t *p0 = reinterpret_cast<const uint32_t *>(c0 + o), *p1 = reinterpret_cast<const uint32_t *>(c1 + o);
+    const uint32_t u[4] = {p0[0], p0[1], p1[0], p1[1]};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int pp = 2 * (j >> 1);
+        h[j] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, __builtin_amdgcn_perm(u[pp + 1], u[pp], X.sel[j])),
+                                      __builtin_bit_cast(u16x2, X.cf[j]), 0u, false) & 0xffffff00u;
+    }
+}
+
+template <class Emit>
+__device__ __forceinline__ void pyr_strip(const XQuad &X, const uint32_t *rows, const YRow *ys, int n, Emit emit) {
+    const char *c0 = reinterpret_cast<const char *>(rows + X.a[0]), *c1 = reinterpret_cast<const char *>(rows + X.a[1]);
+    uint32_t hA[4], hB[4];
+    int idA = -1, idB = -1;
+    for (int r = 0; r < n; ++r) {
+        const YRow y = ys[r];
+        if (y.o0 != idA) {
+            if (y.o0 == idB) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) hA[j] = hB[j];
+            } else {
+                pyr_hsums(hA, X, c0, c1, y.o0);
+            }
+            idA = y.o0;
+        }
+        if (y.o1 != idB) {   // summed again even when it is row o0 (the clamped last row): a copy would cost every row
+            pyr_hsums(hB, X, c0, c1, y.o1);
+            idB = y.o1;
+        }
+        uint32_t packed = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)   // <= 255: the weights sum to <= 2049
+            packed |= ((omv::mulhi_u24(y.b0, hA[j]) + omv::mulhi_u24(y.b1, hB[j]) + 2) >> 2) << (8 * j);
+        emit(packed);
+    }
+}
+
+// nr source rows of n4 16-byte groups each (row pitch sp bytes, m4 = ceil(2^32 / n4)) into LDS, by the 256 threads of
+// a workgroup with four loads in flight per thread: one load per trip left a thread waiting out ~4 (720 px) to ~10
+// (1080p) memory round trips in a row before the barrier
+__device__ __forceinline__ void pyr_stage16(uint32_t *rows, const uint8_t *src, size_t sp, int nr, int n4, uint32_t m4,
+                                            int tid) {
+    const int total = nr * n4;
+    for (int q = tid; q < total; q += 4 * 256) {
+        uint4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int qk = min(q + 256 * k, total - 1);   // past the end: the last group again, not stored
+            const int r = (int)__umulhi((uint32_t)qk, m4), i = qk - r * n4;
+            v[k] = reinterpret_cast<const uint4 *>(src + (size_t)r * sp)[i];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (q + 256 * k < total) reinterpret_cast<uint4 *>(rows)[q + 256 * k] = v[k];
+    }
+}
+
+// a staged y entry of the quad path from the table's: sbase = the first staged source row, ndw = dwords per staged row
+__device__ __forceinline__ YRow pyr_yrow(const XTab y, int sbase, int ndw) {
+    return YRow{omv::mul_u24(y.sx0 - sbase, ndw) * 4, omv::mul_u24(y.sx1 - sbase, ndw) * 4,
+                ((uint32_t)y.coef & 0xffffu) << 8, ((uint32_t)y.coef >> 16) << 8};
+}
+
+// four output pixels at dst: one dword, or the `left` < 4 pixels of a level's last, partial quad
+__device__ __forceinline__ void pyr_store(uint8_t *dst, uint32_t packed, int left) {
+    if (left >= 4) {
+        *reinterpret_cast<uint32_t *>(dst) = packed;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (j < left) dst[j] = (uint8_t)(packed >> (8 * j));
+    }
 }
 
 __global__ void __launch_bounds__(256) pyr_resize_kernel(Geom g, int l, const uint8_t *images, size_t img_stride,
@@ -153,26 +256,30 @@ __global__ void __launch_bounds__(256) pyr_resize_kernel(Geom g, int l, const ui
     const int sw = g.lv[l - 1].w;
     const int ndw = ((sw + 15) >> 4) << 2;   // LDS row: whole 16-byte groups
     const int nq = (L.w + 3) >> 2;
-    XTab *xs = reinterpret_cast<XTab *>(pyr_lds);            // [L.w]  (generic path)
-    XQuad *xqs = reinterpret_cast<XQuad *>(pyr_lds);         // [nq]   (quad path)
-    uint32_t *rows = pyr_lds + 12 * nq;                      // [nr][ndw] (+4 dwords of slack)
+    const bool quad = L.use_xq != 0;
+    XTab *xs = reinterpret_cast<XTab *>(pyr_lds);            // [L.w]  (generic path only)
+    uint32_t *rows = pyr_lds + (quad ? 0 : 12 * nq);         // [nr][ndw] (+4 dwords of slack)
     const int sy0 = yt[L.ytab_off + dy0].sx0, sy1 = yt[L.ytab_off + dy1 - 1].sx1;
     const int nr = sy1 - sy0 + 1;
-    XTab *ys = reinterpret_cast<XTab *>(rows + nr * ndw + 4);   // [kPyrBlock] the block's y entries
-    const bool quad = L.use_xq != 0;
-    if (quad)
-        for (int i = tid; i < nq; i += 256) xqs[i] = xq[L.xq_off + i];
-    else
+    // the quad path's tasks: (strip of kPyrStrip rows, quad column), strip-major; a thread's first column entry is
+    // loaded ahead of the staging, which hides its latency
+    const int nt = quad ? ((dy1 - dy0 + kPyrStrip - 1) / kPyrStrip) * nq : 0;
+    const uint32_t mq = L.m_quads;
+    int s = (int)__umulhi((uint32_t)tid, mq), qd = tid - omv::mul_u24(s, nq);
+    XQuad X{};
+    if (tid < nt) X = xq[L.xq_off + qd];
+    XTab *ys = reinterpret_cast<XTab *>(rows + nr * ndw + 4);   // [kPyrBlock] the block's y entries (generic path)
+    YRow *ysq = reinterpret_cast<YRow *>(rows + nr * ndw + 4);  // [kPyrBlock]                       (quad path)
+    if (!quad)
         for (int i = tid; i < L.w; i += 256) xs[i] = xt[L.xtab_off + i];
-    if (tid < dy1 - dy0) ys[tid] = yt[L.ytab_off + dy0 + tid];
+    if (tid < dy1 - dy0) {
+        const XTab y = yt[L.ytab_off + dy0 + tid];
+        if (quad) ysq[tid] = pyr_yrow(y, sy0, ndw);
+        else ys[tid] = y;
+    }
     // q / d as __umulhi(q, ceil(2^32 / d)): exact for q < 2^32 / d (q < 2^16 here)
     if ((sp & 15) == 0 && (((uintptr_t)src) & 15) == 0) {   // 16-byte loads (the groups stay inside the pitch)
-        const int n4 = ndw >> 2;
-        const uint32_t m4 = g.lv[l - 1].m_groups;
-        for (int q = tid; q < nr * n4; q += 256) {
-            const int r = (int)__umulhi((uint32_t)q, m4), i = q - r * n4;
-            reinterpret_cast<uint4 *>(rows)[q] = reinterpret_cast<const uint4 *>(src + (size_t)(sy0 + r) * sp)[i];
-        }
+        pyr_stage16(rows, src + (size_t)sy0 * sp, (size_t)sp, nr, ndw >> 2, g.lv[l - 1].m_groups, tid);
     } else {
         uint8_t *b = reinterpret_cast<uint8_t *>(rows);
         const uint32_t mw = g.lv[l - 1].m_w;
@@ -182,53 +289,43 @@ __global__ void __launch_bounds__(256) pyr_resize_kernel(Geom g, int l, const ui
         }
     }
     __syncthreads();
-    const uint32_t mq = L.m_quads;
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    uint8_t *out = pyr + (size_t)img * g.pyr_bytes + L.off + (size_t)dy0 * L.pitch;
+    if (quad) {
+        for (int t = tid; t < nt; t += 256) {
+            if (t != tid) {   // strip / column split as 24-bit multiplies (s <= kPyrBlock, nq < 2^12)
+                s = (int)__umulhi((uint32_t)t, mq), qd = t - omv::mul_u24(s, nq);
+                X = xq[L.xq_off + qd];
+            }
+            const int r0 = s * kPyrStrip, left = L.w - 4 * qd, pitch = L.pitch;
+            uint8_t *dst = out + (size_t)omv::mul_u24(r0, pitch) + 4 * qd;
+            pyr_strip(X, rows, ysq + r0, min(kPyrStrip, dy1 - dy0 - r0), [&](uint32_t packed) {
+                pyr_store(dst, packed, left);
+                dst += pitch;
+            });
+        }
+        return;
+    }
     for (int q = tid; q < (dy1 - dy0) * nq; q += 256) {
         // row / column split and LDS row offsets as 24-bit multiplies (r < kPyrBlock, nq and ndw < 2^12)
-        const int r = (int)__umulhi((uint32_t)q, mq), qd = q - omv::mul_u24(r, nq), dx0 = qd * 4,
-                  dy = dy0 + r;
+        const int r = (int)__umulhi((uint32_t)q, mq), qd = q - omv::mul_u24(r, nq), dx0 = qd * 4;
         const XTab y = ys[r];
         const int b0 = (short)(y.coef & 0xffff), b1 = (short)(y.coef >> 16);
         uint32_t packed = 0;
-        if (quad) {
-            const XQuad X = *reinterpret_cast<const XQuad *>(reinterpret_cast<const char *>(xqs) + omv::mul_u24(qd, 48u));
-            const uint32_t *R0 = rows + omv::mul_u24(y.sx0 - sy0, ndw),
-                           *R1 = rows + omv::mul_u24(y.sx1 - sy0, ndw);
-            const uint32_t u0[4] = {R0[X.a[0]], R0[X.a[0] + 1], R0[X.a[1]], R0[X.a[1] + 1]};
-            const uint32_t u1[4] = {R1[X.a[0]], R1[X.a[0] + 1], R1[X.a[1]], R1[X.a[1] + 1]};
+        const uint8_t *R0 = reinterpret_cast<const uint8_t *>(rows + omv::mul_u24(y.sx0 - sy0, ndw));
+        const uint8_t *R1 = reinterpret_cast<const uint8_t *>(rows + omv::mul_u24(y.sx1 - sy0, ndw));
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int pp = 2 * (j >> 1);
-                const u16x2 cf = __builtin_bit_cast(u16x2, X.cf[j]);
-                const int h0 = (int)__builtin_amdgcn_udot2(
-                    __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(u0[pp + 1], u0[pp], X.sel[j])), cf, 0u, false);
-                const int h1 = (int)__builtin_amdgcn_udot2(
-                    __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(u1[pp + 1], u1[pp], X.sel[j])), cf, 0u, false);
-                packed |= (uint32_t)vmix(b0, b1, h0, h1) << (8 * j);   // <= 255: the weights sum to <= 2049
-            }
-        } else {
-            const uint8_t *R0 = reinterpret_cast<const uint8_t *>(rows + omv::mul_u24(y.sx0 - sy0, ndw));
-            const uint8_t *R1 = reinterpret_cast<const uint8_t *>(rows + omv::mul_u24(y.sx1 - sy0, ndw));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int dx = dx0 + j;
-                if (dx < L.w) {
-                    const XTab x = xs[dx];
-                    const int a0 = (short)(x.coef & 0xffff), a1 = (short)(x.coef >> 16);
-                    const int h0 = R0[x.sx0] * a0 + R0[x.sx1] * a1;
-                    const int h1 = R1[x.sx0] * a0 + R1[x.sx1] * a1;
-                    const int v = vmix(b0, b1, h0, h1);
-                    packed |= (uint32_t)min(v, 255) << (8 * j);
-                }
+        for (int j = 0; j < 4; ++j) {
+            const int dx = dx0 + j;
+            if (dx < L.w) {
+                const XTab x = xs[dx];
+                const int a0 = (short)(x.coef & 0xffff), a1 = (short)(x.coef >> 16);
+                const int h0 = R0[x.sx0] * a0 + R0[x.sx1] * a1;
+                const int h1 = R1[x.sx0] * a0 + R1[x.sx1] * a1;
+                const int v = vmix(b0, b1, h0, h1);
+                packed |= (uint32_t)min(v, 255) << (8 * j);
             }
         }
-        uint8_t *dst = pyr + (size_t)img * g.pyr_bytes + L.off + (size_t)dy * L.pitch;
-        if (dx0 + 3 < L.w) {
-            *reinterpret_cast<uint32_t *>(dst + dx0) = packed;
-        } else {
-            for (int j = 0; j < 4 && dx0 + j < L.w; ++j) dst[dx0 + j] = (uint8_t)(packed >> (8 * j));
-        }
+        pyr_store(out + (size_t)r * L.pitch + dx0, packed, L.w - dx0);
     }
 }
 
@@ -250,23 +347,18 @@ __global__ void __launch_bounds__(256) pyr_chain_kernel(Geom g, const uint8_t *i
     const int b = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
     const PyrBand *B = bands + (size_t)b * kMaxLevels;
     uint32_t *prev = pyr_lds, *cur = pyr_lds + buf_dw;
-    // the level's x table (quads or pixels) and the y entries of its needed rows, staged per level: every output
-    // quad of the band reads them (from memory that was 48 + 12 bytes of table traffic per 4 output pixels)
+    // the generic path's x table and the y entries of the level's needed rows, staged per level (the quad path's
+    // table entry goes from memory into each strip's registers)
     uint32_t *tab = pyr_lds + 2 * (size_t)buf_dw + 4;
     XTab *ys = reinterpret_cast<XTab *>(tab + tab_dw);
-    XQuad *xqs = reinterpret_cast<XQuad *>(tab);
+    YRow *ysq = reinterpret_cast<YRow *>(tab + tab_dw);
     XTab *xs = reinterpret_cast<XTab *>(tab);
     {   // level 0's needed rows from the image
         const PyrBand b0 = B[0];
         const int sw = g.lv[0].w, ndw = ((sw + 15) >> 4) << 2, nr = b0.need_hi - b0.need_lo;
         const uint8_t *src = images + (size_t)img * img_stride;
         if ((pitch0 & 15) == 0 && (((uintptr_t)src) & 15) == 0) {
-            const int n4 = ndw >> 2;
-            const uint32_t m4 = g.lv[0].m_groups;
-            for (int q = tid; q < nr * n4; q += 256) {
-                const int r = (int)__umulhi((uint32_t)q, m4), i = q - r * n4;
-                reinterpret_cast<uint4 *>(prev)[q] = reinterpret_cast<const uint4 *>(src + (size_t)(b0.need_lo + r) * pitch0)[i];
-            }
+            pyr_stage16(prev, src + (size_t)b0.need_lo * pitch0, pitch0, nr, ndw >> 2, g.lv[0].m_groups, tid);
         } else {
             uint8_t *bb = reinterpret_cast<uint8_t *>(prev);
             const uint32_t mw = g.lv[0].m_w;
@@ -277,43 +369,44 @@ __global__ void __launch_bounds__(256) pyr_chain_kernel(Geom g, const uint8_t *i
         }
     }
     __syncthreads();
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
     for (int l = 1; l < g.nlevels; ++l) {
         const LevelGeom &L = g.lv[l];
         const PyrBand bp = B[l - 1], bc = B[l];
         const int sndw = ((g.lv[l - 1].w + 15) >> 4) << 2, cndw = ((L.w + 15) >> 4) << 2;
         const int nq = (L.w + 3) >> 2, nr = bc.need_hi - bc.need_lo;
         const bool quad = L.use_xq != 0;
-        if (quad)
-            for (int i = tid; i < nq; i += 256) xqs[i] = xq[L.xq_off + i];
-        else
+        if (!quad)
             for (int i = tid; i < L.w; i += 256) xs[i] = xt[L.xtab_off + i];
-        for (int i = tid; i < nr; i += 256) ys[i] = yt[L.ytab_off + bc.need_lo + i];
+        for (int i = tid; i < nr; i += 256) {
+            const XTab y = yt[L.ytab_off + bc.need_lo + i];
+            if (quad) ysq[i] = pyr_yrow(y, bp.need_lo, sndw);
+            else ys[i] = y;
+        }
         __syncthreads();
         const uint32_t mq = L.m_quads;
-        for (int q = tid; q < nr * nq; q += 256) {
-            const int r = (int)__umulhi((uint32_t)q, mq), qd = q - omv::mul_u24(r, nq), dx0 = qd * 4,
-                      dy = bc.need_lo + r;
-            const XTab y = ys[r];
-            const int b0 = (short)(y.coef & 0xffff), b1 = (short)(y.coef >> 16);
-            uint32_t packed = 0;
-            if (quad) {
-                const XQuad X = *reinterpret_cast<const XQuad *>(reinterpret_cast<const char *>(xqs) + omv::mul_u24(qd, 48u));
-                const uint32_t *R0 = prev + omv::mul_u24(y.sx0 - bp.need_lo, sndw),
-                               *R1 = prev + omv::mul_u24(y.sx1 - bp.need_lo, sndw);
-                const uint32_t u0[4] = {R0[X.a[0]], R0[X.a[0] + 1], R0[X.a[1]], R0[X.a[1] + 1]};
-                const uint32_t u1[4] = {R1[X.a[0]], R1[X.a[0] + 1], R1[X.a[1]], R1[X.a[1] + 1]};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int pp = 2 * (j >> 1);
-                    const u16x2 cf = __builtin_bit_cast(u16x2, X.cf[j]);
-                    const int h0 = (int)__builtin_amdgcn_udot2(
-                        __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(u0[pp + 1], u0[pp], X.sel[j])), cf, 0u, false);
-                    const int h1 = (int)__builtin_amdgcn_udot2(
-                        __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(u1[pp + 1], u1[pp], X.sel[j])), cf, 0u, false);
-                    packed |= (uint32_t)vmix(b0, b1, h0, h1) << (8 * j);   // <= 255: the weights sum to <= 2049
-                }
-            } else {
+        uint8_t *out = pyr + (size_t)img * g.pyr_bytes + L.off;
+        if (quad) {
+            const int ns = (nr + kPyrStrip - 1) / kPyrStrip;
+            for (int t = tid; t < ns * nq; t += 256) {
+                const int s = (int)__umulhi((uint32_t)t, mq), qd = t - omv::mul_u24(s, nq), r0 = s * kPyrStrip;
+                const XQuad X = xq[L.xq_off + qd];
+                const int left = L.w - 4 * qd, pitch = L.pitch;
+                int dy = bc.need_lo + r0;
+                uint32_t *c = cur + omv::mul_u24(r0, cndw) + qd;
+                uint8_t *dst = out + (size_t)dy * pitch + 4 * qd;
+                pyr_strip(X, prev, ysq + r0, min(kPyrStrip, nr - r0), [&](uint32_t packed) {
+                    *c = packed;   // the next level's source row (bytes past the width are never read)
+                    if (dy >= bc.own_lo && dy < bc.own_hi) pyr_store(dst, packed, left);
+                    c += cndw, dst += pitch, ++dy;
+                });
+            }
+        } else {
+            for (int q = tid; q < nr * nq; q += 256) {
+                const int r = (int)__umulhi((uint32_t)q, mq), qd = q - omv::mul_u24(r, nq), dx0 = qd * 4,
+                          dy = bc.need_lo + r;
+                const XTab y = ys[r];
+                const int b0 = (short)(y.coef & 0xffff), b1 = (short)(y.coef >> 16);
+                uint32_t packed = 0;
                 const uint8_t *R0 = reinterpret_cast<const uint8_t *>(prev + omv::mul_u24(y.sx0 - bp.need_lo, sndw));
                 const uint8_t *R1 = reinterpret_cast<const uint8_t *>(prev + omv::mul_u24(y.sx1 - bp.need_lo, sndw));
 #pragma unroll
@@ -328,15 +421,9 @@ __global__ void __launch_bounds__(256) pyr_chain_kernel(Geom g, const uint8_t *i
                         packed |= (uint32_t)min(v, 255) << (8 * j);
                     }
                 }
-            }
-            cur[omv::mul_u24(r, cndw) + qd] = packed;   // the next level's source row (bytes past the width are never read)
-            if (dy >= bc.own_lo && dy < bc.own_hi) {
-                uint8_t *dst = pyr + (size_t)img * g.pyr_bytes + L.off + (size_t)dy * L.pitch;
-                if (dx0 + 3 < L.w) {
-                    *reinterpret_cast<uint32_t *>(dst + dx0) = packed;
-                } else {
-                    for (int j = 0; j < 4 && dx0 + j < L.w; ++j) dst[dx0 + j] = (uint8_t)(packed >> (8 * j));
-                }
+                cur[omv::mul_u24(r, cndw) + qd] = packed;   // the next level's source row (bytes past the width are never read)
+                if (dy >= bc.own_lo && dy < bc.own_hi)
+                    pyr_store(out + (size_t)dy * L.pitch + dx0, packed, L.w - dx0);
             }
         }
         __syncthreads();
@@ -1424,7 +1511,8 @@ struct omv_orb {
     size_t pyr_lds[kMaxLevels] = {};   // K1 dynamic LDS per level: x table + the widest row block
     PyrBand *d_bands = nullptr;        // K1 as one launch (pyr_chain_kernel): per (band, level) rows
     int pyr_nb = 0, pyr_buf_dw = 0;    //   bands per image, dwords per LDS ping-pong buffer (0: per-level launches)
-    int pyr_tab_dw = 0, pyr_rows = 0;  //   dwords of the staged x table, the most rows a band needs at a level >= 1
+    int pyr_tab_dw = 0, pyr_rows = 0;  //   dwords of the staged x table (generic levels), the most rows a band needs at a level >= 1
+    int pyr_ydw = 3;                   //   dwords per staged y entry: 3 (XTab), 4 (YRow) when a level takes the quad path
     // host staging for the synchronous path
     uint8_t *d_img1 = nullptr;
     omv_kp *d_kp1 = nullptr;
@@ -1584,9 +1672,9 @@ static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vect
                     }
                     const int base = 4 * X.a[j >> 1], o0 = row[dx].sx0 - base, o1 = row[dx].sx1 - base;
                     const int a0 = (short)(row[dx].coef & 0xffff), a1 = (short)(row[dx].coef >> 16);
-                    if (o0 < 0 || o0 > 7 || o1 < 0 || o1 > 7 || a0 < 0 || a1 < 0) L.use_xq = 0;
+                    if (o0 < 0 || o0 > 7 || o1 < 0 || o1 > 7 || a0 < 0 || a1 < 0 || a0 > 2048 || a1 > 2048) L.use_xq = 0;
                     X.sel[j] = (uint32_t)(o0 & 7) | 0x0c00u | ((uint32_t)(o1 & 7) << 16) | 0x0c000000u;
-                    X.cf[j] = (uint32_t)(a0 & 0xffff) | ((uint32_t)(a1 & 0xffff) << 16);
+                    X.cf[j] = (uint32_t)((16 * a0) & 0xffff) | ((uint32_t)((16 * a1) & 0xffff) << 16);
                 }
                 xq.push_back(X);
             }
@@ -1596,6 +1684,7 @@ static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vect
                 fy -= sy;
                 int b0 = (short)host_round_even((1.f - fy) * 2048.f), b1 = (short)host_round_even(fy * 2048.f);
                 const int r0 = std::min(std::max(sy, 0), sh - 1), r1 = std::min(std::max(sy + 1, 0), sh - 1);
+                if (b0 < 0 || b1 < 0 || b0 > 2048 || b1 > 2048) L.use_xq = 0;   // the quad path's b << 8 operands
                 yt.push_back(XTab{r0, r1, (b0 & 0xffff) | (b1 << 16)});
             }
         }
@@ -1689,15 +1778,29 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
     const size_t n = (size_t)max_images;
     HIP_OK(hipMalloc(&o->d_cells, sizeof(Cell) * cells.size()));
     HIP_OK(hipMemcpy(o->d_cells, cells.data(), sizeof(Cell) * cells.size(), hipMemcpyHostToDevice));
-    for (int l = 1; l < g.nlevels; ++l) {   // K1 LDS: the level's x table + the most source rows a row block reads
+    for (int l = 1; l < g.nlevels; ++l) {   // K1 LDS: the generic path's x table + the most source rows a row block reads
         const LevelGeom &L = g.lv[l];
         int nr = 0;
         for (int dy0 = 0; dy0 < L.h; dy0 += kPyrBlock) {
             const int dy1 = std::min(dy0 + kPyrBlock, L.h);
             nr = std::max(nr, yt[L.ytab_off + dy1 - 1].sx1 - yt[L.ytab_off + dy0].sx0 + 1);
         }
-        o->pyr_lds[l] = sizeof(uint32_t) * (12 * (size_t)((L.w + 3) / 4) + (size_t)nr * (((g.lv[l - 1].w + 15) / 16) * 4) + 4 +
-                                            3 * kPyrBlock);
+        const size_t rows_dw = (size_t)nr * (((g.lv[l - 1].w + 15) / 16) * 4) + 4;
+        o->pyr_lds[l] = sizeof(uint32_t) * (12 * (size_t)((L.w + 3) / 4) + rows_dw + 3 * kPyrBlock);
+        if (L.use_xq) {
+            // An occupancy cap, on purpose.  The quad path no longer stages its table: it needs the rows and
+            // 4 kPyrBlock dwords of y entries.  It still requests the table's share (unused) up to kPyrLdsHold, because
+            // the request is what limits the pyramid's workgroups per CU.  They wait on memory in over half their
+            // cycles; with only `need` requested more of them sit on a CU while fast_cells / describe of the other
+            // two streams run, and the overlapped 5 x 720x540 step is no faster than before the strips, or slower
+            // (8.67-8.77 ms against 8.63-8.70; with the share held 8.50-8.60).  Above kPyrLdsHold the share is
+            // given back: at 1080p the rows alone are 40 KB, and 2 -> 4 workgroups per CU is that shape's whole
+            // isolated gain (4.30 -> 3.1 ms, 4.23 with the share held).  Both A/Bs: DESIGN section 6 "Pyramid
+            // resize: column strips" and profiles/pyr_strip_ab.log.  24 KB lies between the two measured shapes
+            // (22.5 KB at level 1 of 720x540); shapes in between are unmeasured.
+            const size_t need = sizeof(uint32_t) * (rows_dw + 4 * kPyrBlock);
+            o->pyr_lds[l] = std::max(need, std::min(o->pyr_lds[l], kPyrLdsHold));
+        }
         if (o->pyr_lds[l] > 160 * 1024) {   // images wider than ~8000 px
             delete o;
             return OMV_ERR_ARG;
@@ -1735,18 +1838,19 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
             for (int nb = 8; nb <= 128 && L > 1 && !o->pyr_nb; ++nb) {
                 const int worst = plan(nb, bands);
                 if (worst > budget) continue;
-                int tab = 0, rows = 0;
+                int tab = 0, rows = 0, ydw = 3;   // x table of the generic levels; dwords per staged y entry
                 for (int l = 1; l < L; ++l) {
-                    tab = std::max(tab, g.lv[l].use_xq ? 12 * ((g.lv[l].w + 3) / 4) : 3 * g.lv[l].w);
+                    if (g.lv[l].use_xq) ydw = 4;
+                    else tab = std::max(tab, 3 * g.lv[l].w);
                     for (int b = 0; b < nb; ++b) {
                         const PyrBand &pb = bands[(size_t)b * kMaxLevels + l];
                         rows = std::max(rows, pb.need_hi - pb.need_lo);
                     }
                 }
-                o->pyr_nb = nb, o->pyr_buf_dw = worst, o->pyr_tab_dw = (tab + 3) & ~3, o->pyr_rows = rows;
+                o->pyr_nb = nb, o->pyr_buf_dw = worst, o->pyr_tab_dw = (tab + 3) & ~3, o->pyr_rows = rows, o->pyr_ydw = ydw;
                 HIP_OK(hipMalloc(&o->d_bands, sizeof(PyrBand) * bands.size()));
                 HIP_OK(hipMemcpy(o->d_bands, bands.data(), sizeof(PyrBand) * bands.size(), hipMemcpyHostToDevice));
-                const int lds = (int)(sizeof(uint32_t) * (2 * (size_t)worst + 4 + o->pyr_tab_dw + 3 * (size_t)rows));
+                const int lds = (int)(sizeof(uint32_t) * (2 * (size_t)worst + 4 + o->pyr_tab_dw + (size_t)ydw * rows));
                 if (lds > 160 * 1024) {   // no plan: the per-level launches
                     (void)hipFree(o->d_bands);
                     o->d_bands = nullptr, o->pyr_nb = 0;
@@ -1829,7 +1933,7 @@ omv_status omv_orb_extract_batch(omv_orb *o, int n, const uint8_t *images, size_
     // "levels" / "chain" (read at omv_orb_create) picks the path
     const bool chain = o->pyr_mode >= 0 ? o->pyr_mode == 1 : n <= kPyrChainMaxImages;
     if (o->pyr_nb > 0 && chain) {
-        const size_t lds = sizeof(uint32_t) * (2 * (size_t)o->pyr_buf_dw + 4 + o->pyr_tab_dw + 3 * (size_t)o->pyr_rows);
+        const size_t lds = sizeof(uint32_t) * (2 * (size_t)o->pyr_buf_dw + 4 + o->pyr_tab_dw + (size_t)o->pyr_ydw * o->pyr_rows);
         pyr_chain_kernel<<<dim3(o->pyr_nb, n), 256, lds, st>>>(g, images, image_stride, pitch, o->d_pyr, o->d_xt, o->d_yt,
                                                                o->d_xq, o->d_bands, o->pyr_buf_dw, o->pyr_tab_dw);
     } else {
