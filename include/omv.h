@@ -1070,6 +1070,36 @@ omv_status omv_selftest_inertial_info9(int par, int batch, const float *C, doubl
  * (entry (r, c) at 16 r + (c ^ r)), only the lower triangle read -> Dinv [batch][256], the full inverse in the same
  * layout; bad [batch]: the routine's flag (a zero or non-finite pivot). */
 omv_status omv_selftest_inv16(int batch, const double *D, double *Dinv, int32_t *bad, void *stream);
+
+/* The float layer under the bit-exact kernels (csrc/omv_math.h, rcp_nr, the plain `/` and `a * b + c` of the build
+ * flags), elementwise over n elements of device memory, one thread per element, on `stream` (not synchronised).
+ * float unless noted; [n] unless noted:
+ *   SINCOSF a -> out [n][2] (sin, cos)      ATANF, TANF, SQRTF a -> out      ATAN2F, FAST_ATAN2_DEG (a = y, b = x) -> out
+ *   ROUND_EVEN a -> int32                   DIVF a / b                       MULADD_F32 a * b + c (plain operators)
+ *   MULADD_F64 the same on doubles          RCP_NR double a -> double
+ *   KB8_PROJECT / PINHOLE_PROJECT     a = X [n][3], b = k[8] -> uv [n][2]
+ *   KB8_UNPROJECT / PINHOLE_UNPROJECT a = px [n][2], b = k[8] -> ray [n][3]
+ *   PREDICT_SCALE a = ratio, b[0] = log scale factor -> int32 (int)ceil(log((double)a) / (double)b[0])
+ * An unknown fn, n < 0, or a NULL among the pointers fn reads with n > 0: OMV_ERR_ARG before any launch; n == 0:
+ * OMV_OK. */
+#define OMV_MATH_SINCOSF 0
+#define OMV_MATH_ATANF 1
+#define OMV_MATH_ATAN2F 2
+#define OMV_MATH_TANF 3
+#define OMV_MATH_SQRTF 4
+#define OMV_MATH_FAST_ATAN2_DEG 5
+#define OMV_MATH_ROUND_EVEN 6
+#define OMV_MATH_DIVF 7
+#define OMV_MATH_MULADD_F32 8
+#define OMV_MATH_MULADD_F64 9
+#define OMV_MATH_RCP_NR 10
+#define OMV_MATH_KB8_PROJECT 11
+#define OMV_MATH_KB8_UNPROJECT 12
+#define OMV_MATH_PINHOLE_PROJECT 13
+#define OMV_MATH_PINHOLE_UNPROJECT 14
+#define OMV_MATH_PREDICT_SCALE 15
+omv_status omv_selftest_math(int fn, int64_t n, const void *a, const void *b, const void *c, void *out, void *stream);
+
 /* One reduced-system solve on a handle after omv_lba_set_problem, at the current state: errors, build, assemble and
  * the block LDL^T once, through the optimiser's own launches, with the damping `lambda` (> 0: the padding pivots are
  * lambda) and the robust kernels of the problem (`o` is validated only: no option changes them).  Host outputs, n =

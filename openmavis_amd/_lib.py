@@ -329,6 +329,7 @@ SIGNATURES = {
     "omv_selftest_pinv15": (_I, [_I, _VP, _VP, _VP, _VP]),
     "omv_selftest_inertial_info9": (_I, [_I, _I, _VP, _VP, _VP, _VP]),
     "omv_selftest_inv16": (_I, [_I, _VP, _VP, _VP, _VP]),
+    "omv_selftest_math": (_I, [_I, ctypes.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "omv_lba_debug_solve": (_I, [_VP, ctypes.POINTER(LbaOpts), ctypes.c_double, _VP, _VP, _VP, ctypes.POINTER(_I),
                                  _VP, _I]),
     "omv_sim3_solver_create": (_I, [_I, _I, _I, ctypes.POINTER(_VP)]),

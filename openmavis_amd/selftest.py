@@ -1,6 +1,7 @@
-"""Bindings of the library's test hooks for the device linear algebra (omv_selftest_* in include/omv.h): the pose
+"""Bindings of the library's test hooks (omv_selftest_* in include/omv.h).  The device linear algebra: the pose
 kernels' pivoted LDL^T solves, pinv15_wave, inertial_info9_wave and the reduced-system solver's inv16, each on a batch
-of host arrays (one workgroup per problem on the device).  There is no CPU fallback."""
+of host arrays (one workgroup per problem on the device).  The float layer underneath: math(), the functions of
+csrc/omv_math.h elementwise.  There is no CPU fallback."""
 import ctypes
 
 import numpy as np
@@ -87,3 +88,50 @@ def inv16(D):
     _lib.check(lib.omv_selftest_inv16(B, _lib.ptr(dD), _lib.ptr(out), _lib.ptr(bad), _stream()), "omv_selftest_inv16")
     torch.cuda.synchronize()
     return out.cpu().numpy()[:, SW16.ravel()].reshape(B, 16, 16), bad.cpu().numpy()
+
+
+# omv_selftest_math: the OMV_MATH_* codes of include/omv.h
+(SINCOSF, ATANF, ATAN2F, TANF, SQRTF, FAST_ATAN2_DEG, ROUND_EVEN, DIVF, MULADD_F32, MULADD_F64, RCP_NR, KB8_PROJECT,
+ KB8_UNPROJECT, PINHOLE_PROJECT, PINHOLE_UNPROJECT, PREDICT_SCALE) = range(16)
+MATH_NAMES = ("SINCOSF", "ATANF", "ATAN2F", "TANF", "SQRTF", "FAST_ATAN2_DEG", "ROUND_EVEN", "DIVF", "MULADD_F32",
+              "MULADD_F64", "RCP_NR", "KB8_PROJECT", "KB8_UNPROJECT", "PINHOLE_PROJECT", "PINHOLE_UNPROJECT",
+              "PREDICT_SCALE")
+# per fn: input dtype, scalars per element of a, (dtype, scalars per element) of out
+MATH_IO = {SINCOSF: (np.float32, 1, np.float32, 2), ATANF: (np.float32, 1, np.float32, 1),
+           ATAN2F: (np.float32, 1, np.float32, 1), TANF: (np.float32, 1, np.float32, 1),
+           SQRTF: (np.float32, 1, np.float32, 1), FAST_ATAN2_DEG: (np.float32, 1, np.float32, 1),
+           ROUND_EVEN: (np.float32, 1, np.int32, 1), DIVF: (np.float32, 1, np.float32, 1),
+           MULADD_F32: (np.float32, 1, np.float32, 1), MULADD_F64: (np.float64, 1, np.float64, 1),
+           RCP_NR: (np.float64, 1, np.float64, 1), KB8_PROJECT: (np.float32, 3, np.float32, 2),
+           KB8_UNPROJECT: (np.float32, 2, np.float32, 3), PINHOLE_PROJECT: (np.float32, 3, np.float32, 2),
+           PINHOLE_UNPROJECT: (np.float32, 2, np.float32, 3), PREDICT_SCALE: (np.float32, 1, np.int32, 1)}
+
+
+def math_args(fn, a, b, c):
+    """The arrays of one math() / oracle.math_map() call in the hook's layout: (n, a, b, c, an empty out).  b of the
+    camera codes is k[8], of PREDICT_SCALE one float; every other b / c has a's length."""
+    tin, wa, tout, wo = MATH_IO[fn]
+    a = np.ascontiguousarray(a, tin)
+    n = a.size // wa
+    assert a.size == n * wa
+    if b is not None:
+        b = np.ascontiguousarray(b, tin)
+        assert b.size == (8 if wa > 1 else 1 if fn == PREDICT_SCALE else n)
+    if c is not None:
+        c = np.ascontiguousarray(c, tin)
+        assert c.size == n
+    return n, a, b, c, np.empty((n, wo) if wo > 1 else (n,), tout)
+
+
+def math(fn, a, b=None, c=None):
+    """omv_selftest_math on host arrays -> a numpy array ([n], or [n][2] / [n][3] for the codes with several outputs
+    per element; SINCOSF: column 0 sin, column 1 cos).  The output is pre-filled with 0xff bytes."""
+    import torch
+    n, a, b, c, out = math_args(fn, a, b, c)
+    lib = _lib.load()
+    da, db, dc = (None if x is None else torch.from_numpy(x).cuda() for x in (a, b, c))
+    dout = torch.full((max(out.nbytes, 1),), 0xff, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.omv_selftest_math(int(fn), n, _lib.ptr(da), _lib.ptr(db), _lib.ptr(dc), _lib.ptr(dout), _stream()),
+               "omv_selftest_math")
+    torch.cuda.synchronize()
+    return dout[:out.nbytes].cpu().numpy().view(out.dtype).reshape(out.shape)

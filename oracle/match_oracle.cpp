@@ -425,6 +425,10 @@ static void pinhole_project_f(const float *k, const float *X, float &u, float &v
     v = k[1] * X[1] / X[2] + k[3];
 }
 
+// Parity hooks for the camera projections (oracle_libm_map, math_host.cpp).
+void oracle_kb8_project(const float *cam, const float *X, float *uv) { kb8_project_f(cam, X, uv[0], uv[1]); }
+void oracle_pinhole_project(const float *cam, const float *X, float *uv) { pinhole_project_f(cam, X, uv[0], uv[1]); }
+
 int oracle_frustum(const RigF *rig, const PoseF *pose, const float *pos, const float *normal, const float *min_d,
                    const float *max_d, int M, float cos_limit, float *proj_x, float *proj_y, float *view_cos,
                    int32_t *level, uint8_t *in_view, float *track_depth) {

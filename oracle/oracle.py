@@ -489,6 +489,29 @@ def kb8_unproject(cam, x, y):
     return ray
 
 
+def _math(entry, fn, a, b, c):
+    from openmavis_amd.selftest import math_args   # the hook's array layout, one definition
+    n, a, b, c, out = math_args(fn, a, b, c)
+    f = getattr(lib(), entry)
+    f.restype = ctypes.c_int
+    st = f(ctypes.c_int(int(fn)), ctypes.c_int64(n), _p(a), _p(b), _p(c), _p(out))
+    if st != 0:
+        raise ValueError(f"{entry}: fn {fn} not available or bad arguments")
+    return out
+
+
+def math_map(fn, a, b=None, c=None):
+    """The product's csrc/omv_math.h compiled for the host, elementwise: same codes, arrays and result layout as
+    openmavis_amd.selftest.math (RCP_NR: the IEEE quotient)."""
+    return _math("oracle_math_map", fn, a, b, c)
+
+
+def libm_map(fn, a, b=None, c=None):
+    """The same codes through the C library and the oracle's own restatements (no copy of the header's text); DIVF,
+    MULADD_* and RCP_NR have none and raise."""
+    return _math("oracle_libm_map", fn, a, b, c)
+
+
 def jacobi_svd4_v(A):
     A = np.ascontiguousarray(A, np.float32).reshape(4, 4)
     V = np.zeros((4, 4), np.float32)

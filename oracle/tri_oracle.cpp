@@ -440,6 +440,7 @@ void oracle_tri_point(const float *cam1, const float *cam2, const omv_kp *kp1, c
 
 // Parity hooks for the camera-model pieces.
 void oracle_kb8_unproject(const float *cam, float x, float y, float *ray) { kb8_unproject_f(cam, x, y, ray); }
+void oracle_pinhole_unproject(const float *cam, float x, float y, float *ray) { pinhole_unproject_f(cam, x, y, ray); }
 void oracle_jacobi_svd4_v(const float *A, float *V) { jacobi_svd4_v(A, V); }
 void oracle_eigen_inverse3(const float *m, float *r) { eigen_inverse3(m, r); }
 int oracle_pinhole_epipolar(const float *k1, const float *k2, const omv_kp *kp1, const omv_kp *kp2, const float *R12,

@@ -1,0 +1,467 @@
+"""Input sets of the float-layer tests (tests/test_math_header_cpu.py, tests/test_math_device_gpu.py): fixed seeds, one
+definition for the CPU and the GPU side.  Every generator returns a list of (name, a, b, c) calls, each of at most
+2^24 elements; the arrays are cached and must be treated as read-only.
+
+The argument sweeps of sincosf / tanf / atanf over |y| < 120 take every 97th float bit pattern of either sign (11.6 M
+patterns per sign, one call per sign), which is as dense on [0, 2 pi] as the sweep these tests replace."""
+import functools
+from fractions import Fraction
+
+import numpy as np
+
+from openmavis_amd import selftest as st
+from openmavis_amd.synth_ba_const import CAMS
+
+F32, U32 = np.float32, np.uint32
+SIGN = U32(0x80000000)
+B120 = 0x42f00000            # bits of 120.0f
+BINF = 0x7f800000
+# branch thresholds of the restatements, as float bit patterns
+THRESH_SINCOS = [0x39800000, 0x3f490fdb]                                            # 2^-12, pi/4 (top12 compares)
+THRESH_ATAN = [0x31000000, 0x3ee00000, 0x3f300000, 0x3f980000, 0x401c0000, 0x4c000000]
+THRESH_TAN = [0x39000000, 0x3f2ca140, 0x3f490fda]
+SPECIAL_BITS = [0x00000000, 0x00000001, 0x007fffff, 0x00800000]                     # 0, denormal min / max, FLT_MIN
+
+
+def f32(bits):
+    return np.ascontiguousarray(bits, U32).view(F32)
+
+
+def bits(x):
+    return np.ascontiguousarray(x, F32).view(U32)
+
+
+def both_signs(b):
+    b = np.asarray(b, U32)
+    return np.concatenate([b, b | SIGN])
+
+
+def around(centre_bits, ulps):
+    """Every bit pattern within +-ulps of each centre (positive patterns, clipped at 0)."""
+    c = np.asarray(centre_bits, np.int64)[:, None] + np.arange(-ulps, ulps + 1, dtype=np.int64)[None, :]
+    return np.unique(c[(c >= 0) & (c <= BINF)]).astype(U32)
+
+
+def same_bits(x, y):
+    """Elementwise: equal bit patterns, or both NaN (a NaN's payload and sign are the hardware's)."""
+    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
+    assert x.dtype == y.dtype and x.shape == y.shape
+    if x.dtype.kind != "f":
+        return x == y
+    u = {4: np.uint32, 8: np.uint64}[x.dtype.itemsize]
+    return (x.view(u) == y.view(u)) | (np.isnan(x) & np.isnan(y))
+
+
+def mismatches(x, y):
+    """Indices (first axis) at which x and y are not same_bits."""
+    ok = same_bits(x, y)
+    return np.flatnonzero(~ok.reshape(len(ok), -1).all(axis=1))
+
+
+@functools.lru_cache(None)
+def trig_edges():
+    """+-256 ulps of every branch threshold of sincosf / atanf / tanf and of n pi/2, n pi/4 (n = 1..76), +-0, the
+    denormal extremes and +-FLT_MIN; |y| < 120."""
+    n = np.arange(1, 77, dtype=np.float64)
+    multiples = bits(np.concatenate([n * (np.pi / 2), n * (np.pi / 4)]).astype(F32))
+    centres = np.concatenate([np.array(THRESH_SINCOS + THRESH_ATAN + THRESH_TAN, np.int64), multiples.astype(np.int64)])
+    b = np.unique(np.concatenate([around(centres, 256), np.array(SPECIAL_BITS, U32)]))
+    return f32(both_signs(b[b < B120]))
+
+
+@functools.lru_cache(None)
+def trig():
+    """sincosf, tanf (and atanf): |y| < 120."""
+    sweep = np.arange(0, B120, 97, dtype=np.int64).astype(U32)
+    assert sweep[-1] > bits(F32(2 * np.pi))[()] and len(sweep) <= 1 << 24
+    return [("sweep+", f32(sweep), None, None), ("sweep-", f32(sweep | SIGN), None, None),
+            ("edges", trig_edges(), None, None)]
+
+
+@functools.lru_cache(None)
+def atanf():
+    full = np.arange(0, BINF, 1021, dtype=np.int64).astype(U32)
+    special = np.array([BINF, 0x7fc00000, 0x7f800001, 0x7fffffff], U32)   # inf, quiet / signalling / all-ones NaN
+    wide = np.concatenate([both_signs(full), both_signs(special), both_signs(around([0x4c000000, BINF - 300], 256))])
+    return trig() + [("full range", f32(wide), None, None)]
+
+
+ATAN2_SPECIAL = [0.0, 1.0, np.inf, 1e-45, 1.17549435e-38, 3.4028234664e38, 1e30, 1e-30]
+
+
+@functools.lru_cache(None)
+def atan2():
+    """atan2f and fast_atan2_deg: (name, y, x)."""
+    rng = np.random.default_rng(20240201)
+    ry, rx = (f32(rng.integers(0, 1 << 32, 1 << 23, dtype=np.uint64).astype(U32)) for _ in range(2))
+    # near the diagonal: x = y (1 +- k 2^-23), the ax >= ay switch, over every normal exponent and all four quadrants
+    n = 1 << 22
+    y = f32((rng.integers(1, 254, n, dtype=np.uint64) << 23 | rng.integers(0, 1 << 23, n, dtype=np.uint64)).astype(U32))
+    k = rng.integers(-8, 9, n).astype(np.float64)
+    x = (y.astype(np.float64) * (1.0 + k * 2.0 ** -23)).astype(F32)
+    y = f32(bits(y) | (rng.integers(0, 2, n, dtype=np.uint64).astype(U32) << 31))
+    x = f32(bits(x) | (rng.integers(0, 2, n, dtype=np.uint64).astype(U32) << 31))
+    v = np.array(ATAN2_SPECIAL, F32)
+    v = np.concatenate([v, -v, np.array([np.nan], F32)])
+    assert v[3] == f32([1])[0] and len(v) == 17
+    sy, sx = (g.ravel().copy() for g in np.meshgrid(v, v, indexing="ij"))
+    return [("random bits", ry, rx, None), ("near diagonal", y, x, None), ("special x special", sy, sx, None)]
+
+
+@functools.lru_cache(None)
+def fast_atan2():
+    """fast_atan2_deg additionally on integer moments (m01, m10) in [-2^20, 2^20], as IC_Angle produces them."""
+    rng = np.random.default_rng(20240202)
+    m01, m10 = (rng.integers(-(1 << 20), (1 << 20) + 1, 1 << 21).astype(F32) for _ in range(2))
+    g = np.arange(-40, 41).astype(F32)
+    gy, gx = (a.ravel().copy() for a in np.meshgrid(g, g, indexing="ij"))
+    e = np.array([-(1 << 20), -1, 0, 1, 1 << 20], F32)
+    ey, ex = (a.ravel().copy() for a in np.meshgrid(e, e, indexing="ij"))
+    return atan2() + [("integer moments", np.concatenate([m01, gy, ey]), np.concatenate([m10, gx, ex]), None)]
+
+
+@functools.lru_cache(None)
+def sqrtf():
+    """Every 131st non-negative float (denormals included), +inf, and the few inputs with special results."""
+    sweep = np.arange(0, BINF + 1, 131, dtype=np.int64).astype(U32)
+    extra = np.array(SPECIAL_BITS + [BINF, 0x7f7fffff, 0x80000000, 0xbf800000, 0x80000001, 0x7fc00000], U32)
+    squares = (np.arange(1, 4097, dtype=np.float64) ** 2).astype(F32)
+    return [("sweep", f32(np.concatenate([sweep, extra, around(bits(squares), 1)])), None, None)]
+
+
+@functools.lru_cache(None)
+def divf():
+    """Random bit patterns; a denormal operand on either side; denormal quotients; exact ties.  A quotient of two floats
+    can lie exactly half-way between two floats only where the result is denormal: (2 j + 1) 2^-150, reached as
+    d (2 j + 1) 2^(s - 150) / (d 2^s) with d = 1, 3."""
+    rng = np.random.default_rng(20240203)
+    n = 1 << 22
+    ra, rb = (f32(rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(U32)) for _ in range(2))
+    m = 1 << 20
+
+    def normal(lo_exp, hi_exp, cnt):   # random mantissa, biased exponent in [lo_exp, hi_exp), random sign
+        return f32((rng.integers(0, 2, cnt, dtype=np.uint64) << 31 | rng.integers(lo_exp, hi_exp, cnt, dtype=np.uint64) << 23
+                    | rng.integers(0, 1 << 23, cnt, dtype=np.uint64)).astype(U32))
+    den = f32((rng.integers(0, 2, m, dtype=np.uint64) << 31 | rng.integers(1, 1 << 23, m, dtype=np.uint64)).astype(U32))
+    mid = normal(100, 150, m)
+    # denormal quotient: the divisor's exponent 126..152 above the dividend's
+    num = normal(1, 100, m)
+    dexp = rng.integers(1, 27, m, dtype=np.uint64)
+    div = f32(((bits(num) >> 23 & U32(0xff)).astype(np.uint64) + 126 + dexp << 23
+               | rng.integers(0, 1 << 23, m, dtype=np.uint64)).astype(U32))
+    j = rng.integers(0, 1 << 21, m).astype(np.float64)
+    s = rng.integers(24, 100, m).astype(np.float64)
+    d = np.where(rng.integers(0, 2, m) == 1, 3.0, 1.0)
+    tie_a = (d * (2 * j + 1) * 2.0 ** (s - 150)).astype(F32)
+    tie_b = (d * 2.0 ** s).astype(F32)
+    assert np.array_equal(tie_a.astype(np.float64) / tie_b.astype(np.float64), (2 * j + 1) * 2.0 ** -150)
+    a = np.concatenate([den, mid, num, tie_a, -tie_a])
+    b = np.concatenate([mid, den, div, tie_b, tie_b])
+    return [("random bits", ra, rb, None), ("denormals and ties", a, b, None)]
+
+
+@functools.lru_cache(None)
+def round_even():
+    rng = np.random.default_rng(20240204)
+    half = np.arange(-4096, 4097, dtype=np.float64).astype(F32) + F32(0.5)
+    nb = np.concatenate([half, np.nextafter(half, F32(np.inf)), np.nextafter(half, F32(-np.inf))])
+    rnd = (rng.random(1 << 20) * 2.0 ** 24 - 2.0 ** 23).astype(F32)
+    rnd = rnd[np.abs(rnd) < 2.0 ** 23]
+    small = f32(both_signs(np.array(SPECIAL_BITS, U32)))
+    return [("halves and random", np.concatenate([nb, small, rnd]), None, None)]
+
+
+@functools.lru_cache(None)
+def muladd_f32():
+    """Triples (a, b, c) on which the fused and the unfused a * b + c differ, and the unfused value.  Selected in
+    float64, where the product of two floats (48 bits) is exact, and so are both sums: c is drawn within 2 binades of
+    the product (or is its negated rounding, the cancellation case), so each sum spans at most 52 bits."""
+    rng = np.random.default_rng(20240205)
+    n = 1 << 20
+    a, b = ((rng.random(n) + 1.0) * 2.0 ** rng.integers(-20, 21, n) * rng.choice([-1.0, 1.0], n) for _ in range(2))
+    a, b = a.astype(F32), b.astype(F32)
+    p = a.astype(np.float64) * b.astype(np.float64)
+    pr = p.astype(F32)
+    c = ((rng.random(n) + 1.0) * 2.0 ** rng.integers(-2, 3, n) * rng.choice([-1.0, 1.0], n) * np.abs(p)).astype(F32)
+    c[: n // 4] = -pr[: n // 4]
+    fused = (p + c.astype(np.float64)).astype(F32)
+    unfused = (pr.astype(np.float64) + c.astype(np.float64)).astype(F32)
+    sel = bits(fused) != bits(unfused)
+    assert sel.sum() >= 100000
+    return a[sel], b[sel], c[sel], unfused[sel], fused[sel]
+
+
+@functools.lru_cache(None)
+def muladd_f64():
+    """The same for doubles, selected with fractions.Fraction: fused = the exact a b + c rounded once (float(Fraction)
+    rounds correctly), unfused = Python's own a * b + c (two IEEE roundings).  Half of the candidates cancel the
+    rounded product (c = -(a * b))."""
+    rng = np.random.default_rng(20240206)
+    n = 180000
+    a, b = ((rng.random(n) + 1.0) * 2.0 ** rng.integers(-30, 31, n) * rng.choice([-1.0, 1.0], n) for _ in range(2))
+    c = (rng.random(n) + 1.0) * 2.0 ** rng.integers(-2, 3, n) * rng.choice([-1.0, 1.0], n) * np.abs(a * b)
+    c[: n // 2] = -(a * b)[: n // 2]
+    keep, un, fu = [], [], []
+    for i, (x, y, z) in enumerate(zip(a.tolist(), b.tolist(), c.tolist())):
+        f = float(Fraction(x) * Fraction(y) + Fraction(z))
+        u = x * y + z
+        if f != u:
+            keep.append(i), un.append(u), fu.append(f)
+    assert len(keep) >= 100000, len(keep)
+    keep = np.array(keep)
+    return a[keep], b[keep], c[keep], np.array(un), np.array(fu)
+
+
+@functools.lru_cache(None)
+def rcp_nr():
+    """2^22 doubles with a normal reciprocal: random mantissas at exponents -1000..1000, and the mantissas 1, 1 + eps,
+    2 - eps at every one of those exponents; both signs."""
+    rng = np.random.default_rng(20240207)
+    e = np.arange(-1000, 1001)
+    edge = np.concatenate([np.ldexp(m, e) for m in (1.0, 1.0 + 2.0 ** -52, 2.0 - 2.0 ** -52)])
+    n = (1 << 22) - 2 * len(edge)
+    rnd = np.ldexp(1.0 + rng.integers(0, 1 << 52, n).astype(np.float64) * 2.0 ** -52, rng.integers(-1000, 1001, n))
+    rnd *= rng.choice([-1.0, 1.0], n)
+    x = np.concatenate([edge, -edge, rnd])
+    assert len(x) == 1 << 22
+    return [("all", x, None, None)]
+
+
+W, H = 720, 540
+CALIBS = [("hilti cam%d" % (i + 1), np.array(k, F32)) for i, k in enumerate(CAMS)] + \
+         [("no distortion", np.array(CAMS[0][:4] + [0.0] * 4, F32))]
+
+
+@functools.lru_cache(None)
+def project_points():
+    """Points for kb8_project_f / pinhole_project_f: directions from the axis to behind the camera (theta up to pi),
+    |X| from 1e-3 to 1e4, on the axis with both zero signs, and x or y exactly 0."""
+    rng = np.random.default_rng(20240208)
+    n = 1 << 17
+    theta = rng.random(n) * np.pi
+    theta[: n // 2] = rng.random(n // 2) * 1.2          # half of them inside the field of view
+    psi = rng.random(n) * 2 * np.pi
+    rad = 10.0 ** (rng.random(n) * 7 - 3)
+    X = (rad[:, None] * np.stack([np.sin(theta) * np.cos(psi), np.sin(theta) * np.sin(psi), np.cos(theta)], 1)).astype(F32)
+    # a coordinate exactly 0 (either sign): four points each.  There psi is +-pi/2 or pi as a float, sin / cos (psi) is
+    # within 1e-15 of +-1, and k r sin(psi) + c is the sum of two floats to within a double ulp: it lands on the
+    # midpoint of two floats about once in 16 points, where any double evaluation, glibc's included, rounds the tie
+    # and not the exact value.  A handful exercises the branch; thousands would only count such midpoints.
+    X[0:4, 0] = 0.0
+    X[4:8, 0] = -0.0
+    X[8:12, 1] = 0.0
+    X[12:16, 1] = -0.0
+    z = (10.0 ** (rng.random(64) * 7 - 3)).astype(F32)
+    axis = np.concatenate([np.stack([np.full(64, sx, F32), np.full(64, sy, F32), sz * z], 1)
+                           for sx in (0.0, -0.0) for sy in (0.0, -0.0) for sz in (1.0, -1.0)])
+    return np.ascontiguousarray(np.concatenate([X, axis]), F32)
+
+
+def newton_steps(k, px):
+    """How many Newton steps kb8_unproject_f takes per pixel (0: the scale = 1 branch), from a float32 restatement
+    that is used to describe the input set only, never as a reference.  Also returns the clamped flag."""
+    k = np.asarray(k, F32)
+    pwx, pwy = (px[:, 0] - k[2]) / k[0], (px[:, 1] - k[3]) / k[1]
+    td = np.sqrt((pwx * pwx + pwy * pwy).astype(np.float64)).astype(F32)
+    clamped = td > F32(np.pi / 2)
+    td = np.minimum(td, F32(np.pi / 2))
+    th, steps, live = td.copy(), np.zeros(len(td), int), td.astype(np.float64) > 1e-8
+    for _ in range(10):
+        t2 = th * th
+        t4 = t2 * t2
+        t6, t8 = t4 * t2, t4 * t4
+        a, b, c, d = k[4] * t2, k[5] * t4, k[6] * t6, k[7] * t8
+        fix = (th * (1 + a + b + c + d) - td) / (1 + 3 * a + 5 * b + 7 * c + 9 * d)
+        th = np.where(live, th - fix, th)
+        steps += live
+        live = live & ~(np.abs(fix) < F32(1e-6))
+    return steps, clamped
+
+
+@functools.lru_cache(None)
+def unproject_pixels(ci):
+    """Pixels for kb8_unproject_f / pinhole_unproject_f with calibration CALIBS[ci]: a grid over the image plus a 50 %
+    margin, the principal point itself (theta_d = 0: the scale = 1 branch) and its neighbours, rings of radius around
+    and beyond fx pi / 2 (the clamp).  Where all 10 Newton steps are needed is a property of the calibration; the test
+    counts them with newton_steps()."""
+    k = CALIBS[ci][1].astype(np.float64)
+    rng = np.random.default_rng(20240209 + ci)
+    gx, gy = np.meshgrid(np.arange(-W / 2, 1.5 * W + 1, 3.0), np.arange(-H / 2, 1.5 * H + 1, 3.0))
+    grid = np.stack([gx.ravel(), gy.ravel()], 1) + rng.random((gx.size, 2))
+    grid[::7] = np.round(grid[::7])                      # keypoint coordinates are often integers at level 0
+    pp = np.array([[k[2], k[3]]]) + np.array([[0, 0], [1e-5, 0], [0, -1e-5], [1e-3, 1e-3], [-0.5, 0.25]])
+    ang = rng.random(4096) * 2 * np.pi
+    r = k[0] * (np.pi / 2) * np.concatenate([rng.random(2048) * 0.1 + 0.95, 10.0 ** (rng.random(2048) * 2)])
+    ring = np.stack([k[2] + r * np.cos(ang), k[3] + r * np.sin(ang)], 1)
+    return np.ascontiguousarray(np.concatenate([grid, pp, ring]), F32)
+
+
+LSF = np.array([np.log(1.2)], F32)   # mfLogScaleFactor = (float)log(1.2)
+
+
+@functools.lru_cache(None)
+def predict_scale():
+    """Ratios within +-4096 ulps of float(1.2^k), k = -3..12 (where the ceil flips), and 2^20 random ratios in
+    [0.3, 10]."""
+    rng = np.random.default_rng(20240210)
+    centres = bits((1.2 ** np.arange(-3, 13, dtype=np.float64)).astype(F32))
+    rnd = (0.3 + rng.random(1 << 20) * 9.7).astype(F32)
+    return [("all", np.concatenate([f32(around(centres, 4096)), rnd]), LSF, None)]
+
+
+# fn -> the calls of its input set, for the functions with plain [n] arguments
+SETS = {st.SINCOSF: trig, st.TANF: trig, st.ATANF: atanf, st.ATAN2F: atan2, st.FAST_ATAN2_DEG: fast_atan2,
+        st.SQRTF: sqrtf, st.DIVF: divf, st.ROUND_EVEN: round_even, st.RCP_NR: rcp_nr, st.PREDICT_SCALE: predict_scale}
+
+
+def camera_sets(fn):
+    """The calls of a camera code: one per calibration (b = k[8])."""
+    if fn in (st.KB8_PROJECT, st.PINHOLE_PROJECT):
+        return [(name, project_points(), k, None) for name, k in CALIBS]
+    return [(name, unproject_pixels(ci), k, None) for ci, (name, k) in enumerate(CALIBS)]
+
+
+# ---- the two functions that call a double libm function (cos / sin in kb8_project_f, log in PredictScale) ----
+# Device and host libraries may round a double cos / sin / log differently in the last place.  That can change the
+# float (or the integer) only when the exact value of the written expression sits on a rounding boundary; the rule
+# below accepts exactly that and nothing else.
+
+def kb8_project_operands(k, X):
+    """The double operands of kb8_project_f's last line for each point: (k0 r, k1 r, psi, k2, k3) with r and psi from
+    the float chain (atan2f / sqrtf through the host header, the polynomial in numpy float32, left to right)."""
+    import oracle
+    k, X = np.asarray(k, F32), np.asarray(X, F32)
+    x2y2 = X[:, 0] * X[:, 0] + X[:, 1] * X[:, 1]
+    theta = oracle.math_map(st.ATAN2F, oracle.math_map(st.SQRTF, x2y2), X[:, 2].copy())
+    psi = oracle.math_map(st.ATAN2F, X[:, 1].copy(), X[:, 0].copy())
+    t2 = theta * theta
+    t3 = theta * t2
+    t5 = t3 * t2
+    t7 = t5 * t2
+    t9 = t7 * t2
+    r = theta + k[4] * t3 + k[5] * t5 + k[6] * t7 + k[7] * t9
+    return (k[0] * r).astype(np.float64), (k[1] * r).astype(np.float64), psi.astype(np.float64), float(k[2]), float(k[3])
+
+
+def _ulp64(v):
+    import mpmath
+    return mpmath.ldexp(1, int(mpmath.floor(mpmath.log(abs(v), 2))) - 52) if v != 0 else mpmath.mpf(2) ** -1074
+
+
+def float_tie_ok(value, got):
+    """value: the 50-digit value of the expression; got: a float32 result.  True when `got` is the correct rounding;
+    "tie" when value lies within 4 double ulps of the boundary between the two floats around it and got is one of
+    them; False otherwise."""
+    import mpmath
+    near = F32(float(value))                      # some float next to value (double rounding cannot move it further)
+    cands = sorted({float(near), float(np.nextafter(near, F32(-np.inf))), float(np.nextafter(near, F32(np.inf)))})
+    lo = max(c for c in cands if mpmath.mpf(c) <= value)
+    hi = min(c for c in cands if mpmath.mpf(c) >= value)
+    if lo == hi:
+        return float(got) == lo
+    mid = (mpmath.mpf(lo) + mpmath.mpf(hi)) / 2
+    right = lo if value < mid else hi if value > mid else (lo if (bits(F32(lo))[()] & 1) == 0 else hi)
+    if float(got) == right:
+        return True
+    return "tie" if abs(value - mid) <= 4 * _ulp64(value) and float(got) in (lo, hi) else False
+
+
+def ceil_tie_ok(value, got):
+    """The same for (int)ceil(value): "tie" when value is within 4 double ulps of an integer n and got is n or n + 1."""
+    import mpmath
+    if int(got) == int(mpmath.ceil(value)):
+        return True
+    n = int(mpmath.nint(value))
+    return "tie" if abs(value - n) <= 4 * _ulp64(value) and int(got) in (n, n + 1) else False
+
+
+def kb8_project_exact(kr, psi, k2, which):
+    import mpmath
+    f = mpmath.cos if which == 0 else mpmath.sin
+    return mpmath.mpf(kr) * f(mpmath.mpf(psi)) + mpmath.mpf(k2)
+
+
+def predict_scale_exact(ratio, lsf):
+    import mpmath
+    return mpmath.log(mpmath.mpf(float(ratio))) / mpmath.mpf(float(lsf))
+
+
+def judge_kb8_project(k, X, got, idx):
+    """Apply the rule to the points `idx` of one KB8_PROJECT call: (number of ties, list of failures)."""
+    import mpmath
+    ties, bad = 0, []
+    kr0, kr1, psi, k2, k3 = kb8_project_operands(k, X[idx])
+    with mpmath.workdps(50):
+        for j, i in enumerate(idx):
+            for which, kr, kk in ((0, kr0[j], k2), (1, kr1[j], k3)):
+                g = got[i, which]
+                v = kb8_project_exact(kr, psi[j], kk, which)
+                if not (mpmath.isfinite(v) and np.isfinite(g)):
+                    ok = bool(np.isnan(g)) == bool(mpmath.isnan(v))
+                else:
+                    ok = float_tie_ok(v, g)
+                if ok == "tie":
+                    ties += 1
+                    print(f"kb8_project tie: X {X[i]} component {which} exact {mpmath.nstr(v, 25)} got {g!r}")
+                elif not ok:
+                    bad.append((int(i), which, float(g), mpmath.nstr(v, 25)))
+    return ties, bad
+
+
+def judge_predict_scale(ratio, lsf, got, idx):
+    import mpmath
+    ties, bad = 0, []
+    with mpmath.workdps(50):
+        for i in idx:
+            v = predict_scale_exact(ratio[i], lsf)
+            ok = ceil_tie_ok(v, got[i])
+            if ok == "tie":
+                ties += 1
+                print(f"predict_scale tie: ratio {ratio[i]!r} exact {mpmath.nstr(v, 25)} got {got[i]}")
+            elif not ok:
+                bad.append((int(i), float(ratio[i]), int(got[i]), mpmath.nstr(v, 25)))
+    return ties, bad
+
+
+# ---- known answers of this project's libm (tests/golden/libm_kat.npz, written by tools/make_golden.py) ----
+KAT_F32, KAT_F64 = 2000, 900
+
+
+@functools.lru_cache(None)
+def kat_inputs():
+    """name -> argument tuple of the libm known-answer test: float sinf / cosf / tanf / atanf / atan2f (2,000 each, half
+    from the branch-threshold neighbourhoods) and double cos / sin / log (900 each) on promoted floats, as
+    kb8_project_f and PredictScale call them."""
+    rng = np.random.default_rng(20240211)
+    edges = trig_edges()
+    trig_in = np.concatenate([rng.choice(edges, KAT_F32 // 2, replace=False),
+                              f32(rng.integers(0, B120, KAT_F32 // 2, dtype=np.uint64).astype(U32)
+                                  | (rng.integers(0, 2, KAT_F32 // 2, dtype=np.uint64).astype(U32) << 31))])
+    wide = atanf()[-1][1]
+    atan_in = np.concatenate([rng.choice(edges, KAT_F32 // 2, replace=False), rng.choice(wide, KAT_F32 // 2, replace=False)])
+    sets = atan2()
+    pick = rng.choice(len(sets[0][1]), KAT_F32 - 800, replace=False)
+    pick2 = rng.choice(len(sets[1][1]), 800 - 289, replace=False)
+    y = np.concatenate([sets[0][1][pick], sets[1][1][pick2], sets[2][1]])
+    x = np.concatenate([sets[0][2][pick], sets[1][2][pick2], sets[2][2]])
+    psi = ((rng.random(KAT_F64) * 2 - 1) * np.pi).astype(F32).astype(np.float64)
+    ratio = (0.3 + rng.random(KAT_F64) * 9.7).astype(F32).astype(np.float64)
+    return {"sinf": (trig_in,), "cosf": (trig_in,), "tanf": (trig_in,), "atanf": (atan_in,), "atan2f": (y, x),
+            "cos": (psi,), "sin": (psi,), "log": (ratio,)}
+
+
+def kat_eval():
+    """The running C library on kat_inputs(): name -> outputs."""
+    import ctypes
+    import ctypes.util
+    import oracle
+    libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    ins = kat_inputs()
+    sc = oracle.libm_map(st.SINCOSF, ins["sinf"][0])
+    out = {"sinf": sc[:, 0].copy(), "cosf": sc[:, 1].copy(), "tanf": oracle.libm_map(st.TANF, ins["tanf"][0]),
+           "atanf": oracle.libm_map(st.ATANF, ins["atanf"][0]), "atan2f": oracle.libm_map(st.ATAN2F, *ins["atan2f"])}
+    for name in ("cos", "sin", "log"):
+        f = getattr(libm, name)
+        f.restype, f.argtypes = ctypes.c_double, [ctypes.c_double]
+        out[name] = np.array([f(v) for v in ins[name][0].tolist()])
+    return out

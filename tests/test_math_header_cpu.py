@@ -1,0 +1,211 @@
+"""The product's float layer (openmavis_amd/csrc/omv_math.h) compiled for the host, against the C library itself.
+
+Three links carry every "bit-exact" claim of the kernels, each a bit comparison of different things:
+  1. device build of the header == host build of the header       tests/test_math_device_gpu.py (needs no libm)
+  2. host build of the header == this machine's glibc              here: oracle.math_map == oracle.libm_map
+  3. this glibc == the recorded answers of glibc 2.35              here: tests/golden/libm_kat.npz
+The input sets are tests/math_inputs.py, shared with the GPU side."""
+import numpy as np
+import pytest
+
+import math_inputs as mi
+from openmavis_amd import selftest as st
+
+LIBM_BACKED = [st.SINCOSF, st.ATANF, st.ATAN2F, st.TANF, st.SQRTF, st.FAST_ATAN2_DEG, st.ROUND_EVEN, st.PREDICT_SCALE]
+CAMERA = [st.KB8_PROJECT, st.KB8_UNPROJECT, st.PINHOLE_PROJECT, st.PINHOLE_UNPROJECT]
+
+
+def _calls(fn):
+    return mi.camera_sets(fn) if fn in CAMERA else mi.SETS[fn]()
+
+
+def _describe(fn, name, a, b, got, want, bad):
+    rows = []
+    for i in bad[:5]:
+        args = a[i] if b is None or len(b) != len(a) else (a[i], b[i])
+        rows.append(f"{args!r}: {got[i]!r} != {want[i]!r}")
+    return f"{st.MATH_NAMES[fn]} [{name}]: {len(bad)} of {len(got)} differ, e.g. " + "; ".join(rows)
+
+
+@pytest.mark.parametrize("fn", LIBM_BACKED + CAMERA, ids=lambda f: st.MATH_NAMES[f])
+def test_host_header_equals_libm(oracle, fn):
+    """oracle_math_map (the header) == oracle_libm_map (sinf / cosf / atanf / atan2f / tanf / sqrtf / nearbyintf, the
+    oracle's kb8_project_f / kb8_unproject_f / Pinhole pair with glibc's double cos / sin / tan, oracle_fast_atan2, and
+    ceil(log()) for PredictScale), bit for bit, NaN == NaN, on every input set.
+
+    Asserted domain of sincosf / tanf: |y| < 120.  The restatement has glibc's reduce_fast only, no large-argument
+    reduction, and first departs from libm near 200; nothing is asserted beyond 120.  The callers stay far inside:
+    orb_extract.hip's angles are in [0, 2 pi), imu.hip's arguments are dt * theta (~1e-3), tri.hip takes cosines of
+    parallax angles through cosf_glibc, and kb8_unproject_f's tanf argument is clamped to pi / 2.  atanf / atan2f are
+    asserted over the whole float range, infinities and NaNs included."""
+    total = 0
+    for name, a, b, c in _calls(fn):
+        got, want = oracle.math_map(fn, a, b, c), oracle.libm_map(fn, a, b, c)
+        bad = mi.mismatches(got, want)
+        assert len(bad) == 0, _describe(fn, name, a, b, got, want, bad)
+        total += len(got)
+    print(f"{st.MATH_NAMES[fn]}: {total} inputs, header == libm")
+
+
+def test_input_sets_cover_the_unproject_branches():
+    """The pixel sets reach the scale = 1 branch (the principal point), the pi / 2 clamp, and rigs that need all ten
+    Newton steps (Hilti cameras 3 and 4 beyond the image; cameras 1 and 2 converge within four everywhere)."""
+    ten = 0
+    for ci, (_, k) in enumerate(mi.CALIBS):
+        steps, clamped = mi.newton_steps(k, mi.unproject_pixels(ci))
+        assert (steps == 0).sum() >= 1 and clamped.sum() >= 1000
+        ten += int((steps == 10).sum())
+    assert ten >= 1000
+    for name, a, *_ in mi.trig():
+        assert len(a) <= 1 << 24 and np.all(np.abs(a) < 120), name
+
+
+def test_running_libm_reproduces_the_recorded_answers():
+    """tests/golden/libm_kat.npz holds glibc 2.35's answers (tools/make_golden.py libm_kat) on 2,000 inputs per float
+    function and 900 per double function.  A C library that rounds one of them differently fails here, as a libm
+    difference, and not in the header comparison above as a header bug."""
+    import os
+    kat = np.load(os.path.join(os.path.dirname(__file__), "golden", "libm_kat.npz"))
+    got = mi.kat_eval()
+    assert sorted(got) == sorted(k for k in kat.files if k != "libc")
+    for name, v in got.items():
+        bad = mi.mismatches(v, kat[name])
+        assert len(bad) == 0, (f"this C library's {name} differs from the recorded {kat['libc']} on {len(bad)} of {len(v)} "
+                               f"inputs, e.g. {[a[bad[0]] for a in mi.kat_inputs()[name]]!r}: {v[bad[0]]!r} != "
+                               f"{kat[name][bad[0]]!r}")
+
+
+def _ulp32(v):
+    import mpmath
+    if v == 0:
+        return mpmath.mpf(2) ** -149
+    return mpmath.ldexp(1, max(int(mpmath.floor(mpmath.log(abs(v), 2))), -126) - 23)
+
+
+def test_accuracy_against_mpmath(oracle):
+    """A sanity check that the recorded libm is a sane one: the error of the host header and of libm against mpmath at
+    50 digits, in ulps of float, on 4,096 samples per transcendental function drawn from the input sets.  The bar for
+    the header is libm's own figure of the same run, with no margin (the two are bit-identical).
+
+    Measured (glibc 2.35): sinf 0.5372, cosf 0.5291, tanf 0.6540, atanf 0.5871, atan2f 0.8618 ulp at most, header and
+    libm alike."""
+    import mpmath
+    rng = np.random.default_rng(20240212)
+
+    def pick(arrs, cond):
+        ok = np.flatnonzero(cond(*arrs))
+        idx = rng.choice(ok, 4096, replace=False)
+        return [np.ascontiguousarray(a[idx]) for a in arrs]
+    trig_in = np.concatenate([a for _, a, *_ in mi.trig()])
+    (x,) = pick([trig_in], np.isfinite)
+    (xa,) = pick([np.concatenate([a for _, a, *_ in mi.atanf()])], np.isfinite)
+    sets = mi.atan2()
+    y2, x2 = pick([np.concatenate([s[1] for s in sets]), np.concatenate([s[2] for s in sets])],
+                  lambda y, x: np.isfinite(y) & np.isfinite(x) & ((y != 0) | (x != 0)))
+    cases = [("sinf", st.SINCOSF, 0, (x,), mpmath.sin), ("cosf", st.SINCOSF, 1, (x,), mpmath.cos),
+             ("tanf", st.TANF, None, (x,), mpmath.tan), ("atanf", st.ATANF, None, (xa,), mpmath.atan),
+             ("atan2f", st.ATAN2F, None, (y2, x2), mpmath.atan2)]
+    with mpmath.workdps(50):
+        for name, fn, col, args, ref in cases:
+            hdr, libm = oracle.math_map(fn, *args), oracle.libm_map(fn, *args)
+            if col is not None:
+                hdr, libm = hdr[:, col], libm[:, col]
+            err = [mpmath.mpf(0), mpmath.mpf(0)]
+            for i in range(4096):
+                want = ref(*[mpmath.mpf(float(a[i])) for a in args])
+                u = _ulp32(want)
+                for j, got in enumerate((hdr[i], libm[i])):
+                    err[j] = max(err[j], abs(mpmath.mpf(float(got)) - want) / u)
+            print(f"{name}: header {float(err[0]):.4f} ulp, libm {float(err[1]):.4f} ulp")
+            assert err[1] < 1.0, f"{name}: this libm is off by {float(err[1])} ulp"
+            assert err[0] <= err[1], f"{name}: header {float(err[0])} ulp > libm {float(err[1])} ulp"
+
+
+def _fast_atan2_numpy(y, x):
+    """cv::fastAtan2 from OpenCV's published atan_f32 (modules/core/src/mathfuncs_core.simd.hpp), in numpy float32:
+    every operation one IEEE float operation, the coefficients the float products p_k * (float)(180 / pi)."""
+    f = np.float32
+    r2d = f(180.0 / np.pi)
+    p1, p3, p5, p7 = (f(v) * r2d for v in (0.9997878412794807, -0.3258083974640975, 0.1555786518463281,
+                                            -0.04432655554792128))
+    eps = f(2.220446049250313e-16)
+    ax, ay = np.abs(x), np.abs(y)
+    with np.errstate(all="ignore"):
+        big = ax >= ay
+        c = np.where(big, ay / (ax + eps), ax / (ay + eps))
+        c2 = c * c
+        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c
+        a = np.where(big, a, f(90.0) - a)
+        a = np.where(x < 0, f(180.0) - a, a)
+        a = np.where(y < 0, f(360.0) - a, a)
+    assert a.dtype == np.float32
+    return a
+
+
+def test_numpy_restatements_agree_with_the_host_header(oracle):
+    """fast_atan2_deg against OpenCV's formula in numpy float32; sqrtf_cr, `/` and round_even against numpy's IEEE
+    float32 sqrt, divide and rint."""
+    for name, y, x, _ in mi.fast_atan2():
+        bad = mi.mismatches(oracle.math_map(st.FAST_ATAN2_DEG, y, x), _fast_atan2_numpy(y, x))
+        assert len(bad) == 0, (name, len(bad), y[bad[:3]], x[bad[:3]])
+    with np.errstate(all="ignore"):
+        for name, a, *_ in mi.sqrtf():
+            bad = mi.mismatches(oracle.math_map(st.SQRTF, a), np.sqrt(a))
+            assert len(bad) == 0, (name, len(bad), a[bad[:3]])
+        for name, a, b, _ in mi.divf():
+            bad = mi.mismatches(oracle.math_map(st.DIVF, a, b), a / b)
+            assert len(bad) == 0, (name, len(bad), a[bad[:3]], b[bad[:3]])
+    for name, a, *_ in mi.round_even():
+        assert np.array_equal(oracle.math_map(st.ROUND_EVEN, a), np.rint(a).astype(np.int32)), name
+
+
+def test_host_build_does_not_contract(oracle):
+    """The host build of the probes returns the unfused a * b + c on >= 10^5 triples each whose fused value differs
+    (-ffp-contract=off in oracle/Makefile)."""
+    for fn, (a, b, c, unfused, fused) in ((st.MULADD_F32, mi.muladd_f32()), (st.MULADD_F64, mi.muladd_f64())):
+        assert len(a) >= 100000 and not mi.same_bits(unfused, fused).any()
+        got = oracle.math_map(fn, a, b, c)
+        assert mi.same_bits(got, unfused).all(), (st.MATH_NAMES[fn], int((~mi.same_bits(got, unfused)).sum()))
+
+
+def test_host_double_libm_calls_against_50_digits(oracle):
+    """kb8_project_f and PredictScale call glibc's double cos / sin / log.  On the committed seeds the host result is
+    held to the rule of the GPU tests: it equals the correct rounding of the 50-digit value of the written expression,
+    or that value lies within 4 double ulps of a rounding boundary (of an integer, for the ceil) and the result is one
+    of the two neighbours; at most one such sample per test is the reference's to use up.
+
+    Every sample is first evaluated in numpy's 80-bit long double; only samples whose long-double value is within 2^-40
+    (relative) of a boundary, or whose host result differs from the long-double rounding, go to mpmath.
+
+    Measured: the reference uses up 0 samples of kb8_project_f (5 calibrations x 131,584 points) and 0 of PredictScale
+    (1,179,664 ratios)."""
+    ld = np.longdouble
+    assert np.finfo(ld).nmant >= 63
+    # PredictScale
+    (_, ratio, lsf, _), = mi.predict_scale()
+    got = oracle.math_map(st.PREDICT_SCALE, ratio, lsf)
+    v = np.log(ratio.astype(ld)) / ld(lsf[0])
+    near = np.abs(v - np.rint(v)) <= np.abs(v) * ld(2.0) ** -40 + ld(2.0) ** -60
+    idx = np.flatnonzero(near | (got != np.ceil(v).astype(np.int32)))
+    ties, bad = mi.judge_predict_scale(ratio, lsf[0], got, idx)
+    print(f"PredictScale: {len(idx)} of {len(ratio)} samples to mpmath, {ties} on a boundary")
+    assert not bad and ties <= 1, (ties, bad[:5])
+    # kb8_project_f
+    total = 0
+    for name, X, k, _ in mi.camera_sets(st.KB8_PROJECT):
+        got = oracle.math_map(st.KB8_PROJECT, X, k)
+        kr0, kr1, psi, k2, k3 = mi.kb8_project_operands(k, X)
+        with np.errstate(all="ignore"):
+            cand = np.zeros(len(X), bool)
+            for col, kr, kk, f in ((0, kr0, k2, np.cos), (1, kr1, k3, np.sin)):
+                v = kr.astype(ld) * f(psi.astype(ld)) + ld(kk)
+                r = v.astype(np.float32)
+                lo, hi = np.nextafter(r, np.float32(-np.inf)).astype(ld), np.nextafter(r, np.float32(np.inf)).astype(ld)
+                gap = np.minimum(np.abs(v - (r.astype(ld) + lo) / 2), np.abs(v - (r.astype(ld) + hi) / 2))
+                cand |= np.isfinite(v) & ((gap <= np.abs(v) * ld(2.0) ** -40) | ~mi.same_bits(got[:, col], r))
+        idx = np.flatnonzero(cand)
+        ties, bad = mi.judge_kb8_project(k, X, got, idx)
+        print(f"kb8_project_f [{name}]: {len(idx)} of {len(X)} points to mpmath, {ties} on a boundary")
+        assert not bad, bad[:5]
+        total += ties
+    assert total <= 1

@@ -1,5 +1,5 @@
 """CPU checks of native pieces that do not need a GPU: the introsort replica against libstdc++'s
-std::sort, the glibc sincosf restatement against the host libm, and the C ABI export table."""
+std::sort and the C ABI export table (the libm restatements: tests/test_math_header_cpu.py)."""
 import os
 import re
 import subprocess
@@ -50,29 +50,6 @@ def test_introsort_replica_matches_std_sort():
                                src, "-o", exe])
         out = subprocess.run([exe], capture_output=True, text=True)
         assert out.returncode == 0 and "OK" in out.stdout, out.stdout
-
-
-def test_sincosf_restatement_matches_libm():
-    """tools/check_sincosf.c carries the same constants/ops as omv_device.h::glibc_sincosf; here a
-    strided sweep of [0, 2*pi] (the full sweep is bit-exact too: 1,086,918,620 floats)."""
-    src = os.path.join(ROOT, "tools", "check_sincosf.c")
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "cs")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-DUSEFMA", "-DSTRIDE=97", src, "-o", exe, "-lm"])
-        out = subprocess.run([exe], capture_output=True, text=True, timeout=120).stdout
-        m = re.search(r"cos_bad (\d+) sin_bad (\d+)", out)
-        assert m and m.group(1) == "0" and m.group(2) == "0", out
-
-
-def test_atan2f_restatement_matches_libm():
-    """tools/check_atan2f.c carries the same constants/ops as omv_device.h::glibc_atan2f (KB8 projection)."""
-    src = os.path.join(ROOT, "tools", "check_atan2f.c")
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "at")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-DN=3000000L", src, "-o", exe, "-lm"])
-        out = subprocess.run([exe], capture_output=True, text=True, timeout=120).stdout
-        m = re.search(r"n (\d+) bad (\d+)", out)
-        assert m and int(m.group(1)) > 2000000 and m.group(2) == "0", out
 
 
 def _declared_symbols():

@@ -1,7 +1,7 @@
 """CPU checks of the SearchForTriangulation restatement (oracle/tri_oracle.cpp; ORBmatcher.cc:1131-1456,
 KannalaBrandt8.cpp:96-126, 219-229, 319-429, Eigen::JacobiSVD<Matrix4f>).  The reference holds no
 fixtures for these (parity unpinned vs OpenCV/Eigen); these pin the restatement's behaviour, and
-tools/check_tanf.c pins the std::tan(float) it depends on against glibc (exhaustive)."""
+tests/test_math_header_cpu.py pins the std::tan(float) it depends on against glibc."""
 import numpy as np
 import pytest
 

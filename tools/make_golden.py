@@ -5,7 +5,8 @@ hold no fixtures for this path, so these vectors pin the oracle's restated seman
 real OpenCV stays unpinned).  Images are regenerated from their seed at test time and checked by
 SHA-256; keypoints, descriptors and matcher outputs are stored.
 
-    python tools/make_golden.py
+    python tools/make_golden.py             # everything
+    python tools/make_golden.py libm_kat    # only the C library's known answers (tests/golden/libm_kat.npz)
 """
 import hashlib
 import os
@@ -32,8 +33,25 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+def make_libm_kat():
+    """The running C library's sinf / cosf / tanf / atanf / atan2f and double cos / sin / log on the inputs of
+    tests/math_inputs.kat_inputs() (regenerated from their seed at test time, so only the outputs are stored).  The
+    bit-exact claims of the device float layer are claims about this glibc (2.35); the test that reads the file tells a
+    different C library apart from a broken header."""
+    import platform
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import math_inputs
+    out = math_inputs.kat_eval()
+    path = os.path.join(OUT, "libm_kat.npz")
+    np.savez_compressed(path, libc=" ".join(platform.libc_ver()), **out)
+    print("libm_kat", {k: len(v) for k, v in out.items()}, os.path.getsize(path), "bytes")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["libm_kat"]:
+        return make_libm_kat()
+    make_libm_kat()
     for name, seed, w, h, nf, ini, mn, lap in ORB_CASES:
         img = synth.synth_image(seed, w, h)
         mono, kps, desc = oracle.orb_extract(img, nf, 1.2, 8, ini, mn, lap)
