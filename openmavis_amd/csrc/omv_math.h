@@ -114,8 +114,8 @@ OMV_MATH_FN void glibc_sincosf(float y, float *sinp, float *cosp) {
     double r = x * t0.hpi_inv;
     int n = ((int32_t)r + 0x800000) >> 24;
     double xr = __builtin_fma(-(double)n, t0.hpi, x);
-    const double sgn[4] = {1.0, -1.0, -1.0, 1.0};
-    double s = sgn[n & 3];
+    // glibc's sign table {1, -1, -1, 1}[n & 3] as a select (an indexed table is a memory load on the device)
+    double s = ((n + 1) & 2) ? -1.0 : 1.0;
     const SinCosTab &p = (n & 2) ? t1 : t0;
     *sinp = sincosf_poly(xr * s, xr * xr, p, n);
     *cosp = sincosf_poly(xr * s, xr * xr, p, n ^ 1);

@@ -83,7 +83,19 @@ struct LevelGeom {
 
 struct Cell {
     int level, y0, y1, x0, x1;   // region rows [y0,y1), cols [x0,x1) in level coordinates
+    // What K2 derives from the rectangle alone, host-computed (fast_cell_constants) and read with the rectangle by
+    // one scalar load; every wave of every image recomputed them, three integer divisions included.  The dword path's
+    // values hold for a dword-aligned level base and pitch, where the region's misalignment is o = x0 & 3 (the
+    // kernel tests the alignment at run time; its byte path has o = 0 and uses ndet and mdw only).
+    int o, nd, rpi;              // dwords of a staged row (x1 - x0 + o + 3) >> 2, rows per 64-lane band 64 / nd
+    uint32_t mnd;                // lane / nd = lane * mnd >> 16 (lane < 64)
+    int ndet;                    // detection window pixels (x1 - x0 - 6) * (y1 - y0 - 6), 0 when empty
+    uint32_t mdw;                // i / dw = i * mdw >> 20
+    int jq0, npr, np;            // first LDS dword of the window, dword pairs per row, pairs of the window
+    uint32_t mp;                 // t / npr = t * mp >> 20
+    int nband;                   // whole bands of rpi rows in the region: (y1 - y0) / rpi
 };
+static_assert(sizeof(Cell) == 64, "Cell: one 64-byte scalar load");
 
 struct Geom {
     int nlevels;
@@ -520,8 +532,8 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
     const uint8_t *src = level_base(g, images, img_stride, pitch0, pyr, img, c.level, &sp);
     const uint8_t *row0 = src + (size_t)c.y0 * sp + c.x0;
     const bool dwords = ((sp & 3) == 0) && ((((uintptr_t)src) & 3) == 0);
-    const int o = dwords ? (int)(((uintptr_t)row0) & 3) : 0;
-    const int rs = RS > 0 ? RS : ((rw + o + 3) & ~3);
+    const int o = dwords ? c.o : 0;   // = row0 & 3
+    const int rs = RS > 0 ? RS : dwords ? 4 * c.nd : ((rw + 3) & ~3);
     uint8_t *pix = smem + o;
     // the strength map covers the NMS reach only: rows / columns 2 .. n-3 of the region, (r, q) at
     // S[(r - 2) * sw + q - 2] (the region's outer rows never hold a candidate or an NMS neighbour)
@@ -529,19 +541,23 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
     const int sw = rw - 4;
     uint16_t *cand = (uint16_t *)(smem + rmax + smax);
     if (dwords) {
-        const int nd = (rw + o + 3) >> 2;   // dwords of a row read (the LDS row holds rs / 4)
-        const uint32_t *g0 = (const uint32_t *)(row0 - o);
-        const int sw = sp >> 2;
+        const int nd = c.nd;   // dwords of a row read (the LDS row holds rs / 4)
+        // uniform base + a 32-bit byte offset per lane: lr < 64 and pitch < 2^24 (level pitches are <= 4,000, level
+        // 0's is checked by omv_orb_extract_batch), so lr * sp is a 24-bit multiply and 80 rows stay below 2^31
+        const uint8_t *g0 = row0 - o;
         uint32_t *l0 = (uint32_t *)smem;
         // lane -> (row lr of a band of rpi rows, dword w); the band steps down the region by pointer increments
-        const int rpi = 64 / nd, lr = lane / nd, w = lane - lr * nd;
+        const int rpi = c.rpi, lr = omv::mul_u24(lane, (int)c.mnd) >> 16, w = lane - omv::mul_u24(lr, nd);
         if (lr < rpi) {
-            const uint32_t *gs = g0 + (size_t)lr * sw + w;
-            uint32_t *ld = l0 + lr * (rs >> 2) + w;
-            const size_t gstep = (size_t)rpi * sw;
+            uint32_t gs = (uint32_t)(omv::mul_u24(lr, sp) + 4 * w);
+            uint32_t *ld = l0 + omv::mul_u24(lr, rs >> 2) + w;
+            const uint32_t gstep = (uint32_t)(rpi * sp);
             const int lstep = rpi * (rs >> 2);
+            // rh / rpi whole bands, then the rows left for the first lanes (a per-lane trip count r < rh is one more
+            // integer division for the unrolled loop's remainder)
 #pragma unroll 4
-            for (int r = lr; r < rh; r += rpi, gs += gstep, ld += lstep) *ld = *gs;
+            for (int b = 0; b < c.nband; ++b, gs += gstep, ld += lstep) *ld = *(const uint32_t *)(g0 + gs);
+            if (lr < rh - c.nband * rpi) *ld = *(const uint32_t *)(g0 + gs);
         }
     } else {
         for (int i = lane; i < rw * rh; i += 64) {
@@ -552,9 +568,9 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
     for (int i = lane; i < (sw * (rh - 4) + 15) >> 4; i += 64) ((uint4 *)S)[i] = make_uint4(0, 0, 0, 0);   // rmax % 16 == 0
     __syncthreads();
     const int dw = rw - 6, dh = rh - 6;   // detection window [3, rw-4] x [3, rh-4]
-    const int ndet = (dw > 0 && dh > 0) ? dw * dh : 0;
+    const int ndet = c.ndet;
     // i / dw by multiply-shift with m = floor(2^20/dw) + 1: exact while i * dw < 2^20 (cells are < 80 px wide)
-    const uint32_t mdw = dw > 0 ? (1u << 20) / (uint32_t)dw + 1u : 0u;
+    const uint32_t mdw = c.mdw;
     auto rowcol = [&](int i, int &r, int &q) {
         const int rr = omv::mul_u24(i, (int)mdw) >> 20;
         r = 3 + rr, q = 3 + i - omv::mul_u24(rr, dw);   // 24-bit multiplies: full rate
@@ -569,10 +585,11 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
             // v_perm each), the tests on packed int16 pairs.  The adjacent-pair test (a0&a4)|(a4&a8)|(a8&a12)|(a12&a0) is (a0|a8)&(a4|a12).  Survivors go to the
             // list by a DPP wave scan of the per-lane counts, each lane then writing its set bits.
             const uint32_t *w32 = reinterpret_cast<const uint32_t *>(smem);
-            const int jq0 = (o + 3) >> 2, jq1 = (o + rw - 4) >> 2, nqr = jq1 - jq0 + 1, rsw = rs >> 2;
-            const int npr = (nqr + 1) >> 1;   // dword pairs per row
-            const int np = npr * dh;
-            const uint32_t mp = (1u << 20) / (uint32_t)npr + 1u;   // tp / npr, exact while tp * npr < 2^20
+            // window dwords jq0 = (o + 3) >> 2 .. (o + rw - 4) >> 2 of a row, in pairs
+            const int jq0 = c.jq0, rsw = rs >> 2;
+            const int npr = c.npr;   // dword pairs per row
+            const int np = c.np;
+            const uint32_t mp = c.mp;   // tp / npr, exact while tp * npr < 2^20
             const pk16 T0{(short)t, (short)t};
             // bytes s, s+1 (lo) / s+2, s+3 (hi) of the 8-byte {a:b} as a packed int16 pair
             auto lo = [](uint32_t a, uint32_t b, uint32_t s) {
@@ -1266,9 +1283,20 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-__global__ void __launch_bounds__(256) describe_kernel(Geom g, DescArgs a, int n_blocks) {
+// Sum of lanes 0 .. 15 of v (row_shr 1 / 2 / 4 / 8 leave it in lane 15), wave-uniform; every lane must be active.
+__device__ __forceinline__ int row0_sum_dpp(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+    return __builtin_amdgcn_readlane(v, 15);
+}
+
+// (256, 2): with the register budget of two workgroups per SIMD the MFMA results stay in VGPRs (the default budget
+// put them in AGPRs: 48 accumulator copies per wave); the allocation itself still fits eight waves per SIMD
+__global__ void __launch_bounds__(256, 2) describe_kernel(Geom g, DescArgs a, int n_blocks) {
     // the wave index is wave-uniform: everything derived from the slot (record, level, counts, patch origin) is
-    // scalar work and scalar loads
+    // scalar work
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int blk = omv::xcd_block(n_blocks);
     if (blk < 0) return;
@@ -1276,21 +1304,30 @@ __global__ void __launch_bounds__(256) describe_kernel(Geom g, DescArgs a, int n
     const int img = slot / g.out_per_img;
     const int s = slot - img * g.out_per_img;
     if (img >= a.n_images) return;
+    // the image's level counts (total, mono, lapping), level q in lane q: one wave-wide load, issued together with the
+    // slot's record (one round trip; slots past the count are in bounds) and ahead of the level search.  Everything
+    // the kernel needs of the counts is summed from these registers (kMaxLevels = 16 lanes = one DPP row)
+    static_assert(kMaxLevels <= 16, "describe_kernel: the level counts fill one 16-lane row");
+    const int *cnts = a.lvl_cnt + (size_t)img * g.nlevels * 3;
+    int c_tot = 0, c_mono = 0, c_lap = 0;
+    if (lane < g.nlevels) c_tot = cnts[3 * lane], c_mono = cnts[3 * lane + 1], c_lap = cnts[3 * lane + 2];
+    const uint32_t p = a.lvl_out[(size_t)img * g.out_per_img + s];
+    const uint32_t cl = a.lvl_cls[(size_t)img * g.out_per_img + s];
     int l = 0;
     while (l + 1 < g.nlevels && s >= g.lv[l + 1].out_off) ++l;
     const LevelGeom &L = g.lv[l];
     const int j = s - L.out_off;
-    const int *cnts = a.lvl_cnt + (size_t)img * g.nlevels * 3;
-    if (s == 0 && lane == 0) {
-        int tot = 0, mono = 0;
-        for (int q = 0; q < g.nlevels; ++q) tot += cnts[3 * q], mono += cnts[3 * q + 1];
-        a.n_out[img] = tot;
-        a.mono[img] = mono;
+    const int total = row0_sum_dpp(c_tot);
+    if (s == 0) {
+        const int mono = row0_sum_dpp(c_mono);
+        if (lane == 0) {
+            a.n_out[img] = total;
+            a.mono[img] = mono;
+        }
     }
-    // the slot's record is loaded with the level count (one round trip; slots past the count are in bounds)
-    const uint32_t p = a.lvl_out[(size_t)img * g.out_per_img + s];
-    const uint32_t cl = a.lvl_cls[(size_t)img * g.out_per_img + s];
-    if (j >= cnts[3 * l]) return;
+    if (j >= __builtin_amdgcn_readlane(c_tot, l)) return;
+    // final row: monoIndex order (front) or lapping order (back, reversed)
+    const int mono_before = row0_sum_dpp(lane < l ? c_mono : 0), lap_before = row0_sum_dpp(lane < l ? c_lap : 0);
     // the lane's constant tables (independent of the record: in flight together)
     const uint4 dm0 = reinterpret_cast<const uint4 *>(a.disc)[2 * lane], dm1 = reinterpret_cast<const uint4 *>(a.disc)[2 * lane + 1];
     float4 pat[4];
@@ -1448,12 +1485,6 @@ __global__ void __launch_bounds__(256) describe_kernel(Geom g, DescArgs a, int n
         const int bdx = omv::round_even(bx * fa - by * fb);
         words[rd] = __ballot(blurred(adx, ady) < blurred(bdx, bdy));
     }
-    // final row: monoIndex order (front) or lapping order (back, reversed)
-    int mono_before = 0, lap_before = 0, total = 0;
-    for (int q = 0; q < g.nlevels; ++q) {
-        total += cnts[3 * q];
-        if (q < l) mono_before += cnts[3 * q + 1], lap_before += cnts[3 * q + 2];
-    }
     const int rank = (int)(cl & 0x7fffffffu);
     const int row = (cl >> 31) ? total - 1 - (lap_before + rank) : mono_before + rank;
     omv_kp *kp = a.kps + (size_t)img * g.n_max + row;
@@ -1550,6 +1581,27 @@ static void mark(omv_orb *o, hipStream_t st) {
     o->ev.push_back(e);
 }
 
+// A FAST cell with the constants K2 reads instead of deriving (struct Cell): the same integer expressions the
+// kernel used to evaluate per wave.
+static Cell fast_cell_constants(int level, int y0, int y1, int x0, int x1) {
+    Cell c{};
+    c.level = level, c.y0 = y0, c.y1 = y1, c.x0 = x0, c.x1 = x1;
+    const int rw = x1 - x0, rh = y1 - y0, dw = rw - 6, dh = rh - 6;
+    c.o = x0 & 3;
+    c.nd = (rw + c.o + 3) >> 2;
+    c.rpi = c.nd > 0 ? 64 / c.nd : 0;
+    c.nband = c.rpi > 0 ? rh / c.rpi : 0;
+    c.mnd = c.nd > 0 ? (1u << 16) / (uint32_t)c.nd + 1u : 0u;   // exact while lane * nd < 2^16
+    c.ndet = (dw > 0 && dh > 0) ? dw * dh : 0;
+    c.mdw = dw > 0 ? (1u << 20) / (uint32_t)dw + 1u : 0u;
+    c.jq0 = (c.o + 3) >> 2;
+    const int jq1 = (c.o + rw - 4) >> 2, nqr = jq1 - c.jq0 + 1;
+    c.npr = (nqr + 1) >> 1;
+    c.np = c.npr * dh;
+    c.mp = c.npr > 0 ? (1u << 20) / (uint32_t)c.npr + 1u : 0u;
+    return c;
+}
+
 static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vector<XTab> &xt, std::vector<XTab> &yt, std::vector<XQuad> &xq) {
     const omv_orb_params &p = o->p;
     const int nl = p.nlevels;
@@ -1604,11 +1656,13 @@ static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vect
         // FAST cells (:718-742)
         const float width = (float)(L.maxBX - kMinB), height = (float)(L.maxBY - kMinB);
         const int nCols = (int)(width / 35.f), nRows = (int)(height / 35.f);
-        if (nCols < 1 || nRows < 1) return OMV_ERR_ARG;   // level too small: the reference divides by 0
-        const int wCell = (int)std::ceil(width / nCols), hCell = (int)std::ceil(height / nRows);
+        // a level too small for one 35-px cell has no cells: the reference's loops over 0 rows / 0 columns do not
+        // run (its cell size, a float division by zero, is then never used) and the level yields no keypoint
+        const bool has_cells = nCols >= 1 && nRows >= 1;
+        const int wCell = has_cells ? (int)std::ceil(width / nCols) : 0, hCell = has_cells ? (int)std::ceil(height / nRows) : 0;
         L.cell_begin = (int)cells.size();
         long long cap_lvl = 0;
-        for (int i = 0; i < nRows; ++i) {
+        for (int i = 0; has_cells && i < nRows; ++i) {
             const float iniY = (float)(kMinB + i * hCell);
             float maxY = iniY + hCell + 6;
             if (iniY >= L.maxBY - 3) continue;
@@ -1618,7 +1672,7 @@ static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vect
                 float maxX = iniX + wCell + 6;
                 if (iniX >= L.maxBX - 6) continue;
                 if (maxX > L.maxBX) maxX = (float)L.maxBX;
-                Cell c{l, (int)iniY, (int)maxY, (int)iniX, (int)maxX};
+                const Cell c = fast_cell_constants(l, (int)iniY, (int)maxY, (int)iniX, (int)maxX);
                 cells.push_back(c);
                 max_rw = std::max(max_rw, c.x1 - c.x0);
                 max_rh = std::max(max_rh, c.y1 - c.y0);
@@ -1628,6 +1682,7 @@ static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vect
         max_cells_lvl = std::max(max_cells_lvl, L.cell_end - L.cell_begin);
         // octree initial strips (:505-507)
         const int Wn = L.maxBX - kMinB, Hn = L.maxBY - kMinB;
+        if (Wn < 1 || Hn < 1) return OMV_ERR_ARG;   // the reference divides by zero here
         L.nIni = (int)std::round((float)Wn / Hn);
         if (L.nIni < 1) return OMV_ERR_ARG;   // the reference divides by zero here
         L.hX = (float)Wn / L.nIni;
@@ -1693,6 +1748,7 @@ static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vect
         L.m_quads = divm((L.w + 3) / 4), L.m_groups = divm((L.w + 15) / 16), L.m_w = divm(L.w);
     }
     g.n_cells = (int)cells.size();
+    if (g.n_cells == 0) return OMV_ERR_ARG;   // no level holds a cell
     if (max_rw > 80 || max_rh > 80) return OMV_ERR_ARG;   // K2's index arithmetic (cells are ~35-45 px)
     const int dw = max_rw - 6, dh = max_rh - 6;
     g.cell_cap = ((dw + 1) / 2) * ((dh + 1) / 2);
@@ -1918,6 +1974,7 @@ omv_status omv_orb_extract_batch(omv_orb *o, int n, const uint8_t *images, size_
     if (!o || n <= 0 || n > o->max_images || !images || !lapping || !kps || !desc || !n_out || !mono_index)
         return OMV_ERR_ARG;
     if (pitch < (size_t)o->W || image_stride < pitch * o->H) return OMV_ERR_ARG;
+    if (pitch >= ((size_t)1 << 24)) return OMV_ERR_ARG;   // K2's 32-bit row offsets (fast_cells_kernel's staging)
     hipStream_t st = (hipStream_t)stream;
     o->last_stream = st;
     o->last_n = n;
