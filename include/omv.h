@@ -1048,6 +1048,53 @@ omv_status omv_sim3_solver_debug(omv_sim3_solver *h, int job, int32_t *n_hyp, in
                                  float *scale, float *T12, float *T21, int32_t *count, uint64_t *mask_words,
                                  void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Optimizer::OptimizeSim3 (src/Optimizer.cc:2460-2726): the Sim3 refinement of LoopClosing's loop / merge candidates
+ * (src/LoopClosing.cc:658, :899, :935), after Sim3Solver and between the SearchByProjection calls.  One call optimises
+ * n_jobs independent candidate pairs, one wavefront each.  Double arithmetic as g2o's, except that the two projection
+ * edges are differentiated analytically where g2o differentiates them numerically (delta 1e-9): the result agrees with
+ * the reference's to within that scheme's own noise, not bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+#define OMV_OPTSIM3_KEPT 0        /* match kept, not counted: P3D2c.z < 0 (no edge), or the call returned 0 early */
+#define OMV_OPTSIM3_INLIER 1      /* counted in n_in                                                             */
+#define OMV_OPTSIM3_REMOVED_1 2   /* vpMatches1[i] nulled after the first round                                  */
+#define OMV_OPTSIM3_REMOVED_2 3   /* vpMatches1[i] nulled by the final test                                      */
+typedef struct omv_optsim3 omv_optsim3;
+
+/* A handle for up to max_jobs candidate pairs and max_entries_total correspondences over all of them per call. */
+omv_status omv_optimize_sim3_create(int max_jobs, int max_entries_total, omv_optsim3 **out);
+omv_status omv_optimize_sim3_destroy(omv_optsim3 *h);
+
+/* Every pointer is HOST memory; the call synchronises `stream`.  Job j owns the entries entry_start[j] ..
+ * entry_start[j+1]-1 (entry_start[0] = 0): the i of vpMatches1 that pass the graph-side tests of :2522-2589 (a match, the
+ * keypoint on cameraID1, both map points present and not bad, i2 >= 0 || bAllPoints), in ascending i.  Per entry:
+ *   Xw1, Xw2      [n][3] pMP1 / pMP2->GetWorldPos()            obs1 [n][2] kp1.pt, inv_sigma2_1 [n] mvInvLevelSigma2[octave]
+ *   has_kp2       [n] i2 >= 0; then obs2 [n][2] = kp2.pt and inv_sigma2_2 [n] its level's; otherwise obs2 is computed
+ *                 (pCamera2->project(P3D2c) in float) and inv_sigma2_2 is that of pMP2->GetTrackScaleLevel(cameraID2)
+ * Per job: pose1/2 [12] Riw row-major then tiw (GetRotation / GetTranslation(cameraID)), cam1/2 [8] fx fy cx cy k0..k3,
+ * model1/2 OMV_CAM_KB8 / OMV_CAM_PINHOLE, fix_scale, th2, and g2oS12 in / out as q [4] (x y z w), t [3], s.
+ * Outputs: n_in [n_jobs] the return value; status [n] per entry (OMV_OPTSIM3_*): vpMatches1[i] is nulled for 2 and 3,
+ * and n_in is the number of entries with status 1.  The reference's quirks are kept: an entry with P3D2c.z < 0 is no
+ * edge and keeps its match; the round-one test reads the edges' stale errors; with fewer than 10 pairs left after round
+ * one the call returns 0 with g2oS12 untouched and the round-one removals in place; a NaN chi2 fails every `> th2`
+ * test, so its pair is kept and counted.  mAcumHessian is zero in the reference (set, never filled): not an output.
+ * OMV_ERR_ARG: an unknown camera model, a negative size or a descending entry_start, more jobs or entries than the
+ * handle holds, a NULL pointer with a non-zero size. */
+omv_status omv_optimize_sim3(omv_optsim3 *h, int n_jobs, const int32_t *entry_start, const float *Xw1, const float *Xw2,
+                             const float *obs1, const float *inv_sigma2_1, const uint8_t *has_kp2, const float *obs2,
+                             const float *inv_sigma2_2, const float *pose1, const float *pose2, const float *cam1,
+                             const float *cam2, const int32_t *model1, const int32_t *model2, const int32_t *fix_scale,
+                             const float *th2, double *q, double *t, double *s, int32_t *n_in, uint8_t *status,
+                             void *stream);
+
+/* Test hook: job `job` of the last omv_optimize_sim3 call, host outputs (any may be NULL).  The first buildSystem (at
+ * the input estimate, robust): H [49] row-major, b [7], chi2 (activeRobustChi2), lambda_init, x [7] the first trial's
+ * solution; e12, e21 [n][2] the residuals of every pair at the input estimate (0 where no edge); per round [2] the LM
+ * iterations, the trials, and the largest number of trials in one iteration.  Synchronous. */
+omv_status omv_optimize_sim3_debug(omv_optsim3 *h, int job, double *H, double *b, double *chi2, double *lambda_init,
+                                   double *x, double *e12, double *e21, int32_t *iterations, int32_t *trials,
+                                   int32_t *max_trials, void *stream);
+
 /* ---- Test hooks (no reference counterpart): the device linear-algebra routines on plain device arrays ----
  * Each launches the product's own instantiation of the routine, one workgroup per problem (`batch` problems, on
  * `stream`, not synchronised).  Every pointer is device memory. */

@@ -1418,6 +1418,63 @@ class Sim3Solver {
     DeviceArray<uint8_t> d_inl_;
 };
 
+// ---- Optimizer::OptimizeSim3 -------------------------------------------------------------------------------
+// g2o::Sim3 as the optimiser keeps it: quaternion (x y z w), translation, scale.
+struct Sim3 {
+    double q[4] = {0, 0, 0, 1}, t[3] = {0, 0, 0}, s = 1;
+};
+
+// What OptimizeSim3's loop over vpMatches1 reads (:2522-2653), flattened by the caller for the i that pass its
+// graph-side tests (a match, the keypoint on cameraID1, both map points present and not bad, i2 >= 0 || bAllPoints),
+// in ascending i; the chosen cameras' poses and intrinsics.
+struct OptimizeSim3Input {
+    std::vector<int32_t> index1;               // [N] i in vpMatches1
+    std::vector<float> Xw1, Xw2;               // [N][3] pMP1 / pMP2->GetWorldPos()
+    std::vector<float> obs1, obs2;             // [N][2] kp1.pt / kp2.pt (obs2 unused where has_kp2 is 0)
+    std::vector<float> inv_sigma2_1, inv_sigma2_2;   // [N] mvInvLevelSigma2[octave]; side 2 without a keypoint: of
+                                                     // pMP2->GetTrackScaleLevel(cameraID2)
+    std::vector<uint8_t> has_kp2;              // [N] i2 >= 0
+    float pose1[12] = {}, pose2[12] = {};      // GetRotation(cameraID) row-major, GetTranslation(cameraID)
+    float cam1[8] = {}, cam2[8] = {};          // fx fy cx cy k0..k3
+    int model1 = OMV_CAM_KB8, model2 = OMV_CAM_KB8;
+};
+
+// int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints, ...) on the
+// device.  vpMatches1: vpMatches1[i] != NULL, in / out (the entries the reference nulls become false); g2oS12 in / out
+// (untouched when the reference returns 0 before writing it back); mAcumHessian [49] receives the zero matrix the
+// reference leaves there.  status (optional) receives the per-entry OMV_OPTSIM3_* codes.  `h`: a handle to reuse
+// (at least one job and index1.size() entries), or nullptr for one made and destroyed by the call.
+inline int OptimizeSim3(const OptimizeSim3Input &in, std::vector<bool> &vpMatches1, Sim3 &g2oS12, const float th2,
+                        const bool bFixScale, std::array<double, 49> &mAcumHessian, omv_optsim3 *h = nullptr,
+                        hipStream_t stream = nullptr, std::vector<uint8_t> *status = nullptr) {
+    const int N = (int)in.index1.size();
+    if (in.Xw1.size() != (size_t)3 * N || in.Xw2.size() != (size_t)3 * N || in.obs1.size() != (size_t)2 * N ||
+        in.obs2.size() != (size_t)2 * N || in.inv_sigma2_1.size() != (size_t)N || in.inv_sigma2_2.size() != (size_t)N ||
+        in.has_kp2.size() != (size_t)N)
+        throw Error("OptimizeSim3: array lengths differ from index1's");
+    for (int i = 0; i < N; i++)
+        if (in.index1[i] < 0 || (size_t)in.index1[i] >= vpMatches1.size()) throw Error("OptimizeSim3: index1 out of range");
+    omv_optsim3 *own = nullptr;
+    if (!h) {
+        check(omv_optimize_sim3_create(1, N, &own), "omv_optimize_sim3_create");
+        h = own;
+    }
+    const int32_t entry_start[2] = {0, N}, m1 = in.model1, m2 = in.model2, fs = bFixScale ? 1 : 0;
+    int32_t n_in = 0;
+    std::vector<uint8_t> st(std::max(N, 1));
+    const omv_status rc = omv_optimize_sim3(h, 1, entry_start, in.Xw1.data(), in.Xw2.data(), in.obs1.data(),
+                                            in.inv_sigma2_1.data(), in.has_kp2.data(), in.obs2.data(),
+                                            in.inv_sigma2_2.data(), in.pose1, in.pose2, in.cam1, in.cam2, &m1, &m2, &fs,
+                                            &th2, g2oS12.q, g2oS12.t, &g2oS12.s, &n_in, st.data(), stream);
+    if (own) (void)omv_optimize_sim3_destroy(own);
+    check(rc, "omv_optimize_sim3");
+    for (int i = 0; i < N; i++)
+        if (st[i] == OMV_OPTSIM3_REMOVED_1 || st[i] == OMV_OPTSIM3_REMOVED_2) vpMatches1[in.index1[i]] = false;
+    mAcumHessian.fill(0.0);
+    if (status) status->assign(st.begin(), st.begin() + N);
+    return n_in;
+}
+
 }  // namespace omv_adapt
 
 #endif  // OMV_ADAPTERS_HPP

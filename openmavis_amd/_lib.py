@@ -338,6 +338,10 @@ SIGNATURES = {
     "omv_sim3_solver_iterate": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "omv_sim3_solver_best": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "omv_sim3_solver_debug": (_I, [_VP, _I] + [_VP] * 10),
+    "omv_optimize_sim3_create": (_I, [_I, _I, ctypes.POINTER(_VP)]),
+    "omv_optimize_sim3_destroy": (_I, [_VP]),
+    "omv_optimize_sim3": (_I, [_VP, _I] + [_VP] * 22),
+    "omv_optimize_sim3_debug": (_I, [_VP, _I] + [_VP] * 11),
 }
 
 _lib = None

@@ -990,4 +990,120 @@ __device__ inline bool ldlt_pivot_solve_wave(double *A, const double *b, double 
     return true;
 }
 
+// Eigen's quaternion ops on (x y z w): product and v' = q v q^-1 (_transformVector).
+__device__ __forceinline__ void q_mul(const double *a, const double *b, double *r) {
+    r[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    r[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    r[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    r[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+}
+__device__ __forceinline__ void q_rot(const double *q, const double *v, double *o) {
+    double u0 = q[1] * v[2] - q[2] * v[1], u1 = q[2] * v[0] - q[0] * v[2], u2 = q[0] * v[1] - q[1] * v[0];
+    u0 += u0, u1 += u1, u2 += u2;
+    o[0] = v[0] + q[3] * u0 + (q[1] * u2 - q[2] * u1);
+    o[1] = v[1] + q[3] * u1 + (q[2] * u0 - q[0] * u2);
+    o[2] = v[2] + q[3] * u2 + (q[0] * u1 - q[1] * u0);
+}
+
+// Eigen::LDLT<MatrixXd> (ldlt_inplace::unblocked's pivot order, isPositive(), _solve_impl's D pseudo-inverse below
+// DBL_MIN) of the N x N symmetric H (LDS, row-major) on one wavefront, lane i = pivot position i:
+//   pick order  Eigen swaps the largest |diagonal| of the trailing corner to position k, first position on ties; that
+//               diagonal is never updated before it is picked, so the order follows from the original diagonal alone:
+//               by rank when the magnitudes are distinct, else replayed step by step (one ballot per step)
+//   factor      rows of P H P^T in registers; step k: D_k by v_readlane, column k below scaled by 1 / D_k, trailing
+//               update from row k (v_readlane broadcasts, FMA); a zero pivot leaves its column unscaled and no update
+//               (its terms D_k l l^T vanish in Eigen's left-looking form)
+//   solve       y = P b, L y' = y, y'' = D^+ y', L^T x = y'', x = P^T (same per-element subtraction order as Eigen's
+//               triangular solves; the factor differs from Eigen's by rounding: right-looking, fused multiply-adds)
+// x: LDS out (written only on success); pick / Lm: LDS scratch [N] / [N * N].  Returns isPositive().
+template <int N>
+__device__ __forceinline__ bool ldlt_pick_solve(const double *H, const double *b, double *x, int *pick, double *Lm, int lane) {
+    static_assert(N <= 32, "rows on lanes 0..31");
+    const bool in = lane < N;
+    const double dv = in ? fabs(H[lane * (N + 1)]) : 0.0;
+    int gt = 0, eq = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const double o = fabs(H[j * (N + 1)]);
+        gt += o > dv ? 1 : 0;
+        eq += o == dv ? 1 : 0;
+    }
+    if (__ballot(in && !(dv == dv))) return false;   // a NaN diagonal: no factorisation
+    if (!__ballot(in && eq > 1)) {
+        if (in) pick[gt] = lane;
+    } else {   // selection with positional swaps, lanes = elements (pos = current position)
+        int pos = lane;
+        bool picked = false;
+        for (int k = 0; k < N; ++k) {
+            uint64_t cand = __ballot(in && !picked && gt <= k && k < gt + eq);
+            int e = __builtin_ctzll(cand);
+            if (cand & (cand - 1)) {   // several equal magnitudes: the lowest current position
+                int bp = __builtin_amdgcn_readlane(pos, e);
+                for (uint64_t m = cand & (cand - 1); m; m &= m - 1) {
+                    const int c = __builtin_ctzll(m), pc = __builtin_amdgcn_readlane(pos, c);
+                    if (pc < bp) bp = pc, e = c;
+                }
+            }
+            const int xk = __builtin_ctzll(__ballot(in && pos == k));
+            const int pe = __builtin_amdgcn_readlane(pos, e);
+            if (lane == xk) pos = pe;
+            if (lane == e) pos = k, picked = true;
+            if (lane == 0) pick[k] = e;
+        }
+    }
+    omv::wave_lds_sync();
+    const int pi = in ? pick[lane] : 0;
+    int pj[N];   // the pick order in registers first, then every row read back to back (H symmetric: column pi of row pj)
+#pragma unroll
+    for (int j = 0; j < N; ++j) pj[j] = pick[j];
+    double r[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) r[j] = in ? H[pj[j] * N + pi] : 0.0;
+    if (!(lane_f64(r[0], 0) != 0.0)) {   // largest |diagonal| zero: Eigen stops with ZeroSign; the solve gives x = 0
+        if (in) x[lane] = 0.0;
+        omv::wave_lds_sync();
+        return true;
+    }
+    // One basic block for the whole factorisation (no data-dependent branches) so the pivot chain of step k + 1 can
+    // issue while step k's trailing update is still in flight: a zero pivot gives inv = 0, hence l = 0 (no update,
+    // column k left unscaled), sign bits 1 (a positive D) / 2 (a negative D): Eigen's isPositive() = no bit 2.
+    int sign = 0;
+    double dmine = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const double d = lane_f64(r[k], k);
+        dmine = lane == k ? d : dmine;
+        const bool nz = fabs(d) > 0.0;
+        const double inv = nz ? omv::rcp_nr(d) : 0.0;
+        const bool below = lane > k;
+        const double l = below ? r[k] * inv : 0.0;
+#pragma unroll
+        for (int j = k + 1; j < N; ++j) r[j] = __builtin_fma(-l, lane_f64(r[j], k), r[j]);
+        r[k] = (below && nz) ? l : r[k];
+        sign |= (d > 0 ? 1 : 0) | (d < 0 ? 2 : 0);
+    }
+    if (sign & 2) return false;
+    double y = in ? b[pi] : 0.0;
+#pragma unroll
+    for (int k = 0; k + 1 < N; ++k) {
+        const double yk = lane_f64(y, k);
+        if (lane > k) y = __builtin_fma(-r[k], yk, y);
+    }
+    y = fabs(dmine) > 2.2250738585072014e-308 ? y / dmine : 0.0;
+    if (in)
+#pragma unroll
+        for (int j = 0; j < N; ++j) Lm[lane * N + j] = r[j];
+    omv::wave_lds_sync();
+#pragma unroll
+    for (int j = 0; j < N; ++j) r[j] = in ? Lm[j * N + lane] : 0.0;   // r[j] = L_j,lane
+#pragma unroll
+    for (int j = N - 1; j >= 1; --j) {
+        const double xj = lane_f64(y, j);
+        if (lane < j) y = __builtin_fma(-r[j], xj, y);
+    }
+    if (in) x[pi] = y;
+    omv::wave_lds_sync();
+    return true;
+}
+
 }  // namespace omv_g2o

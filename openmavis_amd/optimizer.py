@@ -310,3 +310,112 @@ class PoseInertialOptimizer:
         _lib.check(lib.omv_pose_constraint(int(H.shape[0]), _lib.ptr(H), _lib.ptr(out), ctypes.c_void_p(st)),
                    "omv_pose_constraint")
         return out
+
+
+# ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:2460-2726) -------------------------------------------------------------
+OPTSIM3_KEPT, OPTSIM3_INLIER, OPTSIM3_REMOVED_1, OPTSIM3_REMOVED_2 = 0, 1, 2, 3
+
+
+def select_sim3_edges(matched, cam_of_kp1, cameraID1, mp1_ok, mp2_ok, i2, bAllPoints=False):
+    """The graph-side filter of OptimizeSim3's loop over vpMatches1 (:2522-2589) on arrays of length N =
+    vpMatches1.size(): matched[i] = vpMatches1[i] != NULL; cam_of_kp1[i] = pKF1->kpIdxToCamIdx(i); mp1_ok[i] =
+    vpMapPoints1[i] && !isBad(); mp2_ok[i] = !vpMatches1[i]->isBad(); i2[i] = the index of vpMatches1[i] in pKF2 on
+    cameraID2 (-1: not seen there).  Returns (index1, has_kp2): the i that become entries of a job, ascending, and whether
+    each has a KF2 keypoint.  The P3D2c.z < 0 test needs the geometry and is the kernel's."""
+    matched, mp1_ok, mp2_ok = (np.asarray(a, bool).reshape(-1) for a in (matched, mp1_ok, mp2_ok))
+    i2 = np.asarray(i2, np.int64).reshape(-1)
+    keep = matched & (np.asarray(cam_of_kp1, np.int64).reshape(-1) == int(cameraID1)) & mp1_ok & mp2_ok
+    keep &= (i2 >= 0) | bool(bAllPoints)
+    idx = np.nonzero(keep)[0].astype(np.int32)
+    return idx, i2[idx] >= 0
+
+
+class Sim3Optimizer:
+    """One omv_optsim3 handle (openmavis_amd/csrc/optsim3.hip): OptimizeSim3 for up to max_jobs candidate pairs and
+    max_entries correspondences per call.  A job is a dict: per entry index1 [N], Xw1, Xw2 [N][3], obs1 [N][2],
+    inv_sigma2_1 [N], has_kp2 [N], obs2 [N][2], inv_sigma2_2 [N]; per job pose1, pose2 [12] (Riw row-major, tiw), cam1,
+    cam2 [8], model1, model2 (_lib.CAM_KB8 / CAM_PINHOLE), fix_scale, th2 and g2oS12 as q [4] (x y z w), t [3], s.
+    There is no CPU fallback."""
+
+    _ENTRY = (("Xw1", np.float32, 3), ("Xw2", np.float32, 3), ("obs1", np.float32, 2), ("inv_sigma2_1", np.float32, 1),
+              ("has_kp2", np.uint8, 1), ("obs2", np.float32, 2), ("inv_sigma2_2", np.float32, 1))
+    _JOB = (("pose1", np.float32, 12), ("pose2", np.float32, 12), ("cam1", np.float32, 8), ("cam2", np.float32, 8),
+            ("model1", np.int32, 1), ("model2", np.int32, 1), ("fix_scale", np.int32, 1), ("th2", np.float32, 1))
+
+    def __init__(self, max_jobs=8, max_entries=4096, stream=None):
+        self._lib, self.stream = _lib.load(), stream
+        self._h = ctypes.c_void_p()
+        _lib.check(self._lib.omv_optimize_sim3_create(int(max_jobs), int(max_entries), ctypes.byref(self._h)),
+                   "omv_optimize_sim3_create")
+        self.n = np.zeros(0, np.int32)
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.omv_optimize_sim3_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def _stream(self):
+        if self.stream is not None:
+            return ctypes.c_void_p(self.stream.cuda_stream)
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def run(self, jobs):
+        """omv_optimize_sim3 on `jobs`; returns (status code, n_in [J], q [J][4], t [J][3], s [J], status per job)."""
+        J = len(jobs)
+        n = np.array([len(np.asarray(j["Xw1"]).reshape(-1, 3)) for j in jobs], np.int32)
+        start = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
+
+        def cat(key, dt, width):
+            if not J:
+                return np.zeros((0, width), dt)
+            return np.ascontiguousarray(np.concatenate([np.asarray(j[key], dt).reshape(-1, width) for j in jobs]))
+
+        entry = [cat(k, dt, w) for k, dt, w in self._ENTRY]
+        per_job = [cat(k, dt, w) for k, dt, w in self._JOB]
+        q, t, s = cat("q", np.float64, 4), cat("t", np.float64, 3), cat("s", np.float64, 1)
+        n_in = np.zeros(max(J, 1), np.int32)
+        status = np.zeros(max(int(start[-1]), 1), np.uint8)
+        code = self._lib.omv_optimize_sim3(self._h, J, _lib.ptr(start), *[_lib.ptr(a) for a in entry + per_job],
+                                           _lib.ptr(q), _lib.ptr(t), _lib.ptr(s), _lib.ptr(n_in), _lib.ptr(status),
+                                           self._stream())
+        if code == _lib.OMV_OK:
+            self.n = n
+        return code, n_in[:J], q, t, s.reshape(-1), [status[start[j]:start[j + 1]] for j in range(J)]
+
+    def debug(self, j):
+        """The library's test hook for job j of the last run: dict(H [7][7], b, chi2, lambda_init, x, e12, e21 [N][2],
+        iterations, trials, max_trials [2])."""
+        N = int(self.n[j])
+        o = dict(H=np.zeros((7, 7)), b=np.zeros(7), chi2=np.zeros(1), lambda_init=np.zeros(1), x=np.zeros(7),
+                 e12=np.zeros((max(N, 1), 2)), e21=np.zeros((max(N, 1), 2)), iterations=np.zeros(2, np.int32),
+                 trials=np.zeros(2, np.int32), max_trials=np.zeros(2, np.int32))
+        _lib.check(self._lib.omv_optimize_sim3_debug(self._h, int(j), *[_lib.ptr(v) for v in o.values()], self._stream()),
+                   "omv_optimize_sim3_debug")
+        o["chi2"], o["lambda_init"] = float(o["chi2"][0]), float(o["lambda_init"][0])
+        o["e12"], o["e21"] = o["e12"][:N], o["e21"][:N]
+        return o
+
+
+def OptimizeSim3(jobs, vpMatches1=None, optimizer=None):
+    """Optimizer::OptimizeSim3 for every job of `jobs` in one device call.  Returns per job (nIn, g2oS12, matches):
+    g2oS12 = dict(q, t, s) -- the input where the reference returns 0 before writing it back -- and matches, the
+    surviving part of vpMatches1: vpMatches1[j] (one bool array of length vpMatches1.size() per job; default: true at
+    the job's index1 in an array just long enough) with the entries the reference nulls set false.  mAcumHessian is
+    the zero 7 x 7 the reference leaves and is not returned.  `optimizer`: a Sim3Optimizer to reuse."""
+    jobs = list(jobs)
+    n_entries = sum(len(np.asarray(j["Xw1"]).reshape(-1, 3)) for j in jobs)
+    opt = optimizer if optimizer is not None else Sim3Optimizer(max(len(jobs), 1), n_entries)
+    code, n_in, q, t, s, status = opt.run(jobs)
+    _lib.check(code, "omv_optimize_sim3")
+    out = []
+    for j, job in enumerate(jobs):
+        idx = np.asarray(job["index1"], np.int64).reshape(-1)
+        if vpMatches1 is not None:
+            m = np.array(vpMatches1[j], bool)
+        else:
+            m = np.zeros(int(idx.max()) + 1 if len(idx) else 0, bool)
+            m[idx] = True
+        m[idx[status[j] >= OPTSIM3_REMOVED_1]] = False
+        out.append((int(n_in[j]), dict(q=q[j].copy(), t=t[j].copy(), s=float(s[j])), m))
+    return out
