@@ -1095,6 +1095,73 @@ omv_status omv_optimize_sim3_debug(omv_optsim3 *h, int job, double *H, double *b
                                    double *x, double *e12, double *e21, int32_t *iterations, int32_t *trials,
                                    int32_t *max_trials, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * KeyFrameDatabase (src/KeyFrameDatabase.cc): add / erase / clear / clearMap, DetectNBestCandidates (:581-713, called at
+ * src/LoopClosing.cc:562) and DetectRelocalizationCandidates (:715-828, called at src/Tracking.cc:3551) on the device,
+ * for a batch of queries, bit-exact.  L1 scoring only (omv_vocab.scoring == 0, what ORBvoc uses): any other `scoring`
+ * is OMV_ERR_ARG.
+ *
+ * The database is a table of BowVectors by slot; the caller chooses a keyframe's slot in [0, max_kf) and keeps the
+ * KeyFrame* <-> slot map.  There is no inverted file: lKFsSharingWords is the occupied slots that share a word with the
+ * query, in ascending (smallest shared word, sequence number of the slot's latest add), which is the order the
+ * reference's walk over mvInvertedFile produces.  Per slot and per mode the handle keeps the reference's persistent
+ * pair (mnPlaceRecognitionQuery, mPlaceRecognitionScore) / (mnRelocQuery, mRelocScore); add resets both to (0, 0), a
+ * fresh KeyFrame (the reference never initialises mRelocScore; it is 0 here), with no neighbours and flags 0; erase
+ * leaves the state in place (a keyframe out of the database is still a neighbour with its stored score).  A keyframe
+ * is listed iff it shares a word, is not in the query's connected set (n_best only) and its stored id differs from the
+ * query's; listing stores the id.  The neighbour loop adds the STORED score of every neighbour whose stored id is the
+ * query's, stale or not.  So a query with id 0 lists no fresh keyframe, and a repeated id lists nothing again.
+ * The queries of one call behave exactly as the same queries made one per call, in order.
+ *
+ * What stays with the caller and arrives as arrays: GetConnectedKeyFrames() of the query, GetBestCovisibilityKeyFrames(10)
+ * of the database keyframes, isBad(), the map id and Map::IsBad().  One stream at a time per handle.  add, erase, clear,
+ * clear_map, set_neighbours and set_flags synchronise `stream`; the two detect calls do not.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct omv_kfdb omv_kfdb;
+
+omv_status omv_kfdb_create(int scoring, int max_kf, int max_bow, int max_queries, int max_query_bow, omv_kfdb **out);
+omv_status omv_kfdb_destroy(omv_kfdb *h);
+
+/* KeyFrameDatabase::add for n keyframes.  slot, map_id [n]: host.  bow_word, bow_value [n][stride], bow_n [n]: device,
+ * as omv_bow_transform leaves them (word ids ascending).  Sequence numbers follow call order, then array order.
+ * OMV_ERR_ARG: a slot out of range, occupied or named twice, bow_n outside [0, stride]; OMV_ERR_CAPACITY: bow_n >
+ * max_bow.  Nothing is changed on an error. */
+omv_status omv_kfdb_add(omv_kfdb *h, int n, const int32_t *slot, const int32_t *map_id, const int32_t *bow_word,
+                        const double *bow_value, const int32_t *bow_n, int stride, void *stream);
+/* erase (slot [n] host; erasing an empty slot is a no-op, as in the reference), clear, clearMap. */
+omv_status omv_kfdb_erase(omv_kfdb *h, int n, const int32_t *slot, void *stream);
+omv_status omv_kfdb_clear(omv_kfdb *h, void *stream);
+omv_status omv_kfdb_clear_map(omv_kfdb *h, int map_id, void *stream);
+/* GetBestCovisibilityKeyFrames(10) of the named slots: neigh host [n][10] slots in the reference's order, -1 padded (a
+ * keyframe that never had a slot is -1).  flags host [n]: bit 0 isBad(), bit 1 GetMap()->IsBad(). */
+omv_status omv_kfdb_set_neighbours(omv_kfdb *h, int n, const int32_t *slot, const int32_t *neigh, void *stream);
+omv_status omv_kfdb_set_flags(omv_kfdb *h, int n, const int32_t *slot, const uint8_t *flags, void *stream);
+
+/* DetectNBestCandidates for n_q queries, in order.  Host: query_id [n_q] pKF->mnId, query_map [n_q], conn_start
+ * [n_q + 1] (conn_start[0] = 0, ascending) and conn_slot: the slots of GetConnectedKeyFrames() that are in the
+ * database.  Device: q_bow_word / q_bow_value [n_q][stride], q_bow_n [n_q], and the outputs loop_out / merge_out
+ * [n_q][n_candidates] (slots in the reference's order, -1 beyond the count) and n_loop / n_merge [n_q].  A q_bow_n
+ * outside [0, min(stride, max_query_bow)] gives that query the counts -1.  Asynchronous. */
+omv_status omv_kfdb_detect_n_best(omv_kfdb *h, int n_q, const int64_t *query_id, const int32_t *query_map,
+                                  const int32_t *conn_start, const int32_t *conn_slot, const int32_t *q_bow_word,
+                                  const double *q_bow_value, const int32_t *q_bow_n, int stride, int n_candidates,
+                                  int32_t *loop_out, int32_t *n_loop, int32_t *merge_out, int32_t *n_merge,
+                                  void *stream);
+/* DetectRelocalizationCandidates: frame_id [n_q] F->mnId and map_id [n_q] host; cand_out device [n_q][max_kf] in
+ * lAccScoreAndMatch order, n_cand [n_q].  Asynchronous. */
+omv_status omv_kfdb_detect_reloc(omv_kfdb *h, int n_q, const int64_t *frame_id, const int32_t *map_id,
+                                 const int32_t *q_bow_word, const double *q_bow_value, const int32_t *q_bow_n,
+                                 int stride, int32_t *cand_out, int32_t *n_cand, void *stream);
+/* Test hook: query `query` of the last detect call, host outputs, any may be NULL; arrays hold up to max_kf entries.
+ * maxCommonWords, minCommonWords (0 when nothing is listed); lKFsSharingWords as list_slot / list_words [n_list];
+ * lScoreAndMatch as scored_slot [n_scored] with the double score before the cast and the float si; lAccScoreAndMatch
+ * in its final order (sorted for n_best, as built for reloc) as acc_bits (the float's bits) / acc_best [n_scored].
+ * Synchronous. */
+omv_status omv_kfdb_debug(omv_kfdb *h, int query, int32_t *max_common_words, int32_t *min_common_words,
+                          int32_t *n_list, int32_t *list_slot, int32_t *list_words, int32_t *n_scored,
+                          int32_t *scored_slot, double *score, float *si, uint32_t *acc_bits, int32_t *acc_best,
+                          void *stream);
+
 /* ---- Test hooks (no reference counterpart): the device linear-algebra routines on plain device arrays ----
  * Each launches the product's own instantiation of the routine, one workgroup per problem (`batch` problems, on
  * `stream`, not synchronised).  Every pointer is device memory. */

@@ -47,6 +47,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -1474,6 +1475,138 @@ inline int OptimizeSim3(const OptimizeSim3Input &in, std::vector<bool> &vpMatche
     if (status) status->assign(st.begin(), st.begin() + N);
     return n_in;
 }
+
+// ---- KeyFrameDatabase ---------------------------------------------------------------------------------------
+// KeyFrameDatabase (src/KeyFrameDatabase.cc) over an omv_kfdb handle and a KeyFrame* <-> slot map.  KF is the caller's
+// keyframe type; the adapter never dereferences a KF*.  BowVectors are device rows as omv_bow_transform leaves them.
+// What the reference reads from the graph is handed over per keyframe by refresh(): GetBestCovisibilityKeyFrames(10),
+// isBad(), GetMap()->IsBad().  A keyframe without a slot (never added, or erased: erase frees the slot) is no
+// neighbour.  Calls synchronise the stream; the handle keeps the reference's per-keyframe query ids and scores.
+template <class KF>
+struct KfdbKeyFrameState {
+    KF *kf = nullptr;
+    std::vector<KF *> best_covisibles;   // GetBestCovisibilityKeyFrames(10), in its order
+    bool bad = false, map_bad = false;   // isBad(), GetMap()->IsBad()
+};
+
+template <class KF>
+struct KfdbQuery {
+    long unsigned int mnId = 0;          // pKF->mnId / F->mnId
+    int map_id = 0;                      // pKF->GetMap() / pMap
+    std::vector<KF *> connected;         // pKF->GetConnectedKeyFrames() (DetectNBestCandidates only)
+    const int32_t *bow_word = nullptr;   // device: mBowVec, bow_n ascending word ids and their values
+    const double *bow_value = nullptr;
+    const int32_t *bow_n = nullptr;
+    int stride = 0;                      // the row length of bow_word / bow_value
+};
+
+template <class KF>
+class KeyFrameDatabase {
+public:
+    KeyFrameDatabase(int max_kf, int max_bow, int max_query_bow, hipStream_t stream = nullptr)
+        : max_kf_(max_kf), stream_(stream), slot_kf_(max_kf, nullptr), slot_map_(max_kf, 0) {
+        check(omv_kfdb_create(0, max_kf, max_bow, 1, max_query_bow, &h_), "omv_kfdb_create");
+        for (int s = max_kf - 1; s >= 0; s--) free_.push_back(s);
+        out_.resize((size_t)2 * max_kf + 2);
+    }
+    KeyFrameDatabase(const KeyFrameDatabase &) = delete;
+    KeyFrameDatabase &operator=(const KeyFrameDatabase &) = delete;
+    ~KeyFrameDatabase() { (void)omv_kfdb_destroy(h_); }
+
+    // add(pKF): bow_word / bow_value point at the keyframe's row, bow_n at its count (device).
+    void add(KF *pKF, int map_id, const int32_t *bow_word, const double *bow_value, const int32_t *bow_n, int stride) {
+        if (slot_of(pKF) >= 0) throw Error("KeyFrameDatabase::add: keyframe already in the database");
+        if (free_.empty()) throw Error("KeyFrameDatabase::add: no free slot");
+        const int32_t s = free_.back(), m = map_id;
+        check(omv_kfdb_add(h_, 1, &s, &m, bow_word, bow_value, bow_n, stride, stream_), "omv_kfdb_add");
+        free_.pop_back();
+        slot_kf_[s] = pKF, slot_map_[s] = map_id, slot_[pKF] = s;
+    }
+    void erase(KF *pKF) {
+        const int32_t s = slot_of(pKF);
+        if (s < 0) return;
+        check(omv_kfdb_erase(h_, 1, &s, stream_), "omv_kfdb_erase");
+        slot_.erase(pKF), slot_kf_[s] = nullptr, free_.push_back(s);
+    }
+    void clear() {
+        check(omv_kfdb_clear(h_, stream_), "omv_kfdb_clear");
+        for (int s = 0; s < max_kf_; s++)
+            if (slot_kf_[s]) slot_.erase(slot_kf_[s]), slot_kf_[s] = nullptr, free_.push_back(s);
+    }
+    void clearMap(int map_id) {
+        check(omv_kfdb_clear_map(h_, map_id, stream_), "omv_kfdb_clear_map");
+        for (int s = 0; s < max_kf_; s++)
+            if (slot_kf_[s] && slot_map_[s] == map_id) slot_.erase(slot_kf_[s]), slot_kf_[s] = nullptr, free_.push_back(s);
+    }
+    // The neighbours and flags of the named keyframes as they are now (those not in the database are skipped).
+    void refresh(const std::vector<KfdbKeyFrameState<KF>> &kfs) {
+        std::vector<int32_t> slot, neigh;
+        std::vector<uint8_t> flags;
+        for (const auto &k : kfs) {
+            const int s = slot_of(k.kf);
+            if (s < 0) continue;
+            slot.push_back(s);
+            flags.push_back((uint8_t)((k.bad ? 1 : 0) | (k.map_bad ? 2 : 0)));
+            for (size_t i = 0; i < 10; i++)
+                neigh.push_back(i < k.best_covisibles.size() ? slot_of(k.best_covisibles[i]) : -1);
+        }
+        const int n = (int)slot.size();
+        check(omv_kfdb_set_neighbours(h_, n, slot.data(), neigh.data(), stream_), "omv_kfdb_set_neighbours");
+        check(omv_kfdb_set_flags(h_, n, slot.data(), flags.data(), stream_), "omv_kfdb_set_flags");
+    }
+    // void DetectNBestCandidates(KeyFrame *pKF, vector<KeyFrame*> &vpLoopCand, vector<KeyFrame*> &vpMergeCand, int n)
+    void DetectNBestCandidates(const KfdbQuery<KF> &q, std::vector<KF *> &vpLoopCand, std::vector<KF *> &vpMergeCand,
+                               int nNumCandidates) {
+        if (nNumCandidates < 0 || nNumCandidates > max_kf_) throw Error("DetectNBestCandidates: nNumCandidates");
+        std::vector<int32_t> conn;
+        for (KF *k : q.connected) {
+            const int s = slot_of(k);
+            if (s >= 0) conn.push_back(s);
+        }
+        const int64_t id = (int64_t)q.mnId;
+        const int32_t map = q.map_id, cstart[2] = {0, (int32_t)conn.size()};
+        int32_t *d = out_.p;   // loop [n], merge [n], n_loop, n_merge
+        const int n = nNumCandidates;
+        check(omv_kfdb_detect_n_best(h_, 1, &id, &map, cstart, conn.data(), q.bow_word, q.bow_value, q.bow_n, q.stride, n,
+                                     d, d + 2 * n, d + n, d + 2 * n + 1, stream_), "omv_kfdb_detect_n_best");
+        std::vector<int32_t> host((size_t)2 * n + 2);
+        out_.download(host.data(), host.size(), stream_);
+        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        if (host[2 * n] < 0) throw Error("DetectNBestCandidates: the query's BowVector exceeds max_query_bow");
+        for (int i = 0; i < host[2 * n]; i++) vpLoopCand.push_back(slot_kf_[host[i]]);
+        for (int i = 0; i < host[2 * n + 1]; i++) vpMergeCand.push_back(slot_kf_[host[n + i]]);
+    }
+    // vector<KeyFrame*> DetectRelocalizationCandidates(Frame *F, Map *pMap)
+    std::vector<KF *> DetectRelocalizationCandidates(const KfdbQuery<KF> &q) {
+        const int64_t id = (int64_t)q.mnId;
+        const int32_t map = q.map_id;
+        int32_t *d = out_.p;   // cand [max_kf], n_cand
+        check(omv_kfdb_detect_reloc(h_, 1, &id, &map, q.bow_word, q.bow_value, q.bow_n, q.stride, d, d + max_kf_, stream_),
+              "omv_kfdb_detect_reloc");
+        std::vector<int32_t> host((size_t)max_kf_ + 1);
+        out_.download(host.data(), host.size(), stream_);
+        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        if (host[max_kf_] < 0) throw Error("DetectRelocalizationCandidates: the BowVector exceeds max_query_bow");
+        std::vector<KF *> vpRelocCandidates;
+        for (int i = 0; i < host[max_kf_]; i++) vpRelocCandidates.push_back(slot_kf_[host[i]]);
+        return vpRelocCandidates;
+    }
+    int slot_of(const KF *pKF) const {
+        const auto it = slot_.find(pKF);
+        return it == slot_.end() ? -1 : it->second;
+    }
+    omv_kfdb *handle() const { return h_; }
+
+private:
+    omv_kfdb *h_ = nullptr;
+    int max_kf_;
+    hipStream_t stream_;
+    std::vector<KF *> slot_kf_;
+    std::vector<int> slot_map_;
+    std::unordered_map<const KF *, int> slot_;
+    std::vector<int32_t> free_;
+    DeviceArray<int32_t> out_;
+};
 
 }  // namespace omv_adapt
 

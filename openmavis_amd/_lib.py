@@ -342,6 +342,17 @@ SIGNATURES = {
     "omv_optimize_sim3_destroy": (_I, [_VP]),
     "omv_optimize_sim3": (_I, [_VP, _I] + [_VP] * 22),
     "omv_optimize_sim3_debug": (_I, [_VP, _I] + [_VP] * 11),
+    "omv_kfdb_create": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(_VP)]),
+    "omv_kfdb_destroy": (_I, [_VP]),
+    "omv_kfdb_add": (_I, [_VP, _I] + [_VP] * 5 + [_I, _VP]),
+    "omv_kfdb_erase": (_I, [_VP, _I, _VP, _VP]),
+    "omv_kfdb_clear": (_I, [_VP, _VP]),
+    "omv_kfdb_clear_map": (_I, [_VP, _I, _VP]),
+    "omv_kfdb_set_neighbours": (_I, [_VP, _I, _VP, _VP, _VP]),
+    "omv_kfdb_set_flags": (_I, [_VP, _I, _VP, _VP, _VP]),
+    "omv_kfdb_detect_n_best": (_I, [_VP, _I] + [_VP] * 7 + [_I, _I] + [_VP] * 5),
+    "omv_kfdb_detect_reloc": (_I, [_VP, _I] + [_VP] * 5 + [_I] + [_VP] * 3),
+    "omv_kfdb_debug": (_I, [_VP, _I] + [_VP] * 12),
 }
 
 _lib = None
