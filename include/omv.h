@@ -1224,6 +1224,13 @@ omv_status omv_selftest_math(int fn, int64_t n, const void *a, const void *b, co
 omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda, double *S, double *rhs, double *x,
                                int32_t *fail, int32_t *plan, int plan_cap);
 
+/* Test hooks on the library's memory ownership (process-wide).  live_allocations: the device, pinned-host and
+ * stream-ordered allocations the library holds now (every handle's buffers and the per-call workspaces).
+ * fail_allocation: the nth next allocation of the library (1-based) fails without a HIP call, as if the device were
+ * out of memory, and the hook disarms itself; 0 disarms, nth < 0 is OMV_ERR_ARG. */
+omv_status omv_debug_live_allocations(int64_t *n);
+omv_status omv_debug_fail_allocation(int nth);
+
 #ifdef __cplusplus
 }
 #endif

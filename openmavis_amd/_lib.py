@@ -353,6 +353,8 @@ SIGNATURES = {
     "omv_kfdb_detect_n_best": (_I, [_VP, _I] + [_VP] * 7 + [_I, _I] + [_VP] * 5),
     "omv_kfdb_detect_reloc": (_I, [_VP, _I] + [_VP] * 5 + [_I] + [_VP] * 3),
     "omv_kfdb_debug": (_I, [_VP, _I] + [_VP] * 12),
+    "omv_debug_live_allocations": (_I, [ctypes.POINTER(ctypes.c_int64)]),
+    "omv_debug_fail_allocation": (_I, [_I]),
 }
 
 _lib = None

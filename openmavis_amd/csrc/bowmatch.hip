@@ -526,7 +526,8 @@ omv_status omv_matcher_search_by_bow(omv_matcher *m, int n_jobs, const omv_bow_j
     char *d_buf = nullptr;
     const int rec_words = mode == OMV_BOW_KF_FRAME ? BowCfg<OMV_BOW_KF_FRAME>::rec : BowCfg<OMV_BOW_KF_KF>::rec;
     const int top = mode == OMV_BOW_KF_FRAME ? BowCfg<OMV_BOW_KF_FRAME>::top : BowCfg<OMV_BOW_KF_KF>::top;
-    HIP_OK(hipMallocAsync((void **)&d_buf, job_bytes + off_bytes + 16 + (size_t)off[n_jobs] * rec_words * 4, st));
+    omv::DeviceArena ws;
+    if (!ws.alloc_async(&d_buf, job_bytes + off_bytes + 16 + (size_t)off[n_jobs] * rec_words * 4, st)) return OMV_ERR_HIP;
     omv_bow_job *d_jobs = (omv_bow_job *)d_buf;
     int *d_off = (int *)(d_buf + job_bytes);
     int *d_err = (int *)(d_buf + job_bytes + off_bytes);
@@ -551,7 +552,7 @@ omv_status omv_matcher_search_by_bow(omv_matcher *m, int n_jobs, const omv_bow_j
     HIP_OK(hipGetLastError());
     int h_err[2] = {0, 0};
     HIP_OK(hipMemcpyAsync(h_err, d_err, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipFreeAsync(d_buf, st));
+    HIP_OK(ws.free(&d_buf));
     HIP_OK(hipStreamSynchronize(st));
     g_bow_rescans += h_err[1];
     return h_err[0] ? (omv_status)h_err[0] : OMV_OK;

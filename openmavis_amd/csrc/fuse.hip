@@ -76,6 +76,7 @@ struct Walk {
     // device scratch
     int32_t *d_i32 = nullptr;
     size_t d_cap = 0;
+    omv::DeviceArena d_mem;   // owns d_i32, in the order of `st`
 
     int *kfmp(int kf) { return g->kf_mps + (size_t)kf * C * kp_cap; }
     int n_of(int kf) const {
@@ -154,11 +155,7 @@ struct Walk {
 
     omv_status scratch(size_t n_i32) {
         if (d_cap >= n_i32) return OMV_OK;
-        if (d_i32) HIP_OK(hipFreeAsync(d_i32, st));
-        d_i32 = nullptr;
-        d_cap = std::max(n_i32, 2 * d_cap);
-        HIP_OK(hipMallocAsync((void **)&d_i32, sizeof(int32_t) * d_cap, st));
-        return OMV_OK;
+        return d_mem.grow_async(&d_i32, &d_cap, std::max(n_i32, 2 * d_cap), st) ? OMV_OK : OMV_ERR_HIP;
     }
     // the pending descriptor recomputations, on the device, into the map-point table
     omv_status flush() {
@@ -349,7 +346,7 @@ extern "C" omv_status omv_search_in_neighbors_fuse(omv_matcher *m, const omv_fra
         for (size_t j = 0; j < jobs.size(); ++j) n_fused[n_targets * C + (int)j] = nf[j];
     }
     OMV_OK_OR_RETURN(w.flush());   // the last survivors' descriptors
-    if (w.d_i32) HIP_OK(hipFreeAsync(w.d_i32, w.st));
+    HIP_OK(w.d_mem.free(&w.d_i32));
     HIP_OK(hipStreamSynchronize(w.st));
     // final observations
     int rows = 0;

@@ -422,14 +422,11 @@ struct omv_kfdb {
     uint64_t next_seq = 0;
     int64_t next_stamp = 1;
     int last_nq = 0, last_hi = 0;
+    omv::DeviceArena mem;   // owns the table, the per-call and staging buffers and `pin`
+    ~omv_kfdb() { if (pin_free) (void)hipEventDestroy(pin_free); }
 };
 
 namespace {
-
-template <class T>
-bool dalloc(T **p, size_t count) {
-    return hipMalloc((void **)p, (count ? count : 1) * sizeof(T)) == hipSuccess;
-}
 
 int high_slot(const omv_kfdb *h) {   // one past the highest occupied slot
     int hi = 0;
@@ -511,20 +508,7 @@ omv_status detect(omv_kfdb *h, int mode, int n_q, const int64_t *query_id, const
 extern "C" {
 
 omv_status omv_kfdb_destroy(omv_kfdb *h) {
-    if (!h) return OMV_OK;
-    Table &t = h->t;
-    (void)hipFree(t.word), (void)hipFree(t.value), (void)hipFree(t.n), (void)hipFree(t.seq), (void)hipFree(t.occ);
-    (void)hipFree(t.map), (void)hipFree(t.neigh), (void)hipFree(t.flags);
-    for (int m = 0; m < 2; ++m) (void)hipFree(t.st_query[m]), (void)hipFree(t.st_score[m]);
-    (void)hipFree(h->words), (void)hipFree(h->first), (void)hipFree(h->score), (void)hipFree(h->conn_stamp);
-    (void)hipFree(h->add_stamp), (void)hipFree(h->gkey), (void)hipFree(h->gval), (void)hipFree(h->tmp_best);
-    (void)hipFree(h->tmp_bits), (void)hipFree(h->acc_bits), (void)hipFree(h->cls), (void)hipFree(h->q_info);
-    (void)hipFree(h->list_slot), (void)hipFree(h->sc_slot), (void)hipFree(h->acc_best), (void)hipFree(h->sc_si);
-    (void)hipFree(h->d_qid), (void)hipFree(h->d_qmap), (void)hipFree(h->d_cstart), (void)hipFree(h->d_cslot);
-    (void)hipFree(h->d_islot), (void)hipFree(h->d_imap), (void)hipFree(h->d_ineigh), (void)hipFree(h->d_iflags);
-    if (h->pin) (void)hipHostFree(h->pin);
-    if (h->pin_free) (void)hipEventDestroy(h->pin_free);
-    delete h;
+    delete h;   // NULL: nothing to do, OMV_OK
     return OMV_OK;
 }
 
@@ -534,27 +518,29 @@ omv_status omv_kfdb_create(int scoring, int max_kf, int max_bow, int max_queries
     if ((long long)max_kf * kNeigh > 0x7fffffffLL) return OMV_ERR_ARG;
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) return OMV_ERR_NO_DEVICE;
-    omv_kfdb *h = new (std::nothrow) omv_kfdb;
+    std::unique_ptr<omv_kfdb> h(new (std::nothrow) omv_kfdb);
     if (!h) return OMV_ERR_HIP;
     Table &t = h->t;
+    omv::DeviceArena &mem = h->mem;
     t.max_kf = max_kf, t.max_bow = max_bow, h->max_q = max_queries, h->max_qbow = max_query_bow;
     while (h->P_cap < max_kf) h->P_cap <<= 1;
     h->conn_cap = (size_t)max_queries * max_kf;
     const size_t mk = max_kf, tb = mk * max_bow, qk = (size_t)max_queries * mk;
     h->pin_bytes = 8 * (size_t)max_queries + 4 * (size_t)max_queries + 4 * ((size_t)max_queries + 1) + 4 * h->conn_cap;
-    bool ok = dalloc(&t.word, tb) && dalloc(&t.value, tb) && dalloc(&t.n, mk) && dalloc(&t.seq, mk) &&
-              dalloc(&t.occ, mk) && dalloc(&t.map, mk) && dalloc(&t.neigh, mk * kNeigh) && dalloc(&t.flags, mk) &&
-              dalloc(&t.st_query[0], mk) && dalloc(&t.st_query[1], mk) && dalloc(&t.st_score[0], mk) &&
-              dalloc(&t.st_score[1], mk) && dalloc(&h->words, qk) && dalloc(&h->first, qk) && dalloc(&h->score, qk) &&
-              dalloc(&h->conn_stamp, mk) && dalloc(&h->add_stamp, mk) && dalloc(&h->gkey, (size_t)h->P_cap) &&
-              dalloc(&h->gval, (size_t)h->P_cap) && dalloc(&h->tmp_best, mk) && dalloc(&h->tmp_bits, mk) &&
-              dalloc(&h->acc_bits, qk) && dalloc(&h->cls, mk) && dalloc(&h->q_info, (size_t)4 * max_queries) &&
-              dalloc(&h->list_slot, qk) && dalloc(&h->sc_slot, qk) && dalloc(&h->acc_best, qk) &&
-              dalloc(&h->sc_si, qk) && dalloc(&h->d_qid, (size_t)max_queries) &&
-              dalloc(&h->d_qmap, (size_t)max_queries) && dalloc(&h->d_cstart, (size_t)max_queries + 1) &&
-              dalloc(&h->d_cslot, h->conn_cap) && dalloc(&h->d_islot, mk) && dalloc(&h->d_imap, mk) &&
-              dalloc(&h->d_ineigh, mk * kNeigh) && dalloc(&h->d_iflags, mk) &&
-              hipHostMalloc((void **)&h->pin, h->pin_bytes, hipHostMallocDefault) == hipSuccess &&
+    bool ok = mem.alloc(&t.word, tb) && mem.alloc(&t.value, tb) && mem.alloc(&t.n, mk) && mem.alloc(&t.seq, mk) &&
+              mem.alloc(&t.occ, mk) && mem.alloc(&t.map, mk) && mem.alloc(&t.neigh, mk * kNeigh) &&
+              mem.alloc(&t.flags, mk) && mem.alloc(&t.st_query[0], mk) && mem.alloc(&t.st_query[1], mk) &&
+              mem.alloc(&t.st_score[0], mk) && mem.alloc(&t.st_score[1], mk) && mem.alloc(&h->words, qk) &&
+              mem.alloc(&h->first, qk) && mem.alloc(&h->score, qk) && mem.alloc(&h->conn_stamp, mk) &&
+              mem.alloc(&h->add_stamp, mk) && mem.alloc(&h->gkey, (size_t)h->P_cap) &&
+              mem.alloc(&h->gval, (size_t)h->P_cap) && mem.alloc(&h->tmp_best, mk) && mem.alloc(&h->tmp_bits, mk) &&
+              mem.alloc(&h->acc_bits, qk) && mem.alloc(&h->cls, mk) && mem.alloc(&h->q_info, (size_t)4 * max_queries) &&
+              mem.alloc(&h->list_slot, qk) && mem.alloc(&h->sc_slot, qk) && mem.alloc(&h->acc_best, qk) &&
+              mem.alloc(&h->sc_si, qk) && mem.alloc(&h->d_qid, (size_t)max_queries) &&
+              mem.alloc(&h->d_qmap, (size_t)max_queries) && mem.alloc(&h->d_cstart, (size_t)max_queries + 1) &&
+              mem.alloc(&h->d_cslot, h->conn_cap) && mem.alloc(&h->d_islot, mk) && mem.alloc(&h->d_imap, mk) &&
+              mem.alloc(&h->d_ineigh, mk * kNeigh) && mem.alloc(&h->d_iflags, mk) &&
+              mem.alloc_pinned(&h->pin, h->pin_bytes) &&
               hipEventCreateWithFlags(&h->pin_free, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMemset(t.occ, 0, mk) == hipSuccess && hipMemset(t.n, 0, mk * 4) == hipSuccess &&
          hipMemset(t.seq, 0, mk * 4) == hipSuccess && hipMemset(t.map, 0, mk * 4) == hipSuccess &&
@@ -570,11 +556,10 @@ omv_status omv_kfdb_create(int scoring, int max_kf, int max_bow, int max_queries
                                  kLdsSortMax * 12) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        omv_kfdb_destroy(h);
         return OMV_ERR_HIP;
     }
     h->h_occ.assign(mk, 0), h->h_map.assign(mk, 0);
-    *out = h;
+    *out = h.release();
     return OMV_OK;
 }
 

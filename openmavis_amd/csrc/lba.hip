@@ -1768,20 +1768,14 @@ std::vector<int> plan_order(int nb, const std::vector<uint8_t> &adj, int max_slo
     return best;
 }
 
-template <typename T>
-T *dalloc(std::vector<void *> &owned, size_t n) {
-    void *p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) return nullptr;
-    owned.push_back(p);
-    return (T *)p;
-}
-
 }  // namespace
 
 // =============================================================================================
 struct omv_lba {
     int max_kf, max_cams, max_pts, max_mono, max_imu;
-    std::vector<void *> owned;   // device allocations of the current problem
+    omv::DeviceArena mem;    // the handle's own blocks: h_out, h_ctl, d_ctl
+    omv::DeviceArena prob;   // the current problem's device buffers and h_stage
+    ~omv_lba();
     // problem
     Rig rig{};
     int n_kf = 0, n_opt = 0, n_pts = 0, n_mono = 0, n_imu = 0, n_red = 0, n_slots = 0;
@@ -1844,7 +1838,7 @@ struct omv_lba {
     int n_mono_all = 0, n_stereo_all = 0;   // caller edge counts (perm_edge >= n_mono_all: EdgeStereo)
     double *d_err3 = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[8];
+    hipEvent_t ev[8] = {};
     double stage_ms[4] = {0, 0, 0, 0};
     int last_trials = 0;
     int host_syncs = 0;        // host waits of the last optimize()'s LM loop (the device driver: one per batch)
@@ -1852,21 +1846,22 @@ struct omv_lba {
 };
 
 static void free_problem(omv_lba *h) {
-    for (void *p : h->owned) (void)hipFree(p);
-    h->owned.clear();
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
+    h->prob.reset();
     h->h_stage = nullptr, h->stage_bytes = 0;
-    if (h->step_exec) (void)hipGraphExecDestroy(h->step_exec);
-    if (h->step_graph) (void)hipGraphDestroy(h->step_graph);
-    if (h->step4_exec) (void)hipGraphExecDestroy(h->step4_exec);
-    if (h->step4_graph) (void)hipGraphDestroy(h->step4_graph);
-    h->step_exec = nullptr, h->step_graph = nullptr;   // the captured step holds the old problem's pointers
-    h->step4_exec = nullptr, h->step4_graph = nullptr;
-    for (int q = 0; q < 2; ++q) {
-        if (h->step4e_exec[q]) (void)hipGraphExecDestroy(h->step4e_exec[q]);
-        if (h->step4e_graph[q]) (void)hipGraphDestroy(h->step4e_graph[q]);
-        h->step4e_exec[q] = nullptr, h->step4e_graph[q] = nullptr;
+    hipGraphExec_t *execs[] = {&h->step_exec, &h->step4_exec, &h->step4e_exec[0], &h->step4e_exec[1]};
+    hipGraph_t *graphs[] = {&h->step_graph, &h->step4_graph, &h->step4e_graph[0], &h->step4e_graph[1]};
+    for (int q = 0; q < 4; ++q) {   // the captured steps hold the old problem's pointers
+        if (*execs[q]) (void)hipGraphExecDestroy(*execs[q]);
+        if (*graphs[q]) (void)hipGraphDestroy(*graphs[q]);
+        *execs[q] = nullptr, *graphs[q] = nullptr;
     }
+}
+
+omv_lba::~omv_lba() {   // `mem` frees h_out, h_ctl and d_ctl after this body
+    free_problem(this);
+    for (auto &e : ev)
+        if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 extern "C" {
@@ -1876,13 +1871,12 @@ omv_status omv_lba_create(int max_kf, int max_cams, int max_pts, int max_mono, i
         return OMV_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return OMV_ERR_NO_DEVICE;
-    omv_lba *h = new omv_lba();
+    auto h = std::make_unique<omv_lba>();
     h->max_kf = max_kf, h->max_cams = max_cams, h->max_pts = max_pts, h->max_mono = max_mono, h->max_imu = max_imu;
     HIP_OK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     for (auto &e : h->ev) HIP_OK(hipEventCreate(&e));
-    HIP_OK(hipHostMalloc((void **)&h->h_out, 4 * sizeof(double), hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void **)&h->h_ctl, sizeof(LmCtl), hipHostMallocDefault));
-    HIP_OK(hipMalloc((void **)&h->d_ctl, sizeof(LmCtl)));
+    if (!h->mem.alloc_pinned(&h->h_out, 4) || !h->mem.alloc_pinned(&h->h_ctl, 1) || !h->mem.alloc(&h->d_ctl, 1))
+        return OMV_ERR_HIP;
     // the reduced-system factorisation stages its nonzero blocks in up to 150 KB of LDS
     h->lds_ok = hipFuncSetAttribute((const void *)ldlt_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)kLdltLds) == hipSuccess &&
@@ -1892,31 +1886,15 @@ omv_status omv_lba_create(int max_kf, int max_cams, int max_pts, int max_mono, i
     if (hipFuncSetAttribute((const void *)build_all_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLds) !=
             hipSuccess ||
         hipFuncSetAttribute((const void *)build_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLds) !=
-            hipSuccess) {
-        delete h;
+            hipSuccess)
         return OMV_ERR_HIP;
-    }
     (void)hipGetLastError();
-    *out = h;
+    *out = h.release();
     return OMV_OK;
 }
 
 omv_status omv_lba_destroy(omv_lba *h) {
     if (!h) return OMV_ERR_ARG;
-    free_problem(h);
-    for (auto &e : h->ev) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->h_out) (void)hipHostFree(h->h_out);
-    if (h->h_ctl) (void)hipHostFree(h->h_ctl);
-    if (h->d_ctl) (void)hipFree(h->d_ctl);
-    if (h->step_exec) (void)hipGraphExecDestroy(h->step_exec);
-    if (h->step_graph) (void)hipGraphDestroy(h->step_graph);
-    if (h->step4_exec) (void)hipGraphExecDestroy(h->step4_exec);
-    if (h->step4_graph) (void)hipGraphDestroy(h->step4_graph);
-    for (int q = 0; q < 2; ++q) {
-        if (h->step4e_exec[q]) (void)hipGraphExecDestroy(h->step4e_exec[q]);
-        if (h->step4e_graph[q]) (void)hipGraphDestroy(h->step4e_graph[q]);
-    }
     delete h;
     return OMV_OK;
 }
@@ -2293,15 +2271,21 @@ omv_status omv_lba_set_problem(omv_lba *h, const omv_lba_problem *p) {
     h->delta_imu = std::sqrt(16.92);
     h->dsqr_imu = h->delta_imu * h->delta_imu;
     // ---- device allocations + uploads
-    std::vector<void *> &ow = h->owned;
+    omv::DeviceArena &mem = h->prob;
     auto up = [&](auto *dst, const auto *src, size_t n) {
         return hipMemcpy(dst, src, n * sizeof(*src), hipMemcpyHostToDevice);
+    };
+    auto upv = [&](const auto &v) {   // a host vector's device copy; null on failure
+        using T = typename std::decay_t<decltype(v)>::value_type;
+        T *d = nullptr;
+        if (mem.alloc(&d, v.size()) && !v.empty() && up(d, v.data(), v.size()) != hipSuccess) d = nullptr;
+        return (const T *)d;
     };
     for (int b = 0; b < 3; ++b) {
         // one contiguous block per state: Rwb | twb | Rcw | tcw | vel | bg | ba | pts (one copy to read back)
         State &s = h->st[b];
-        double *blk = dalloc<double>(ow, h->state_doubles());
-        if (!blk) return OMV_ERR_HIP;
+        double *blk = nullptr;
+        if (!mem.alloc(&blk, h->state_doubles())) return OMV_ERR_HIP;
         s.Rwb = blk, s.twb = s.Rwb + 9 * K, s.Rcw = s.twb + 3 * K, s.tcw = s.Rcw + 9 * K * C;
         s.vel = s.tcw + 3 * K * C, s.bg = s.vel + 3 * K, s.ba = s.bg + 3 * K, s.pts = s.ba + 3 * K;
         HIP_OK(up(s.Rwb, p->Rwb, 9 * K));
@@ -2317,68 +2301,64 @@ omv_status omv_lba_set_problem(omv_lba *h, const omv_lba_problem *p) {
         HIP_OK(up(s.pts, pts.data(), pts.size()));
     }
     h->cur = 0;
-    int *d_e_pt = dalloc<int>(ow, E), *d_e_kf = dalloc<int>(ow, E), *d_e_cam = dalloc<int>(ow, E),
-        *d_e_slot = dalloc<int>(ow, E);
-    double *d_e_obs = dalloc<double>(ow, 2 * (size_t)E);
-    float *d_e_w = dalloc<float>(ow, E), *d_e_ur = dalloc<float>(ow, E);
-    if (!d_e_w) return OMV_ERR_HIP;
+    int *d_e_pt, *d_e_kf, *d_e_cam, *d_e_slot;
+    double *d_e_obs;
+    float *d_e_w, *d_e_ur;
+    if (!mem.alloc(&d_e_pt, E) || !mem.alloc(&d_e_kf, E) || !mem.alloc(&d_e_cam, E) || !mem.alloc(&d_e_slot, E) ||
+        !mem.alloc(&d_e_obs, 2 * (size_t)E) || !mem.alloc(&d_e_w, E) || !mem.alloc(&d_e_ur, E))
+        return OMV_ERR_HIP;
     HIP_OK(up(d_e_pt, e_pt.data(), E));
     HIP_OK(up(d_e_kf, e_kf.data(), E));
     HIP_OK(up(d_e_cam, e_cam.data(), E));
     HIP_OK(up(d_e_slot, e_slot.data(), E));
     HIP_OK(up(d_e_obs, e_obs.data(), 2 * (size_t)E));
     HIP_OK(up(d_e_w, e_w.data(), E));
-    if (!d_e_ur) return OMV_ERR_HIP;
     HIP_OK(up(d_e_ur, e_ur.data(), E));
     h->E = Edges{d_e_pt, d_e_kf, d_e_cam, d_e_slot, d_e_obs, d_e_w, d_e_ur, E};
-    int *d_pt_edge = dalloc<int>(ow, P + 1), *d_pt_slot = dalloc<int>(ow, P + 1), *d_slot_kf = dalloc<int>(ow, h->n_slots),
-        *d_slot_edge = dalloc<int>(ow, h->n_slots + 1);
-    int16_t *d_slot_lkf = dalloc<int16_t>(ow, h->n_slots);
-    double *d_lnd = dalloc<double>(ow, 12 * (size_t)P), *d_M = dalloc<double>(ow, 18 * (size_t)h->n_slots),
-           *d_rec = dalloc<double>(ow, 36 * (size_t)blk_start[n_slots]),
-           *d_rec_rhs = dalloc<double>(ow, 12 * (size_t)rhs_start[nb]);
-    if (!d_rec || !d_rec_rhs || !d_M || !d_lnd || !d_slot_lkf || !d_slot_edge) return OMV_ERR_HIP;
+    int *d_pt_edge, *d_pt_slot, *d_slot_kf, *d_slot_edge;
+    int16_t *d_slot_lkf;
+    double *d_lnd, *d_M, *d_rec, *d_rec_rhs;
+    if (!mem.alloc(&d_pt_edge, P + 1) || !mem.alloc(&d_pt_slot, P + 1) || !mem.alloc(&d_slot_kf, h->n_slots) ||
+        !mem.alloc(&d_slot_edge, h->n_slots + 1) || !mem.alloc(&d_slot_lkf, h->n_slots) ||
+        !mem.alloc(&d_lnd, 12 * (size_t)P) || !mem.alloc(&d_M, 18 * (size_t)h->n_slots) ||
+        !mem.alloc(&d_rec, 36 * (size_t)blk_start[n_slots]) || !mem.alloc(&d_rec_rhs, 12 * (size_t)rhs_start[nb]))
+        return OMV_ERR_HIP;
     HIP_OK(up(d_pt_edge, pt_edge.data(), P + 1));
     HIP_OK(up(d_pt_slot, pt_slot.data(), P + 1));
     HIP_OK(up(d_slot_edge, slot_edge.data(), h->n_slots + 1));
     if (h->n_slots > 0) HIP_OK(up(d_slot_kf, slot_kf.data(), h->n_slots));
     if (h->n_slots > 0) HIP_OK(up(d_slot_lkf, slot_lkf.data(), h->n_slots));
     {
-        auto upl = [&](const auto &v) {
-            using T = typename std::decay_t<decltype(v)>::value_type;
-            T *d = dalloc<T>(ow, v.size());
-            if (d && !v.empty() && up(d, v.data(), v.size()) != hipSuccess) d = nullptr;
-            return (const T *)d;
-        };
         Land &L = h->L;
         L = Land{d_pt_edge, d_pt_slot, d_slot_kf, d_slot_edge, d_slot_lkf, d_lnd, d_M, P,
-                 upl(grp_pt), upl(grp_w), upl(grp_tp), upl(tp),
-                 upl(grp_blk), upl(blkoff), upl(grp_kf), upl(rhsoff), d_rec, d_rec_rhs};
+                 upv(grp_pt), upv(grp_w), upv(grp_tp), upv(tp),
+                 upv(grp_blk), upv(blkoff), upv(grp_kf), upv(rhsoff), d_rec, d_rec_rhs};
         if (!L.grp_pt || !L.grp_w || !L.grp_tp || !L.tp || !L.grp_blk || !L.blkoff ||
             !L.grp_kf || !L.rhsoff)
             return OMV_ERR_HIP;
-        h->d_big = upl(big_grp);
+        h->d_big = upv(big_grp);
         std::vector<int16_t> e_lkf(E);
         for (int e = 0; e < E; ++e) e_lkf[e] = slot_lkf[e_slot[e]];
-        h->d_e_lkf = upl(e_lkf);
-        h->d_lkf_kf = upl(lkf_kf);
+        h->d_e_lkf = upv(e_lkf);
+        h->d_lkf_kf = upv(lkf_kf);
         if (!h->d_big || !h->d_e_lkf || !h->d_lkf_kf) return OMV_ERR_HIP;
     }
-    h->d_offP = dalloc<int>(ow, K), h->d_offV = dalloc<int>(ow, K), h->d_offG = dalloc<int>(ow, K),
-    h->d_offA = dalloc<int>(ow, K);
+    if (!mem.alloc(&h->d_offP, K) || !mem.alloc(&h->d_offV, K) || !mem.alloc(&h->d_offG, K) || !mem.alloc(&h->d_offA, K))
+        return OMV_ERR_HIP;
     HIP_OK(up(h->d_offP, offP.data(), K));
     HIP_OK(up(h->d_offV, offV.data(), K));
     HIP_OK(up(h->d_offG, offG.data(), K));
     HIP_OK(up(h->d_offA, offA.data(), K));
     h->R = Red{nred, h->d_offP, K};
     // inertial
-    int *d_k1 = dalloc<int>(ow, NI), *d_k2 = dalloc<int>(ow, NI);
-    float *d_pre = dalloc<float>(ow, (size_t)NI * kPF);
-    double *d_i9 = dalloc<double>(ow, (size_t)NI * 81), *d_iG = dalloc<double>(ow, (size_t)NI * 9),
-           *d_iA = dalloc<double>(ow, (size_t)NI * 9);
-    uint8_t *d_rob = dalloc<uint8_t>(ow, NI);
-    h->d_imu_contrib = dalloc<double>(ow, (size_t)NI * kImuContrib);
-    if (!d_rob || !h->d_imu_contrib) return OMV_ERR_HIP;
+    int *d_k1, *d_k2;
+    float *d_pre;
+    double *d_i9, *d_iG, *d_iA;
+    uint8_t *d_rob;
+    if (!mem.alloc(&d_k1, NI) || !mem.alloc(&d_k2, NI) || !mem.alloc(&d_pre, (size_t)NI * kPF) ||
+        !mem.alloc(&d_i9, (size_t)NI * 81) || !mem.alloc(&d_iG, (size_t)NI * 9) || !mem.alloc(&d_iA, (size_t)NI * 9) ||
+        !mem.alloc(&d_rob, NI) || !mem.alloc(&h->d_imu_contrib, (size_t)NI * kImuContrib))
+        return OMV_ERR_HIP;
     if (NI > 0) {
         HIP_OK(up(d_k1, p->imu_kf1, NI));
         HIP_OK(up(d_k2, p->imu_kf2, NI));
@@ -2392,12 +2372,6 @@ omv_status omv_lba_set_problem(omv_lba *h, const omv_lba_problem *p) {
     }
     h->I = Imu{NI, d_k1, d_k2, d_pre, d_i9, d_iG, d_iA, d_rob, h->d_offP, h->d_offV, h->d_offG, h->d_offA};
     // reduction work lists
-    auto upv = [&](const auto &v) {
-        using T = typename std::decay_t<decltype(v)>::value_type;
-        T *d = dalloc<T>(ow, v.size());
-        if (d && !v.empty() && up(d, v.data(), v.size()) != hipSuccess) d = nullptr;
-        return (const T *)d;
-    };
     {
         Gather &g = h->G;
         g.blk_start = upv(blk_start), g.rhs_start = upv(rhs_start);
@@ -2446,29 +2420,20 @@ omv_status omv_lba_set_problem(omv_lba *h, const omv_lba_problem *p) {
         }
     }
     // work buffers
-    h->d_err = dalloc<double>(ow, 2 * (size_t)E);
-    h->d_chi2 = dalloc<double>(ow, E);
-    h->d_err3 = dalloc<double>(ow, E);
-    h->d_err9 = dalloc<double>(ow, 19 * (size_t)NI);   // [9n errors | n chi2 | 9n rotation errors eR]
-    h->d_err_b = dalloc<double>(ow, 2 * (size_t)E);       // the device driver's second (double-buffered) set
-    h->d_chi2_b = dalloc<double>(ow, E);
-    h->d_err3_b = dalloc<double>(ow, E);
-    h->d_err9_b = dalloc<double>(ow, 19 * (size_t)NI);
-    h->d_partial = dalloc<double>(ow, std::max(1, h->n_lgrp));
-    h->d_imu_partial = dalloc<double>(ow, 1);
-    h->d_partial0 = dalloc<double>(ow, std::max(1, h->n_lgrp));
-    h->d_imu_partial0 = dalloc<double>(ow, 1);
-    h->d_scale_partial = dalloc<double>(ow, h->n_lgrp + 1);
-    h->d_out = dalloc<double>(ow, 4);
-    // [packed blocks | b | coef]: contiguous, the one buffer a sharded solve all-reduces per trial
-    h->d_S = dalloc<double>(ow, (size_t)n_slots * 256 + 2 * (size_t)nred);
+    // d_err9: [9n errors | n chi2 | 9n rotation errors eR]; the *_b set: the device driver's second (double-buffered) one
+    // d_S: [packed blocks | b | coef], contiguous, the one buffer a sharded solve all-reduces per trial
+    h->n_reduce = (size_t)n_slots * 256 + 2 * (size_t)nred;
+    if (!mem.alloc(&h->d_err, 2 * (size_t)E) || !mem.alloc(&h->d_chi2, E) || !mem.alloc(&h->d_err3, E) ||
+        !mem.alloc(&h->d_err9, 19 * (size_t)NI) || !mem.alloc(&h->d_err_b, 2 * (size_t)E) ||
+        !mem.alloc(&h->d_chi2_b, E) || !mem.alloc(&h->d_err3_b, E) || !mem.alloc(&h->d_err9_b, 19 * (size_t)NI) ||
+        !mem.alloc(&h->d_partial, h->n_lgrp) || !mem.alloc(&h->d_imu_partial, 1) ||
+        !mem.alloc(&h->d_partial0, h->n_lgrp) || !mem.alloc(&h->d_imu_partial0, 1) ||
+        !mem.alloc(&h->d_scale_partial, h->n_lgrp + 1) || !mem.alloc(&h->d_out, 4) || !mem.alloc(&h->d_S, h->n_reduce) ||
+        !mem.alloc(&h->d_x, nred) || !mem.alloc(&h->d_scratch, h->use_lds == 1 ? 8 : h->n_reduce + 8) ||
+        !mem.alloc(&h->d_fail, 1))
+        return OMV_ERR_HIP;
     h->d_bb = h->d_S + (size_t)n_slots * 256;
     h->d_coef = h->d_bb + nred;
-    h->n_reduce = (size_t)n_slots * 256 + 2 * (size_t)nred;
-    h->d_x = dalloc<double>(ow, nred);
-    h->d_scratch = dalloc<double>(ow, h->use_lds == 1 ? 8 : (size_t)n_slots * 256 + 2 * (size_t)nred + 8);
-    h->d_fail = dalloc<int>(ow, 1);
-    if (!h->d_fail) return OMV_ERR_HIP;
     HIP_OK(hipMemset(h->d_imu_partial, 0, sizeof(double)));
     HIP_OK(hipMemset(h->d_imu_partial0, 0, sizeof(double)));
     // device epilogue (single rank): caller-order permutations, trackDepth in device order, the staging block
@@ -2476,15 +2441,15 @@ omv_status omv_lba_set_problem(omv_lba *h, const omv_lba_problem *p) {
         std::vector<float> td(P, 1e30f);
         if (p->pt_track_depth)
             for (int q = 0; q < P; ++q) td[q] = p->pt_track_depth[order[q]];
-        h->d_perm_edge = dalloc<int>(ow, E), h->d_perm_pt = dalloc<int>(ow, P), h->d_track_depth = dalloc<float>(ow, P);
         const size_t head = (size_t)(h->st[0].pts - h->st[0].Rwb);
         h->stage_bytes = (head + 3 * (size_t)P + ((size_t)E + 7) / 8 + (size_t)E) * sizeof(double);
-        h->d_stage = dalloc<double>(ow, (h->stage_bytes + 7) / 8);
-        if (!h->d_perm_edge || !h->d_perm_pt || !h->d_track_depth || !h->d_stage) return OMV_ERR_HIP;
+        if (!mem.alloc(&h->d_perm_edge, E) || !mem.alloc(&h->d_perm_pt, P) || !mem.alloc(&h->d_track_depth, P) ||
+            !mem.alloc(&h->d_stage, (h->stage_bytes + 7) / 8))
+            return OMV_ERR_HIP;
         if (E > 0) HIP_OK(up(h->d_perm_edge, h->perm_edge.data(), E));
         if (P > 0) HIP_OK(up(h->d_perm_pt, order.data(), P));
         if (P > 0) HIP_OK(up(h->d_track_depth, td.data(), P));
-        HIP_OK(hipHostMalloc((void **)&h->h_stage, h->stage_bytes, hipHostMallocDefault));
+        if (!mem.alloc_pinned(&h->h_stage, h->stage_bytes / sizeof(double))) return OMV_ERR_HIP;
     }
     return OMV_OK;
 }
@@ -2558,12 +2523,12 @@ static omv_status lba_eval(omv_lba *h, double *mono_err, double *mono_jx, double
     omv_status r = lba_errors(h, s);
     if (r != OMV_OK) return r;
     std::vector<double> jx, jp;
+    omv::DeviceArena tmp;   // the Jacobians, for this call
     double *d_jx = nullptr, *d_jp = nullptr;
     const int E = h->n_mono;
     const bool jac = mono_jx || mono_jp || st_jx || st_jp;
     if (jac && E > 0) {
-        HIP_OK(hipMalloc(&d_jx, sizeof(double) * 9 * E));
-        HIP_OK(hipMalloc(&d_jp, sizeof(double) * 18 * E));
+        if (!tmp.alloc(&d_jx, 9 * (size_t)E) || !tmp.alloc(&d_jp, 18 * (size_t)E)) return OMV_ERR_HIP;
         mono_jac_kernel<<<(E + 255) / 256, 256, 0, h->stream>>>(h->rig, s, h->E, d_jx, d_jp);
     }
     HIP_OK(hipStreamSynchronize(h->stream));
@@ -2577,8 +2542,6 @@ static omv_status lba_eval(omv_lba *h, double *mono_err, double *mono_jx, double
         jx.resize(9 * (size_t)E), jp.resize(18 * (size_t)E);
         HIP_OK(hipMemcpy(jx.data(), d_jx, jx.size() * sizeof(double), hipMemcpyDeviceToHost));
         HIP_OK(hipMemcpy(jp.data(), d_jp, jp.size() * sizeof(double), hipMemcpyDeviceToHost));
-        (void)hipFree(d_jx);
-        (void)hipFree(d_jp);
     }
     const int EM = h->n_mono_all;
     for (int e = 0; e < E; ++e) {   // back to the caller's edge order

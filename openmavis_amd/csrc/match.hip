@@ -2338,6 +2338,8 @@ struct omv_matcher {
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev;
     double stage_ms[4] = {0, 0, 0, 0};
     omv::MatcherKnobs knobs;   // test knobs, read from the environment once at creation
+    omv::DeviceArena mem;      // owns the d_* buffers, the grown ones included
+    ~omv_matcher() { for (auto &p : ev) (void)hipEventDestroy(p.second.first), (void)hipEventDestroy(p.second.second); }
 };
 
 omv::MatcherKnobs omv::matcher_knobs(const omv_matcher *m) { return m ? m->knobs : omv::MatcherKnobs{}; }
@@ -2416,7 +2418,7 @@ omv_status omv_matcher_create(int max_frames, int n_cams, int kp_cap, int max_mp
     HIP_OK(hipFuncSetAttribute((const void *)resolve_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, resolve_dyn));
     HIP_OK(hipFuncSetAttribute((const void *)lf_resolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResolveLds));
     HIP_OK(hipFuncSetAttribute((const void *)cand_stage_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStageLdsMax));
-    omv_matcher *h = new omv_matcher();
+    auto h = std::make_unique<omv_matcher>();
     h->max_frames = max_frames, h->n_cams = n_cams, h->kp_cap = kp_cap, h->max_mps = max_mps;
     if (const char *e = getenv("OMV_BOW_TOP")) h->knobs.bow_top = atoi(e);
     if (const char *e = getenv("OMV_TRI_SLICES")) h->knobs.tri_slices = atoi(e);
@@ -2425,16 +2427,15 @@ omv_status omv_matcher_create(int max_frames, int n_cams, int kp_cap, int max_mp
     if (const char *e = getenv("OMV_CAND")) h->knobs.cand_mode = strcmp(e, "global") == 0 ? 1 : strcmp(e, "lds") == 0 ? 2 : 0;
     if (const char *e = getenv("OMV_CAND_PW")) h->knobs.cand_pw = atoi(e);
     const size_t fc = (size_t)max_frames * n_cams;
-    HIP_OK(hipMalloc(&h->d_cell_start, sizeof(int32_t) * fc * (kCells + 1)));
-    HIP_OK(hipMalloc(&h->d_cell_idx, sizeof(int32_t) * fc * kp_cap));
-    HIP_OK(hipMalloc(&h->d_recs, sizeof(Rec) * std::max<size_t>(1, fc * max_mps)));
-    HIP_OK(hipMalloc(&h->d_counts, sizeof(int) * std::max<size_t>(1, fc * max_mps)));
-    HIP_OK(hipMalloc(&h->d_flags, sizeof(int) * std::max<size_t>(1, (size_t)max_frames * max_mps)));
-    HIP_OK(hipMalloc(&h->d_knn_i, sizeof(int32_t) * 2 * max_frames * kp_cap));
-    HIP_OK(hipMalloc(&h->d_knn_d, sizeof(int32_t) * 2 * max_frames * kp_cap));
-    HIP_OK(hipMalloc(&h->d_err, sizeof(int)));
+    const size_t knn = (size_t)2 * max_frames * kp_cap;
+    omv::DeviceArena &mem = h->mem;
+    if (!mem.alloc(&h->d_cell_start, fc * (kCells + 1)) || !mem.alloc(&h->d_cell_idx, fc * kp_cap) ||
+        !mem.alloc(&h->d_recs, fc * max_mps) || !mem.alloc(&h->d_counts, fc * max_mps) ||
+        !mem.alloc(&h->d_flags, (size_t)max_frames * max_mps) || !mem.alloc(&h->d_knn_i, knn) ||
+        !mem.alloc(&h->d_knn_d, knn) || !mem.alloc(&h->d_err, 1))
+        return OMV_ERR_HIP;
     HIP_OK(hipMemset(h->d_err, 0, sizeof(int)));
-    *out = h;
+    *out = h.release();
     return OMV_OK;
 }
 
@@ -2472,10 +2473,6 @@ omv_status omv_matcher_last_error(omv_matcher *h) {
 
 omv_status omv_matcher_destroy(omv_matcher *h) {
     if (!h) return OMV_ERR_ARG;
-    void *p[] = {h->d_cell_start, h->d_cell_idx, h->d_recs, h->d_counts, h->d_flags, h->d_knn_i, h->d_knn_d, h->d_err,
-                 h->d_push, h->d_npush, h->d_geo, h->d_jobs};
-    for (void *q : p)
-        if (q) (void)hipFree(q);
     delete h;
     return OMV_OK;
 }
@@ -2591,11 +2588,11 @@ omv_status omv_matcher_search_last_frame(omv_matcher *h, int n_frames, const omv
     G.th = th, G.mb = mb, G.bMono = bMono;
     const int C = h->n_cams;
     const size_t per_frame = (size_t)std::max(1, last->S) * C;
-    if (h->push_cap < per_frame * n_frames) {
-        if (h->d_push) (void)hipFree(h->d_push);
-        if (h->d_npush) (void)hipFree(h->d_npush);
-        HIP_OK(hipMalloc(&h->d_push, sizeof(int2) * per_frame * n_frames));
-        HIP_OK(hipMalloc(&h->d_npush, sizeof(int) * h->max_frames));
+    if (h->push_cap < per_frame * n_frames) {   // d_npush goes with d_push: push_cap stands for both, and is set last
+        (void)h->mem.free(&h->d_push), (void)h->mem.free(&h->d_npush);
+        h->push_cap = 0;
+        if (!h->mem.alloc(&h->d_push, per_frame * n_frames) || !h->mem.alloc(&h->d_npush, h->max_frames))
+            return OMV_ERR_HIP;
         h->push_cap = per_frame * n_frames;
     }
     if (last->S > 0) {
@@ -2640,18 +2637,9 @@ omv_status omv_matcher_search_kf(omv_matcher *h, int n_kf, const omv_frame_geom 
     if (n_jobs == 0) return OMV_OK;
     hipStream_t st = (hipStream_t)stream;
     h->last = st;
-    if (h->jobs_cap < (size_t)n_jobs) {
-        if (h->d_jobs) (void)hipFree(h->d_jobs);
-        h->d_jobs = nullptr, h->jobs_cap = 0;
-        HIP_OK(hipMalloc(&h->d_jobs, sizeof(omv_kf_search_job) * n_jobs));
-        h->jobs_cap = n_jobs;
-    }
-    if (claim && h->geo_cap < (size_t)std::max(1, n_entries)) {
-        if (h->d_geo) (void)hipFree(h->d_geo);
-        h->d_geo = nullptr, h->geo_cap = 0;
-        HIP_OK(hipMalloc(&h->d_geo, sizeof(float4) * std::max(1, n_entries)));
-        h->geo_cap = std::max(1, n_entries);
-    }
+    if (h->jobs_cap < (size_t)n_jobs && !h->mem.grow(&h->d_jobs, &h->jobs_cap, n_jobs)) return OMV_ERR_HIP;
+    if (claim && h->geo_cap < (size_t)std::max(1, n_entries) && !h->mem.grow(&h->d_geo, &h->geo_cap, std::max(1, n_entries)))
+        return OMV_ERR_HIP;
     HIP_OK(hipMemcpyAsync(h->d_jobs, jobs, sizeof(omv_kf_search_job) * n_jobs, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(n_matches, 0, sizeof(int32_t) * n_jobs, st));
     KfArgs a{};
@@ -2703,8 +2691,9 @@ omv_status omv_matcher_search_by_sim3(omv_matcher *h, int n_kf, const omv_frame_
     const size_t job_b = ((sizeof(omv_sim3_job) * n_jobs + 255) / 256) * 256;
     const size_t vn1_b = ((sizeof(int32_t) * std::max(1, n1) + 255) / 256) * 256;
     const size_t vn2_b = sizeof(int32_t) * (size_t)n_jobs * N;
+    omv::DeviceArena ws;
     uint8_t *buf = nullptr;
-    HIP_OK(hipMallocAsync((void **)&buf, job_b + vn1_b + vn2_b, st));
+    if (!ws.alloc_async(&buf, job_b + vn1_b + vn2_b, st)) return OMV_ERR_HIP;
     Sim3Args a{};
     fill_frame(h, g, kps, desc, n_kp, a.f);
     a.jobs = reinterpret_cast<const omv_sim3_job *>(buf);
@@ -2720,7 +2709,7 @@ omv_status omv_matcher_search_by_sim3(omv_matcher *h, int n_kf, const omv_frame_
     if (n1 + n2 > 0) sbs3_cand_kernel<<<(n1 + n2 + 255) / 256, 256, 0, st>>>(a);
     if (n1 > 0) sbs3_agree_kernel<<<(n1 + 255) / 256, 256, 0, st>>>(a);
     HIP_OK(hipGetLastError());
-    HIP_OK(hipFreeAsync(buf, st));
+    HIP_OK(ws.free(&buf));
     return OMV_OK;
 }
 
@@ -2774,17 +2763,18 @@ omv_status omv_matcher_search_for_initialization(omv_matcher *h, int n_pairs, co
     const size_t lds = init_lds_bytes(h->kp_cap);
     if (lds > 160 * 1024) return OMV_ERR_CAPACITY;
     HIP_OK(hipFuncSetAttribute((const void *)init_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    omv::DeviceArena ws;
     int32_t *d_pairs = nullptr;
-    HIP_OK(hipMallocAsync((void **)&d_pairs, sizeof(int32_t) * 2 * n_pairs, st));
+    if (!ws.alloc_async(&d_pairs, (size_t)2 * n_pairs, st)) return OMV_ERR_HIP;
     HIP_OK(hipMemcpyAsync(d_pairs, pairs, sizeof(int32_t) * 2 * n_pairs, hipMemcpyHostToDevice, st));
     uint4 *d_spec = nullptr;
-    HIP_OK(hipMallocAsync((void **)&d_spec, sizeof(uint4) * 4 * (size_t)n_pairs * h->kp_cap, st));
+    if (!ws.alloc_async(&d_spec, 4 * (size_t)n_pairs * h->kp_cap, st)) return OMV_ERR_HIP;
     InitArgs ia{f, d_pairs, prev_matched, window, nnratio, check_ori, matches12, n_matches, d_spec};
     init_spec_kernel<<<dim3((h->kp_cap + 3) / 4, n_pairs), 256, 0, st>>>(ia);
     init_kernel<<<n_pairs, 64, lds, st>>>(ia);
     HIP_OK(hipGetLastError());
-    HIP_OK(hipFreeAsync(d_spec, st));
-    HIP_OK(hipFreeAsync(d_pairs, st));
+    HIP_OK(ws.free(&d_spec));
+    HIP_OK(ws.free(&d_pairs));
     return OMV_OK;
 }
 

@@ -471,15 +471,10 @@ struct omv_optsim3 {
     float *d_f = nullptr;        // prepared: X1 [3], X2 [3], obs2 [2] (8 floats per entry, planar)
     double *d_d = nullptr;       // c12, c21, e0 [4] (6 doubles per entry, planar)
     OptSim3Debug *d_dbg = nullptr;
+    omv::DeviceArena mem;   // owns the device and pinned blocks
 };
 
 namespace {
-void optsim3_free(omv_optsim3 *h) {
-    (void)hipFree(h->d_in), (void)hipFree(h->d_out), (void)hipFree(h->d_f), (void)hipFree(h->d_d);
-    (void)hipFree(h->d_dbg);
-    (void)hipHostFree(h->h_in), (void)hipHostFree(h->h_out);
-    delete h;
-}
 constexpr size_t kOs3InJob = sizeof(OptSim3Job) + 8 * sizeof(double), kOs3InEntry = 12 * sizeof(float) + 1;
 constexpr size_t kOs3OutJob = 8 * sizeof(double) + sizeof(int32_t), kOs3OutEntry = 1;
 static_assert(sizeof(OptSim3Job) % 8 == 0, "S follows the jobs in the upload block");
@@ -491,26 +486,23 @@ omv_status omv_optimize_sim3_create(int max_jobs, int max_entries_total, omv_opt
     if (!out || max_jobs <= 0 || max_entries_total < 0) return OMV_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return OMV_ERR_NO_DEVICE;
-    omv_optsim3 *h = new omv_optsim3();
+    auto h = std::make_unique<omv_optsim3>();
     h->max_jobs = max_jobs, h->max_entries = max_entries_total;
     const size_t ne = (size_t)std::max(1, max_entries_total);
     const size_t in_bytes = max_jobs * kOs3InJob + ne * kOs3InEntry;
     const size_t out_bytes = max_jobs * kOs3OutJob + ne * kOs3OutEntry;
-    if (hipMalloc(&h->d_in, in_bytes) != hipSuccess || hipMalloc(&h->d_out, out_bytes) != hipSuccess ||
-        hipHostMalloc(&h->h_in, in_bytes) != hipSuccess || hipHostMalloc(&h->h_out, out_bytes) != hipSuccess ||
-        hipMalloc(&h->d_f, ne * 8 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&h->d_d, ne * 6 * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->d_dbg, max_jobs * sizeof(OptSim3Debug)) != hipSuccess) {
-        optsim3_free(h);
+    omv::DeviceArena &mem = h->mem;
+    if (!mem.alloc(&h->d_in, in_bytes) || !mem.alloc(&h->d_out, out_bytes) || !mem.alloc_pinned(&h->h_in, in_bytes) ||
+        !mem.alloc_pinned(&h->h_out, out_bytes) || !mem.alloc(&h->d_f, ne * 8) || !mem.alloc(&h->d_d, ne * 6) ||
+        !mem.alloc(&h->d_dbg, max_jobs))
         return OMV_ERR_HIP;
-    }
-    *out = h;
+    *out = h.release();
     return OMV_OK;
 }
 
 omv_status omv_optimize_sim3_destroy(omv_optsim3 *h) {
     if (!h) return OMV_ERR_ARG;
-    optsim3_free(h);
+    delete h;
     return OMV_OK;
 }
 

@@ -1558,6 +1558,8 @@ struct omv_orb {
     std::vector<hipEvent_t> ev;   // 5 events per batch: before K1, K2, K3, K4, after K4
     double stage_ms[kOrbStages] = {};
     long long stage_calls = 0;
+    omv::DeviceArena mem;   // owns every d_* buffer
+    ~omv_orb() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
 };
 
 static void flush_timing(omv_orb *o) {
@@ -1804,7 +1806,9 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
     if (params->nlevels < 1 || params->nlevels > kMaxLevels || params->nfeatures <= 0) return OMV_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return OMV_ERR_NO_DEVICE;
-    omv_orb *o = new omv_orb();
+    auto owner = std::make_unique<omv_orb>();
+    omv_orb *o = owner.get();
+    omv::DeviceArena &mem = o->mem;
     o->p = *params;
     o->W = width, o->H = height, o->max_images = max_images;
     if (const char *pm = getenv("OMV_PYR_MODE")) o->pyr_mode = std::strcmp(pm, "chain") == 0 ? 1 : 0;
@@ -1813,26 +1817,18 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
     std::vector<XTab> xt, yt;
     std::vector<XQuad> xq;
     omv_status st = build_geometry(o, cells, xt, yt, xq);
-    if (st != OMV_OK) {
-        delete o;
-        return st;
-    }
-    if (o->oct_lds > 160 * 1024) {
-        delete o;
-        return OMV_ERR_ARG;
-    }
+    if (st != OMV_OK) return st;
+    if (o->oct_lds > 160 * 1024) return OMV_ERR_ARG;
     // 1080p levels hold ~1,500 cells: the octree's node lists then exceed the default 64 KB dynamic LDS
     if (o->oct_lds > 64 * 1024 &&
         (hipFuncSetAttribute((const void *)octree_kernel<OMV_OCT_WGS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)o->oct_lds) != hipSuccess ||
          hipFuncSetAttribute((const void *)octree_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)o->oct_lds) != hipSuccess)) {
-        delete o;
+                             (int)o->oct_lds) != hipSuccess))
         return OMV_ERR_HIP;
-    }
     const Geom &g = o->g;
     const size_t n = (size_t)max_images;
-    HIP_OK(hipMalloc(&o->d_cells, sizeof(Cell) * cells.size()));
+    if (!mem.alloc(&o->d_cells, cells.size())) return OMV_ERR_HIP;
     HIP_OK(hipMemcpy(o->d_cells, cells.data(), sizeof(Cell) * cells.size(), hipMemcpyHostToDevice));
     for (int l = 1; l < g.nlevels; ++l) {   // K1 LDS: the generic path's x table + the most source rows a row block reads
         const LevelGeom &L = g.lv[l];
@@ -1857,10 +1853,7 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
             const size_t need = sizeof(uint32_t) * (rows_dw + 4 * kPyrBlock);
             o->pyr_lds[l] = std::max(need, std::min(o->pyr_lds[l], kPyrLdsHold));
         }
-        if (o->pyr_lds[l] > 160 * 1024) {   // images wider than ~8000 px
-            delete o;
-            return OMV_ERR_ARG;
-        }
+        if (o->pyr_lds[l] > 160 * 1024) return OMV_ERR_ARG;   // images wider than ~8000 px
         if (o->pyr_lds[l] > 64 * 1024)
             (void)hipFuncSetAttribute((const void *)pyr_resize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)o->pyr_lds[l]);
@@ -1904,12 +1897,12 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
                     }
                 }
                 o->pyr_nb = nb, o->pyr_buf_dw = worst, o->pyr_tab_dw = (tab + 3) & ~3, o->pyr_rows = rows, o->pyr_ydw = ydw;
-                HIP_OK(hipMalloc(&o->d_bands, sizeof(PyrBand) * bands.size()));
+                if (!mem.alloc(&o->d_bands, bands.size())) return OMV_ERR_HIP;
                 HIP_OK(hipMemcpy(o->d_bands, bands.data(), sizeof(PyrBand) * bands.size(), hipMemcpyHostToDevice));
                 const int lds = (int)(sizeof(uint32_t) * (2 * (size_t)worst + 4 + o->pyr_tab_dw + (size_t)ydw * rows));
                 if (lds > 160 * 1024) {   // no plan: the per-level launches
-                    (void)hipFree(o->d_bands);
-                    o->d_bands = nullptr, o->pyr_nb = 0;
+                    (void)mem.free(&o->d_bands);
+                    o->pyr_nb = 0;
                     break;
                 }
                 if (lds > 64 * 1024)
@@ -1917,40 +1910,29 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
             }
         }
     }
-    HIP_OK(hipMalloc(&o->d_xt, sizeof(XTab) * std::max<size_t>(1, xt.size())));
-    HIP_OK(hipMalloc(&o->d_yt, sizeof(XTab) * std::max<size_t>(1, yt.size())));
+    if (!mem.alloc(&o->d_xt, xt.size()) || !mem.alloc(&o->d_yt, yt.size())) return OMV_ERR_HIP;
     if (!xt.empty()) HIP_OK(hipMemcpy(o->d_xt, xt.data(), sizeof(XTab) * xt.size(), hipMemcpyHostToDevice));
     if (!yt.empty()) HIP_OK(hipMemcpy(o->d_yt, yt.data(), sizeof(XTab) * yt.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMalloc(&o->d_xq, sizeof(XQuad) * std::max<size_t>(1, xq.size())));
+    if (!mem.alloc(&o->d_xq, xq.size())) return OMV_ERR_HIP;
     if (!xq.empty()) HIP_OK(hipMemcpy(o->d_xq, xq.data(), sizeof(XQuad) * xq.size(), hipMemcpyHostToDevice));
     {
         const std::vector<uint32_t> dt = disc_table(o->umax);
-        HIP_OK(hipMalloc(&o->d_disc, sizeof(uint32_t) * dt.size()));
+        if (!mem.alloc(&o->d_disc, dt.size())) return OMV_ERR_HIP;
         HIP_OK(hipMemcpy(o->d_disc, dt.data(), sizeof(uint32_t) * dt.size(), hipMemcpyHostToDevice));
     }
-    HIP_OK(hipMalloc(&o->d_pyr, std::max<size_t>(256, (size_t)g.pyr_bytes * n)));
-    HIP_OK(hipMalloc(&o->d_cell_cnt, sizeof(int) * g.n_cells * n));
-    HIP_OK(hipMalloc(&o->d_cell_kp, sizeof(uint32_t) * (size_t)g.n_cells * g.cell_cap * n));
-    HIP_OK(hipMalloc(&o->d_cand, sizeof(uint32_t) * (size_t)g.cand_per_img * n));
-    HIP_OK(hipMalloc(&o->d_nid, sizeof(uint32_t) * (size_t)g.cand_per_img * n));
-    HIP_OK(hipMalloc(&o->d_lvl_out, sizeof(uint32_t) * (size_t)g.out_per_img * n));
-    HIP_OK(hipMalloc(&o->d_lvl_cls, sizeof(uint32_t) * (size_t)g.out_per_img * n));
-    HIP_OK(hipMalloc(&o->d_lvl_cnt, sizeof(int) * 3 * g.nlevels * n));
-    HIP_OK(hipMalloc(&o->d_lap, sizeof(int) * 2 * n));
-    HIP_OK(hipMalloc(&o->d_err, sizeof(int)));
+    if (!mem.alloc(&o->d_pyr, std::max<size_t>(256, (size_t)g.pyr_bytes * n)) ||
+        !mem.alloc(&o->d_cell_cnt, (size_t)g.n_cells * n) || !mem.alloc(&o->d_cell_kp, (size_t)g.n_cells * g.cell_cap * n) ||
+        !mem.alloc(&o->d_cand, (size_t)g.cand_per_img * n) || !mem.alloc(&o->d_nid, (size_t)g.cand_per_img * n) ||
+        !mem.alloc(&o->d_lvl_out, (size_t)g.out_per_img * n) || !mem.alloc(&o->d_lvl_cls, (size_t)g.out_per_img * n) ||
+        !mem.alloc(&o->d_lvl_cnt, (size_t)3 * g.nlevels * n) || !mem.alloc(&o->d_lap, 2 * n) || !mem.alloc(&o->d_err, 1))
+        return OMV_ERR_HIP;
     HIP_OK(hipMemset(o->d_err, 0, sizeof(int)));
-    *out = o;
+    *out = owner.release();
     return OMV_OK;
 }
 
 omv_status omv_orb_destroy(omv_orb *o) {
     if (!o) return OMV_ERR_ARG;
-    for (hipEvent_t e : o->ev) (void)hipEventDestroy(e);
-    void *ptrs[] = {o->d_bands, o->d_cells, o->d_xt, o->d_yt, o->d_xq, o->d_disc, o->d_pyr, o->d_cell_cnt, o->d_cell_kp, o->d_cand, o->d_nid,
-                    o->d_lvl_out, o->d_lvl_cls, o->d_lvl_cnt, o->d_lap, o->d_err, o->d_img1, o->d_kp1,
-                    o->d_desc1, o->d_n1};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
     delete o;
     return OMV_OK;
 }
@@ -2067,11 +2049,11 @@ omv_status omv_orb_extract_host(omv_orb *o, const uint8_t *image, size_t pitch, 
                                 uint8_t *desc, int *n_out, int *mono_index) {
     if (!o || !image || !kps || !desc || !n_out || !mono_index) return OMV_ERR_ARG;
     const size_t dp = (size_t)o->W;
-    if (!o->d_img1) {
-        HIP_OK(hipMalloc(&o->d_img1, dp * o->H));
-        HIP_OK(hipMalloc(&o->d_kp1, sizeof(omv_kp) * o->g.n_max));
-        HIP_OK(hipMalloc(&o->d_desc1, 32 * (size_t)o->g.n_max));
-        HIP_OK(hipMalloc(&o->d_n1, 2 * sizeof(int)));
+    if (!o->d_n1) {   // first use; d_n1 comes last: what a call that failed part-way left is freed and made again
+        (void)o->mem.free(&o->d_img1), (void)o->mem.free(&o->d_kp1), (void)o->mem.free(&o->d_desc1);
+        if (!o->mem.alloc(&o->d_img1, dp * o->H) || !o->mem.alloc(&o->d_kp1, o->g.n_max) ||
+            !o->mem.alloc(&o->d_desc1, 32 * (size_t)o->g.n_max) || !o->mem.alloc(&o->d_n1, 2))
+            return OMV_ERR_HIP;
     }
     HIP_OK(hipMemcpy2D(o->d_img1, dp, image, pitch, o->W, o->H, hipMemcpyHostToDevice));
     int lap[2] = {lap0, lap1};

@@ -2318,6 +2318,7 @@ struct omv_pose {
     uint32_t call = 0;
     int32_t *err = nullptr;
     int mode = OMV_POSE_AUTO, parts = 0;
+    omv::DeviceArena mem;   // owns the buffers above
 };
 
 extern "C" {
@@ -2326,33 +2327,20 @@ omv_status omv_pose_create(int max_frames, int max_edges, omv_pose **out) {
     if (!out || max_frames <= 0 || max_edges < 0) return OMV_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return OMV_ERR_NO_DEVICE;
-    omv_pose *h = new omv_pose();
+    auto h = std::make_unique<omv_pose>();
     h->max_frames = max_frames, h->max_edges = max_edges;
-    const size_t n = 2 * (size_t)std::max(1, max_edges);
-    const size_t xb = (size_t)max_frames * kLatFrameGran * sizeof(unsigned long long);
-    if (hipMalloc(&h->chi2, n * sizeof(double)) != hipSuccess || hipMalloc(&h->act, n) != hipSuccess ||
-        hipMalloc(&h->info, (size_t)max_frames * 99 * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->xbuf, xb) != hipSuccess || hipMemset(h->xbuf, 0, xb) != hipSuccess ||
-        hipMalloc(&h->err, sizeof(int32_t)) != hipSuccess || hipMemset(h->err, 0, sizeof(int32_t)) != hipSuccess) {
-        (void)hipFree(h->chi2);
-        (void)hipFree(h->act);
-        (void)hipFree(h->info);
-        (void)hipFree(h->xbuf);
-        (void)hipFree(h->err);
-        delete h;
+    const size_t n = 2 * (size_t)std::max(1, max_edges), xw = (size_t)max_frames * kLatFrameGran;
+    omv::DeviceArena &mem = h->mem;
+    if (!mem.alloc(&h->chi2, n) || !mem.alloc(&h->act, n) || !mem.alloc(&h->info, (size_t)max_frames * 99) ||
+        !mem.alloc(&h->xbuf, xw) || hipMemset(h->xbuf, 0, xw * sizeof(unsigned long long)) != hipSuccess ||
+        !mem.alloc(&h->err, 1) || hipMemset(h->err, 0, sizeof(int32_t)) != hipSuccess)
         return OMV_ERR_HIP;
-    }
-    *out = h;
+    *out = h.release();
     return OMV_OK;
 }
 
 omv_status omv_pose_destroy(omv_pose *h) {
     if (!h) return OMV_ERR_ARG;
-    (void)hipFree(h->chi2);
-    (void)hipFree(h->act);
-    (void)hipFree(h->info);
-    (void)hipFree(h->xbuf);
-    (void)hipFree(h->err);
     delete h;
     return OMV_OK;
 }

@@ -367,16 +367,10 @@ struct omv_sim3_solver {
     int32_t *d_hidx = nullptr, *d_hcount = nullptr;
     float *d_hf = nullptr;    // per (job, hypothesis): T12 [16], T21 [16], R [9], t [3], s (45 floats, planar)
     unsigned long long *d_hmask = nullptr, *d_best_mask = nullptr;
+    omv::DeviceArena mem;   // owns the d_* buffers
 };
 
 namespace {
-
-void sim3_free(omv_sim3_solver *h) {
-    (void)hipFree(h->d_jobs), (void)hipFree(h->d_state), (void)hipFree(h->d_corr_job), (void)hipFree(h->d_index1);
-    (void)hipFree(h->d_in), (void)hipFree(h->d_pre), (void)hipFree(h->d_hidx), (void)hipFree(h->d_hcount);
-    (void)hipFree(h->d_hf), (void)hipFree(h->d_hmask), (void)hipFree(h->d_best_mask);
-    delete h;
-}
 
 // SetRansacParameters (:194-204) in the reference's types.  Where the reference converts a NaN or an out-of-range
 // double to int (undefined; x86 yields INT_MIN) the result is INT_MIN, so mRansacMaxIts becomes 1.
@@ -400,31 +394,23 @@ omv_status omv_sim3_solver_create(int max_jobs, int max_corr_total, int max_hyp,
     if (!out || max_jobs <= 0 || max_corr_total < 0 || max_hyp <= 0) return OMV_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return OMV_ERR_NO_DEVICE;
-    omv_sim3_solver *h = new omv_sim3_solver();
+    auto h = std::make_unique<omv_sim3_solver>();
     h->max_jobs = max_jobs, h->max_corr = max_corr_total, h->max_hyp = max_hyp;
     h->words_cap = max_corr_total / 64 + max_jobs;
     const size_t nc = (size_t)std::max(1, max_corr_total), nh = (size_t)max_jobs * max_hyp;
-    if (hipMalloc(&h->d_jobs, max_jobs * sizeof(JobParams)) != hipSuccess ||
-        hipMalloc(&h->d_state, max_jobs * sizeof(JobState)) != hipSuccess ||
-        hipMalloc(&h->d_corr_job, nc * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&h->d_index1, nc * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&h->d_in, nc * 8 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&h->d_pre, nc * 12 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&h->d_hidx, nh * 3 * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&h->d_hcount, nh * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&h->d_hf, nh * 45 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&h->d_hmask, (size_t)max_hyp * h->words_cap * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(&h->d_best_mask, (size_t)h->words_cap * sizeof(unsigned long long)) != hipSuccess) {
-        sim3_free(h);
+    omv::DeviceArena &mem = h->mem;
+    if (!mem.alloc(&h->d_jobs, max_jobs) || !mem.alloc(&h->d_state, max_jobs) || !mem.alloc(&h->d_corr_job, nc) ||
+        !mem.alloc(&h->d_index1, nc) || !mem.alloc(&h->d_in, nc * 8) || !mem.alloc(&h->d_pre, nc * 12) ||
+        !mem.alloc(&h->d_hidx, nh * 3) || !mem.alloc(&h->d_hcount, nh) || !mem.alloc(&h->d_hf, nh * 45) ||
+        !mem.alloc(&h->d_hmask, (size_t)max_hyp * h->words_cap) || !mem.alloc(&h->d_best_mask, h->words_cap))
         return OMV_ERR_HIP;
-    }
-    *out = h;
+    *out = h.release();
     return OMV_OK;
 }
 
 omv_status omv_sim3_solver_destroy(omv_sim3_solver *h) {
     if (!h) return OMV_ERR_ARG;
-    sim3_free(h);
+    delete h;
     return OMV_OK;
 }
 

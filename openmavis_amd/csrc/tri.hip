@@ -1345,13 +1345,14 @@ omv_status omv_tri_debug(const float *cams2, const omv_kp *kp1, const omv_kp *kp
     for (int q = 0; q < 9; ++q) h[q] = R12[q];
     for (int q = 0; q < 3; ++q) h[9 + q] = t12[q];
     for (int q = 0; q < 16; ++q) h[12 + q] = svd_in[q];
+    omv::DeviceArena mem;
     float *d = nullptr;
-    HIP_OK(hipMalloc(&d, sizeof(float) * (28 + 31)));
+    if (!mem.alloc(&d, 28 + 31)) return OMV_ERR_HIP;
     HIP_OK(hipMemcpy(d, h, sizeof(float) * 28, hipMemcpyHostToDevice));
     tri_debug_kernel<<<1, 1>>>(C, *kp1, *kp2, d, sigma, unc, d + 28);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(out31, d + 28, sizeof(float) * 31, hipMemcpyDeviceToHost));
-    HIP_OK(hipFree(d));
+    HIP_OK(mem.free(&d));
     return OMV_OK;
 }
 
@@ -1394,8 +1395,9 @@ omv_status tri_search_chunk(omv_matcher *m, int n_pairs, const omv_tri_pair *pai
     const size_t slots = (size_t)n_pairs * S;
     const size_t bytes = sizeof(omv_tri_pair) * n_pairs + slots * (size_t)ecap * 12 + slots * (size_t)tcap * 4 +
                          (2 * slots + 2 * (size_t)n_pairs + 1) * sizeof(int);
+    omv::DeviceArena tmp;
     char *blob = nullptr;
-    HIP_OK(hipMallocAsync((void **)&blob, bytes, st));
+    if (!tmp.alloc_async(&blob, bytes, st)) return OMV_ERR_HIP;
     omv_tri_pair *d_pairs = reinterpret_cast<omv_tri_pair *>(blob);
     TriWs ws;
     ws.pk = reinterpret_cast<uint32_t *>(d_pairs + n_pairs);
@@ -1426,7 +1428,7 @@ omv_status tri_search_chunk(omv_matcher *m, int n_pairs, const omv_tri_pair *pai
         HIP_OK(hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
     }
-    HIP_OK(hipFreeAsync(blob, st));
+    HIP_OK(tmp.free(&blob));
     return h_err ? (omv_status)h_err : OMV_OK;
 }
 
@@ -1494,9 +1496,9 @@ omv_status omv_create_new_map_points(int n_jobs, const omv_cnmp_kf *kf1, const o
     hipStream_t st = (hipStream_t)stream;
     // the keyframe views and jobs travel as one device blob: [kf1 | jobs | last_p1 | state]
     const size_t bytes = sizeof(omv_cnmp_kf) + sizeof(omv_cnmp_job) * n_jobs + sizeof(int) * (n_jobs + 1);
-    void *blob = nullptr;
-    HIP_OK(hipMallocAsync(&blob, bytes, st));
-    char *b = (char *)blob;
+    omv::DeviceArena tmp;
+    char *b = nullptr;
+    if (!tmp.alloc_async(&b, bytes, st)) return OMV_ERR_HIP;
     HIP_OK(hipMemcpyAsync(b, kf1, sizeof(omv_cnmp_kf), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(b + sizeof(omv_cnmp_kf), jobs, sizeof(omv_cnmp_job) * n_jobs, hipMemcpyHostToDevice, st));
     const omv_cnmp_kf *d_kf1 = (const omv_cnmp_kf *)b;
@@ -1509,7 +1511,7 @@ omv_status omv_create_new_map_points(int n_jobs, const omv_cnmp_kf *kf1, const o
     cnmp_kernel<<<n_jobs, kCnmpThreads, 0, st>>>(d_kf1, d_jobs, d_last, a, d_state, check_baseline, has_mp1);
     if (side1_state) cnmp_state_kernel<<<1, 1, 0, st>>>(d_kf1, d_jobs, n_jobs, d_last, d_state, check_baseline, side1_state);
     HIP_OK(hipGetLastError());
-    HIP_OK(hipFreeAsync(blob, st));
+    HIP_OK(tmp.free(&b));
     return OMV_OK;
 }
 
@@ -1561,8 +1563,9 @@ omv_status omv_local_mapping_create_new_map_points(omv_matcher *m, const omv_cnm
     }
     const size_t head = sizeof(omv_tri_pair) * n_nb + sizeof(omv_cnmp_kf) + sizeof(omv_cnmp_job) * n_nb;
     const size_t bytes = head + sizeof(int) * (4 + 2 * (size_t)S) + (size_t)S * ecap * 12 + (size_t)S * tcap * 4;
+    omv::DeviceArena tmp;
     char *blob = nullptr;
-    HIP_OK(hipMallocAsync((void **)&blob, bytes, st));
+    if (!tmp.alloc_async(&blob, bytes, st)) return OMV_ERR_HIP;
     omv_tri_pair *d_pairs = reinterpret_cast<omv_tri_pair *>(blob);
     omv_cnmp_kf *d_kf1 = reinterpret_cast<omv_cnmp_kf *>(blob + sizeof(omv_tri_pair) * n_nb);
     omv_cnmp_job *d_jobs = reinterpret_cast<omv_cnmp_job *>(d_kf1 + 1);
@@ -1601,7 +1604,7 @@ omv_status omv_local_mapping_create_new_map_points(omv_matcher *m, const omv_cnm
     if (side1_state) HIP_OK(hipMemcpyAsync(side1_state, d_state, sizeof(int), hipMemcpyDeviceToDevice, st));
     int h_err = 0;
     HIP_OK(hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipFreeAsync(blob, st));
+    HIP_OK(tmp.free(&blob));
     HIP_OK(hipStreamSynchronize(st));
     return h_err ? (omv_status)h_err : OMV_OK;
 }
