@@ -200,6 +200,9 @@ omv_status omv_matcher_stage_ms(omv_matcher *m, double *ms4, int reset);
  * fewer than 1 / 2 train rows exist. */
 omv_status omv_bf_knn2(int n_pairs, const uint8_t *query, int q_cap, const int *nq, const uint8_t *train, int t_cap,
                        const int *nt, int32_t *idx2, int32_t *dist2, void *stream);
+/* Which kernel omv_bf_knn2 takes at this shape, under the OMV_KNN / OMV_KNN_IDX_LIMIT test knobs: 1 the matrix-core
+ * kernel, 0 the lane kernel (always, once t_cap reaches the 2^16 rows the packed key cannot index).  Launches nothing. */
+int omv_bf_knn2_path(int n_pairs, int q_cap, int t_cap);
 
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono)
  * (src/ORBmatcher.cc:1985-2413, ComputeThreeMaxima :2537-2573): motion-model matching of the last

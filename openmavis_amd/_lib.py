@@ -271,6 +271,7 @@ SIGNATURES = {
                                            _VP, _VP]),
     "omv_matcher_stereo_lapping": (_I, [_VP, _I, _VP, _VP, _VP, ctypes.c_double, _VP, _VP, _VP]),
     "omv_bf_knn2": (_I, [_I, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "omv_bf_knn2_path": (_I, [_I, _I, _I]),
     "omv_matcher_search_last_frame": (_I, [_VP, _I, ctypes.POINTER(FrameGeom), _VP, _VP, _VP, _VP, _VP, _VP,
                                            ctypes.POINTER(SE3f), ctypes.POINTER(LastFrame), _F, _I, _F, _I, _VP, _VP,
                                            _VP, _VP]),

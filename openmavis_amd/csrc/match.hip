@@ -17,6 +17,8 @@
 //                    (a keypoint taken by an earlier point with Observations() > 0 is skipped).
 //   knn2_kernel      cv::BFMatcher(NORM_HAMMING).knnMatch(k=2) (src/Frame.cc:1483): train tiles in
 //                    LDS, one query per lane, 4 x popcount64 per pair, first index wins ties.
+//   knn2_mfma_kernel the same knn for a batch as an i8 product on the matrix cores (train bits as {0, 1},
+//                    query bits as {+1, -1}, accumulator started at popcount(query)): bit-identical.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -1293,11 +1295,162 @@ __global__ void __launch_bounds__(256) knn2_kernel(KnnArgs a, int n_pairs) {
     }
 }
 
-// 8 lanes per query at every batch size: one frame (1,200 queries) needs the spread to fill the chip, and at 128
-// frames the shorter per-lane chains and 8x the waves still win over one lane per query (0.150 vs 0.189 ms per
-// 128-frame launch; G = 2 / 4: 0.169 / 0.154).
-static void launch_knn2(const KnnArgs &a, int n_pairs, int q_cap, hipStream_t st) {
-    if ((long long)n_pairs * q_cap <= 4096)   // a frame or three: 32 lanes per query, shorter chains
+// The same knn as one i8 product per pair on the matrix cores.  With train bit k as the byte t_k in {0, 1} and query
+// bit k as the byte 1 - 2 q_k in {+1, -1}, sum_k t_k (1 - 2 q_k) + popcount(q) is the Hamming distance, exact in
+// i32: the accumulator starts at popcount(q) and v_mfma_i32_16x16x64_i8 leaves the distance itself.  Train rows are
+// the MFMA's rows (A), queries its columns (B): lane l holds the distances of query (l & 15) of a column tile to train
+// rows 4 (l >> 4) + i, i = 0 .. 3, of a row tile (the C/D map every 16x16 MFMA shares).  Both operands are filled by
+// the same rule -- lane l takes descriptor bits 64 s + 16 (l >> 4) + j as byte j of k-step s -- so whatever order
+// the instruction gives k inside its 64 is the same on both sides, and a sum over k does not depend on it.
+//
+// Block = 4 waves x 64 queries (4 column tiles, their 16 B fragments expanded once into 64 VGPRs); 64 train rows a
+// time are expanded into LDS for the four waves.  A lane keeps the two smallest packed keys (distance << 16 | train
+// index) of its rows over all tiles: an unsigned min and a median of three per distance, the lower index winning a
+// tie by the key's low half.  The four lanes of a query merge at the end with two shuffles.  Needs nt < 2^16
+// (launch_knn2).
+constexpr int kKnnTile = 64;          // train rows per LDS tile
+constexpr int kKnnRowB = 256 + 16;    // bytes of an expanded row: 68 dwords, so 16 rows x 16 B cover the 64 banks once
+constexpr uint32_t kKnnNone = ~0u;    // (INT_MAX, -1)
+typedef int knn_i32x4 __attribute__((ext_vector_type(4)));
+
+// descriptor bits 4 d .. 4 d + 3 of w -> 4 bytes {0, 1}, byte j = bit 4 d + j: n (1 + 2^7 + 2^14 + 2^21) has bit j
+// of the nibble n at bit 8 j and the four shifted copies do not overlap
+__device__ __forceinline__ uint32_t knn_spread4(uint32_t w, int d) {
+    return omv_llvm_mul_u24((w >> (4 * d)) & 15u, 0x204081u) & 0x01010101u;
+}
+// 16 descriptor bits -> the 16 B fragment of one k-step; pm: {0, 1} -> {+1, -1}: 0x80 - y is 0x80 / 0x7f in every
+// byte with no borrow between bytes, the xor makes that 0x00 / 0xff, the or 0x01 / 0xff -- three full-rate ops
+template <bool pm>
+__device__ __forceinline__ knn_i32x4 knn_expand16(uint32_t bits) {
+    knn_i32x4 r;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const uint32_t y = knn_spread4(bits, d);
+        r[d] = (int)(pm ? ((0x80808080u - y) ^ 0x80808080u) | 0x01010101u : y);
+    }
+    return r;
+}
+__device__ __forceinline__ uint32_t knn_med3(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+// (two waves per SIMD asked for: at most 256 registers a lane, all VGPRs, so the distances are read where the MFMA
+// leaves them and not copied out of AGPRs)
+__global__ void __launch_bounds__(256, 2) knn2_mfma_kernel(KnnArgs a, int n_pairs) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[kKnnTile * kKnnRowB];
+    const int pair = blockIdx.y;
+    const int qo = a.q_off ? a.q_off[pair * a.pair_stride_off] : 0;
+    const int to = a.t_off ? a.t_off[pair * a.pair_stride_off] : 0;
+    const int nq = a.nq[pair * a.pair_stride_off] - qo;
+    const int nt = a.nt[pair * a.pair_stride_off] - to;
+    if ((int)blockIdx.x * 256 >= max(nq, 0)) return;   // block-uniform
+    const int lane = threadIdx.x & 63, c = lane & 15, h = lane >> 4;
+    const int qb = blockIdx.x * 256 + (threadIdx.x >> 6) * 64;   // the wave's first query
+    const bool live = qb < nq;                                   // wave-uniform: a wave past nq only stages
+    knn_i32x4 bq[4][4];   // [column tile][k-step]
+    int pq[4];
+    uint32_t k0[4], k1[4];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        const int qi = qb + 16 * ct + c;
+        uint64_t dq[4] = {0, 0, 0, 0};
+        if (qi < nq) omv::load_desc(a.q + pair * a.q_stride + (size_t)(qo + qi) * 32, dq);
+        pq[ct] = __popcll(dq[0]) + __popcll(dq[1]) + __popcll(dq[2]) + __popcll(dq[3]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) bq[ct][s] = knn_expand16<true>((uint32_t)(dq[s] >> (16 * h)) & 0xffffu);
+        k0[ct] = k1[ct] = kKnnNone;
+    }
+    const uint8_t *tbase = a.t + pair * a.t_stride + (size_t)to * 32;
+    const int sr = threadIdx.x >> 2, sw = threadIdx.x & 3;   // staging: train row of the tile, u64 word of its descriptor
+    auto score = [&](int b, auto full) {
+#pragma unroll
+        for (int rt = 0; rt < kKnnTile / 16; ++rt) {
+            knn_i32x4 ta[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                ta[s] = *reinterpret_cast<const knn_i32x4 *>(tile + (16 * rt + c) * kKnnRowB + s * 64 + h * 16);
+            const int row = b + 16 * rt + 4 * h;   // this lane's first train row of the row tile
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) {
+                knn_i32x4 acc = {pq[ct], pq[ct], pq[ct], pq[ct]};
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(ta[s], bq[ct][s], acc, 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    uint32_t k = ((uint32_t)acc[i] << 16) | (uint32_t)(row + i);
+                    if (!decltype(full)::value) k = row + i < nt ? k : kKnnNone;
+                    k1[ct] = knn_med3(k, k0[ct], k1[ct]);
+                    k0[ct] = min(k, k0[ct]);
+                }
+            }
+        }
+    };
+    for (int b = 0; b < nt; b += kKnnTile) {
+        __syncthreads();
+        {
+            const int j = b + sr;
+            const uint64_t v = j < nt ? *reinterpret_cast<const uint64_t *>(tbase + (size_t)j * 32 + sw * 8) : 0ull;
+            knn_i32x4 *dst = reinterpret_cast<knn_i32x4 *>(tile + sr * kKnnRowB + sw * 64);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dst[i] = knn_expand16<false>((uint32_t)(v >> (16 * i)) & 0xffffu);
+        }
+        __syncthreads();
+        if (!live) continue;
+        // block-uniform: only the last tile can hold rows past nt, and only there a key is checked against nt
+        if (b + kKnnTile <= nt) score(b, std::true_type{});
+        else score(b, std::false_type{});
+    }
+    if (!live) return;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        uint32_t m0 = k0[ct], m1 = k1[ct];
+#pragma unroll
+        for (int m = 16; m < 64; m <<= 1) {   // merge with the top-2 of the query's other row groups
+            const uint32_t o0 = __shfl_xor(m0, m, 64), o1 = __shfl_xor(m1, m, 64);
+            const uint32_t r0 = min(m0, o0);
+            const uint32_t r1 = m0 < o0 ? min(m1, o0) : min(m0, o1);
+            m0 = r0, m1 = r1;
+        }
+        const int qi = qb + 16 * ct + c;
+        if (qi < nq && h == 0) {
+            int32_t *oi = a.idx2 + ((size_t)pair * a.out_cap + qi) * 2;
+            int32_t *od = a.dist2 + ((size_t)pair * a.out_cap + qi) * 2;
+            oi[0] = m0 == kKnnNone ? -1 : (int32_t)(m0 & 0xffffu), oi[1] = m1 == kKnnNone ? -1 : (int32_t)(m1 & 0xffffu);
+            od[0] = m0 == kKnnNone ? INT_MAX : (int32_t)(m0 >> 16), od[1] = m1 == kKnnNone ? INT_MAX : (int32_t)(m1 >> 16);
+        }
+    }
+}
+
+// OMV_KNN: 0 by shape, 1 "mfma", 2 "lanes"; OMV_KNN_IDX_LIMIT: a surrogate for the packed key's 2^16 train rows
+// (tests of the fallback).  omv_matcher_create reads them into the handle's knobs; omv_bf_knn2 has no handle and
+// reads them per call.
+constexpr int kKnnIdxLimit = 1 << 16;
+static int knn_mode_env() {
+    const char *e = getenv("OMV_KNN");
+    return !e ? 0 : strcmp(e, "mfma") == 0 ? 1 : strcmp(e, "lanes") == 0 ? 2 : 0;
+}
+static int knn_idx_limit_env() {
+    const char *e = getenv("OMV_KNN_IDX_LIMIT");
+    const int v = e ? atoi(e) : 0;
+    return v > 0 && v < kKnnIdxLimit ? v : kKnnIdxLimit;
+}
+// The matrix-core kernel wherever the batch fills the chip with its 256-query blocks; a frame or three (the B = 1
+// chain) keeps the lane kernel, whose 8-query blocks spread 1,200 queries over 150 workgroups.  The packed key needs
+// nt < 2^16: a train capacity that does not promise it always takes the lane kernel.
+static bool knn_use_mfma(int mode, int idx_limit, int n_pairs, int q_cap, int t_cap) {
+    if (t_cap >= idx_limit) return false;
+    return mode == 1 || (mode == 0 && (long long)n_pairs * q_cap > 4096);
+}
+
+// Lane kernel: 8 lanes per query at every batch size: one frame (1,200 queries) needs the spread to fill the chip,
+// and at 128 frames the shorter per-lane chains and 8x the waves still win over one lane per query (0.150 vs 0.189 ms
+// per 128-frame launch; G = 2 / 4: 0.169 / 0.154).
+static void launch_knn2(const KnnArgs &a, int n_pairs, int q_cap, int t_cap, int mode, int idx_limit, hipStream_t st) {
+    if (knn_use_mfma(mode, idx_limit, n_pairs, q_cap, t_cap))
+        knn2_mfma_kernel<<<dim3((q_cap + 255) / 256, n_pairs), 256, 0, st>>>(a, n_pairs);
+    else if ((long long)n_pairs * q_cap <= 4096)   // a frame or three: 32 lanes per query, shorter chains
         knn2_kernel<32><<<dim3((q_cap + 7) / 8, n_pairs), 256, 0, st>>>(a, n_pairs);
     else
         knn2_kernel<8><<<dim3((q_cap + 31) / 32, n_pairs), 256, 0, st>>>(a, n_pairs);
@@ -2426,6 +2579,7 @@ omv_status omv_matcher_create(int max_frames, int n_cams, int kp_cap, int max_mp
     if (const char *e = getenv("OMV_TRI_WALK")) h->knobs.tri_walk_seq = strcmp(e, "seq") == 0 ? 1 : 0;
     if (const char *e = getenv("OMV_CAND")) h->knobs.cand_mode = strcmp(e, "global") == 0 ? 1 : strcmp(e, "lds") == 0 ? 2 : 0;
     if (const char *e = getenv("OMV_CAND_PW")) h->knobs.cand_pw = atoi(e);
+    h->knobs.knn_mode = knn_mode_env(), h->knobs.knn_idx_limit = knn_idx_limit_env();
     const size_t fc = (size_t)max_frames * n_cams;
     const size_t knn = (size_t)2 * max_frames * kp_cap;
     omv::DeviceArena &mem = h->mem;
@@ -2718,9 +2872,13 @@ omv_status omv_bf_knn2(int n_pairs, const uint8_t *query, int q_cap, const int *
     if (n_pairs <= 0 || !query || !train || !nq || !nt || !idx2 || !dist2 || q_cap <= 0 || t_cap <= 0)
         return OMV_ERR_ARG;
     KnnArgs a{query, train, (long long)q_cap * 32, (long long)t_cap * 32, nq, nt, nullptr, nullptr, 1, idx2, dist2, q_cap};
-    launch_knn2(a, n_pairs, q_cap, (hipStream_t)stream);
+    launch_knn2(a, n_pairs, q_cap, t_cap, knn_mode_env(), knn_idx_limit_env(), (hipStream_t)stream);
     HIP_OK(hipGetLastError());
     return OMV_OK;
+}
+
+int omv_bf_knn2_path(int n_pairs, int q_cap, int t_cap) {
+    return knn_use_mfma(knn_mode_env(), knn_idx_limit_env(), n_pairs, q_cap, t_cap) ? 1 : 0;
 }
 
 omv_status omv_matcher_stereo_lapping(omv_matcher *h, int n_frames, const uint8_t *desc, const int *n_kp,
@@ -2735,7 +2893,7 @@ omv_status omv_matcher_stereo_lapping(omv_matcher *h, int n_frames, const uint8_
     // query = camera 0 rows [mono0, n0), train = camera 1 rows [mono1, n1)
     KnnArgs a{desc, desc + (size_t)cap * 32, (long long)C * cap * 32, (long long)C * cap * 32, n_kp, n_kp + 1,
               mono, mono + 1, C, h->d_knn_i, h->d_knn_d, cap};
-    launch_knn2(a, n_frames, cap, st);
+    launch_knn2(a, n_frames, cap, cap, h->knobs.knn_mode, h->knobs.knn_idx_limit, st);
     dim3 g2((cap + 255) / 256, n_frames);
     stereo_pairs_kernel<<<g2, 256, 0, st>>>(h->d_knn_i, h->d_knn_d, cap, n_kp, mono, C, cap, ratio, l2r, r2l, n_frames);
     if (h->timing) h->ev.push_back({1, {e0, mk_event(st)}});

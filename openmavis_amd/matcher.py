@@ -511,3 +511,8 @@ def bf_knn2(query, nq, train, nt, stream=None):
     _lib.check(lib.omv_bf_knn2(P, _lib.ptr(query), Q, _lib.ptr(nq), _lib.ptr(train), train.shape[1], _lib.ptr(nt),
                                _lib.ptr(idx2), _lib.ptr(dist2), s), "omv_bf_knn2")
     return idx2, dist2
+
+
+def bf_knn2_path(n_pairs, q_cap, t_cap):
+    """The kernel bf_knn2 takes at this shape under the OMV_KNN / OMV_KNN_IDX_LIMIT knobs: "mfma" or "lanes"."""
+    return "mfma" if _lib.load().omv_bf_knn2_path(n_pairs, q_cap, t_cap) else "lanes"
