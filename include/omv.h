@@ -1197,6 +1197,9 @@ omv_status omv_selftest_inv16(int batch, const double *D, double *Dinv, int32_t 
  *   KB8_PROJECT / PINHOLE_PROJECT     a = X [n][3], b = k[8] -> uv [n][2]
  *   KB8_UNPROJECT / PINHOLE_UNPROJECT a = px [n][2], b = k[8] -> ray [n][3]
  *   PREDICT_SCALE a = ratio, b[0] = log scale factor -> int32 (int)ceil(log((double)a) / (double)b[0])
+ *   PREDICT_SCALE_CLAMPED the same with b[1] = the number of levels (as a float) -> int32 clamped to [0, levels - 1]
+ *   ROT_BIN (a = angle1, b = angle2) -> int32, the matchers' rotation-histogram bin
+ *   THREE_MAXIMA a = int32 histograms [n][30] -> int32 [n][3], ComputeThreeMaxima's indices (-1: absent)
  * An unknown fn, n < 0, or a NULL among the pointers fn reads with n > 0: OMV_ERR_ARG before any launch; n == 0:
  * OMV_OK. */
 #define OMV_MATH_SINCOSF 0
@@ -1215,6 +1218,9 @@ omv_status omv_selftest_inv16(int batch, const double *D, double *Dinv, int32_t 
 #define OMV_MATH_PINHOLE_PROJECT 13
 #define OMV_MATH_PINHOLE_UNPROJECT 14
 #define OMV_MATH_PREDICT_SCALE 15
+#define OMV_MATH_ROT_BIN 16
+#define OMV_MATH_THREE_MAXIMA 17
+#define OMV_MATH_PREDICT_SCALE_CLAMPED 18
 omv_status omv_selftest_math(int fn, int64_t n, const void *a, const void *b, const void *c, void *out, void *stream);
 
 /* One reduced-system solve on a handle after omv_lba_set_problem, at the current state: errors, build, assemble and

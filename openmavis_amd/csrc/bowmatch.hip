@@ -30,57 +30,11 @@
 
 namespace {
 
-constexpr int TH_LOW = 50, kHisto = 30;
+constexpr int TH_LOW = 50;
 constexpr int kMaxKp = 16384;      // keypoints per view (LDS claim bitmap + rotation bins)
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr int kFree = 0x7fffffff;
 std::atomic<int64_t> g_bow_rescans{0};   // walk rescans over all SearchByBoW calls (diagnostic)
-
-// rot = angle1 - angle2 (float), +360 if negative, bin = round(rot / 30) with 30 -> 0 (ORBmatcher.cc:475-481)
-__device__ __forceinline__ int rot_bin(float a1, float a2) {
-    const float factor = 1.0f / kHisto;
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * factor);
-    if (bin == kHisto) bin = 0;
-    return bin;
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d, 64));
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// ComputeThreeMaxima (ORBmatcher.cc:2537-2573)
-__device__ void three_maxima(const int *cnt, int *ind) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < kHisto; i++) {
-        const int s = cnt[i];
-        if (s > max1) {
-            max3 = max2, max2 = max1, max1 = s;
-            ind3 = ind2, ind2 = ind1, ind1 = i;
-        } else if (s > max2) {
-            max3 = max2, max2 = s;
-            ind3 = ind2, ind2 = i;
-        } else if (s > max3) {
-            max3 = s;
-            ind3 = i;
-        }
-    }
-    if (max2 < 0.1f * (float)max1) {
-        ind2 = -1, ind3 = -1;
-    } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-    }
-    ind[0] = ind1, ind[1] = ind2, ind[2] = ind3;
-}
 
 // camera block of a frame keypoint (ORBmatcher.cc:398-465): L [0, Nleft), R [Nleft, +Nright), SL, SR when the
 // frame has side cameras; a single-camera frame (Nleft == -1) has one block
@@ -167,7 +121,7 @@ __global__ void __launch_bounds__(256) bow_cand_kernel(const omv_bow_job *jobs, 
             const uint64_t *q2 = reinterpret_cast<const uint64_t *>(O.desc + 32 * (size_t)idx2);
             const uint64_t d2[4] = {q2[0], q2[1], q2[2], q2[3]};
             const int dist = omv::hamming256(d1, d2);
-            const int bin = rot_bin(K.kps[idx1].angle, O.kps[idx2].angle);   // static: both angles are fixed
+            const int bin = omv::rot_bin(K.kps[idx1].angle, O.kps[idx2].angle);   // static: both angles are fixed
             uint32_t kk = ((uint32_t)dist << 16) | (uint32_t)(p - o0),
                      ee = ((uint32_t)dist << 23) | ((uint32_t)bin << 16) | (uint32_t)idx2;
 #pragma unroll
@@ -224,9 +178,9 @@ __device__ void scan_node(const omv_kf_view &O, const uint32_t *claimed, const u
     }
 #pragma unroll
     for (int c = 0; c < NB; ++c) {
-        const uint32_t g = wave_min_u32(bk[c]);
+        const uint32_t g = omv::wave_min_u32(bk[c]);
         const uint32_t other = bk[c] == g ? (uint32_t)sec[c] : (bk[c] == kNone ? 256u : bk[c] >> 16);
-        bs[c] = (int)wave_min_u32(other);
+        bs[c] = (int)omv::wave_min_u32(other);
         bd[c] = g == kNone ? 256 : (int)(g >> 16);
         bi[c] = g == kNone ? -1 : O.node_idx[o0 + (int)(g & 0xffffu)];
     }
@@ -248,7 +202,7 @@ __global__ void __launch_bounds__(64 * W) bow_resolve_kernel(const omv_bow_job *
     constexpr int T = 64 * W, kChunkW = kChunk * W;
     __shared__ uint32_t recbuf[2][kChunkW * kRecWords];
     __shared__ int owner[kMaxKp];   // batch claims: the first batch keypoint claiming an other-view keypoint, or kFree
-    __shared__ int cnt[kHisto];
+    __shared__ int cnt[omv::kRotHistLen];
     __shared__ int ind[3];
     __shared__ int s_first, s_nm;
     constexpr int NB = MODE == OMV_BOW_KF_FRAME ? 4 : 1, S = T / NB;
@@ -263,7 +217,7 @@ __global__ void __launch_bounds__(64 * W) bow_resolve_kernel(const omv_bow_job *
     for (int i = tid; i < n_out; i += T) match[i] = -1, bins[i] = 0xff;
     for (int i = tid; i < (O.n + 31) / 32; i += T) claimed[i] = 0;
     for (int i = tid; i < O.n; i += T) owner[i] = kFree;
-    if (tid < kHisto) cnt[tid] = 0;
+    if (tid < omv::kRotHistLen) cnt[tid] = 0;
     if (tid == 0) s_first = INT_MAX, s_nm = 0;
     __syncthreads();
     // records staged through LDS a chunk at a time (one coalesced load per chunk, the next chunk in flight while
@@ -328,7 +282,7 @@ __global__ void __launch_bounds__(64 * W) bow_resolve_kernel(const omv_bow_job *
             scan_node<MODE, NB>(O, claimed, d1, o0, o1, lane, bd, bi, bs);
 #pragma unroll
             for (int cc = 0; cc < NB; ++cc)
-                bb[cc] = check_ori && bd[cc] <= TH_LOW ? rot_bin(K.kps[idx1].angle, O.kps[bi[cc]].angle) : 0;
+                bb[cc] = check_ori && bd[cc] <= TH_LOW ? omv::rot_bin(K.kps[idx1].angle, O.kps[bi[cc]].angle) : 0;
         } else {
 #pragma unroll
             for (int cc = 0; cc < NB; ++cc) {   // lane cc's pick, read into scalar registers
@@ -484,17 +438,17 @@ __global__ void __launch_bounds__(64 * W) bow_resolve_kernel(const omv_bow_job *
 #endif
 #undef OMV_TB
     if (check_ori) {
-        if (tid == 0) three_maxima(cnt, ind);
+        if (tid == 0) omv::three_maxima(cnt, ind);
         __syncthreads();
     }
     int removed = 0;
     for (int i = tid; i < n_out; i += T) {
         const int bn = bins[i];
-        const bool drop = check_ori && bn != 0xff && bn != ind[0] && bn != ind[1] && bn != ind[2];
+        const bool drop = check_ori && bn != 0xff && !omv::rot_bin_kept(bn, ind);
         removed += drop ? 1 : 0;
         J.match[i] = drop ? -1 : (int32_t)match[i];
     }
-    nm -= wave_sum_i32(removed);   // per wavefront: its commits (wave 0: also the lone walks) less its drops
+    nm -= omv::wave_sum_i32(removed);   // per wavefront: its commits (wave 0: also the lone walks) less its drops
     if (lane == 0) atomicAdd(&s_nm, nm);
     __syncthreads();
     if (tid == 0) n_matches[blockIdx.x] = s_nm;

@@ -1170,6 +1170,7 @@ __device__ __forceinline__ void run_domain(const ResolveArgs &a, const ResolveSh
     if (lane == 0 && frame < 2) printf("resolve frame %d domain %d first-round visit ticks %lld\n", frame, w, tp4);
 #endif
 #undef OMV_TP
+    // omv::wave_sum_i32 written out: through the helper the compiler allocates this whole kernel's registers anew
     for (int d = 32; d >= 1; d >>= 1) total += __shfl_xor(total, d, 64);
     if (lane == 0) atomicAdd(sh.total, total);
 }
@@ -1542,10 +1543,8 @@ __global__ void __launch_bounds__(256) frustum_kernel(const omv_frame_pose *pose
                 if (!(dist < minD || dist > maxD)) {
                     const float vc = (PO[0] * Pn[0] + PO[1] * Pn[1] + PO[2] * Pn[2]) / dist;
                     if (!(vc < cos_limit)) {
-                        const float ratio = maxd / dist;
-                        int ns = (int)ceil(log((double)ratio) / (double)rig.log_scale_factor);
-                        ns = ns < 0 ? 0 : (ns >= rig.n_levels ? rig.n_levels - 1 : ns);
-                        px = u, py = v, lvl = ns, vis = true;
+                        px = u, py = v, lvl = omv::predict_scale(maxd / dist, rig.log_scale_factor, rig.n_levels);
+                        vis = true;
                         out.view_cos[o] = vc;
                         if (c == 0) out.track_depth[fm] = Pc_dist;
                     }
@@ -1741,11 +1740,7 @@ __global__ void __launch_bounds__(64) lf_resolve_kernel(LfResolveArgs a) {
                         const int slot = c * cap + best;
                         if (!obs && bit_of(bits, slot)) unblock = true;
                         claim[nclaim] = slot;
-                        float rot = a.L.kps[fs].angle - f.kps[(size_t)frame * S + slot].angle;
-                        if (rot < 0.0f) rot += 360.0f;
-                        int b = (int)roundf(rot * (1.0f / 30));
-                        if (b == 30) b = 0;
-                        bin[nclaim++] = b;
+                        bin[nclaim++] = omv::rot_bin(a.L.kps[fs].angle, f.kps[(size_t)frame * S + slot].angle);
                     }
                 }
             }
@@ -1812,39 +1807,24 @@ __global__ void __launch_bounds__(64) lf_resolve_kernel(LfResolveArgs a) {
 // (second / third only when >= 10% of the first), undo every claim pushed into another bin.
 __global__ void __launch_bounds__(256) lf_histo_kernel(const int2 *pushes, const int *n_push, int per_frame,
                                                        int S, int32_t *kp_to_mp, int *n_matches) {
-    __shared__ int hist[30];
+    __shared__ int hist[omv::kRotHistLen];
     __shared__ int keep[3];
     __shared__ int removed;
     const int frame = blockIdx.x;
     const int n = n_push[frame];
     const int2 *p = pushes + (size_t)frame * per_frame;
-    if (threadIdx.x < 30) hist[threadIdx.x] = 0;
+    if (threadIdx.x < omv::kRotHistLen) hist[threadIdx.x] = 0;
     if (threadIdx.x == 0) removed = 0;
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += blockDim.x) atomicAdd(&hist[p[i].y], 1);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < 30; i++) {
-            const int sz = hist[i];
-            if (sz > max1) {
-                max3 = max2, max2 = max1, max1 = sz, ind3 = ind2, ind2 = ind1, ind1 = i;
-            } else if (sz > max2) {
-                max3 = max2, max2 = sz, ind3 = ind2, ind2 = i;
-            } else if (sz > max3) {
-                max3 = sz, ind3 = i;
-            }
-        }
-        if (max2 < 0.1f * (float)max1) ind2 = -1, ind3 = -1;
-        else if (max3 < 0.1f * (float)max1) ind3 = -1;
-        keep[0] = ind1, keep[1] = ind2, keep[2] = ind3;
-    }
+    if (threadIdx.x == 0) omv::three_maxima(hist, keep);
     __syncthreads();
     int32_t *k2m = kp_to_mp + (size_t)frame * S;
     int rm = 0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const int b = p[i].y;
-        if (b != keep[0] && b != keep[1] && b != keep[2]) {
+        if (!omv::rot_bin_kept(b, keep)) {
             k2m[p[i].x] = -1;
             ++rm;
         }
@@ -1949,8 +1929,7 @@ __global__ void __launch_bounds__(256) kf_cand_kernel(KfArgs a) {
             const float *Pn = a.mps.normal + 3 * (size_t)mp;
             if ((double)(PO[0] * Pn[0] + PO[1] * Pn[1] + PO[2] * Pn[2]) < 0.5 * (double)dist3D) break;
         }
-        int pred = (int)ceil(log((double)(maxd / dist3D)) / (double)a.log_scale);   // MapPoint::PredictScale
-        pred = pred < 0 ? 0 : (pred >= a.n_levels ? a.n_levels - 1 : pred);
+        const int pred = omv::predict_scale(maxd / dist3D, a.log_scale, a.n_levels);
         const float radius = a.th * a.f.scale[pred];
         int minL, maxL;
         kf_levels(mode, pred, minL, maxL);
@@ -1993,17 +1972,9 @@ __global__ void __launch_bounds__(256) kf_cand_kernel(KfArgs a) {
     a.geo[e] = g;
 }
 
-// Rotation bin of a SearchByProjection(Frame&, KF, ...) match (:2502-2510).
-__device__ __forceinline__ int kf_rot_bin(float kf_angle, float frame_angle) {
-    float rot = kf_angle - frame_angle;
-    if (rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * (1.0f / 30));
-    return bin == 30 ? 0 : bin;
-}
-
 __global__ void __launch_bounds__(64) kf_resolve_kernel(KfArgs a) {
     extern __shared__ uint32_t claimed[];
-    __shared__ int hist[30];
+    __shared__ int hist[omv::kRotHistLen];
     const int kf = blockIdx.x, lane = threadIdx.x;
     const int C = a.f.n_cams, cap = a.f.kp_cap, S = C * cap, W = (S + 31) / 32;
     int32_t *cl = a.kp_match + (size_t)kf * S;
@@ -2023,7 +1994,7 @@ __global__ void __launch_bounds__(64) kf_resolve_kernel(KfArgs a) {
         const int cam = J.cam, off = kf_block_offset(a.f, kf, cam);
         const omv_kp *kk = a.f.kps + (size_t)kf * S;
         int nm = 0;
-        if (lane < 30) hist[lane] = 0;
+        if (lane < omv::kRotHistLen) hist[lane] = 0;
         omv::wave_lds_sync();
         for (int e = J.mp_start; e < J.mp_start + J.mp_count; ++e) {
             const int cnt = a.counts[e];
@@ -2058,7 +2029,7 @@ __global__ void __launch_bounds__(64) kf_resolve_kernel(KfArgs a) {
                     claimed[slot >> 5] |= 1u << (slot & 31);
                     cl[slot] = a.mp_list[e];
                     a.best_idx[e] = off + idx, a.best_dist[e] = dist;
-                    if (ori) ++hist[kf_rot_bin(a.mp_angle[e], kk[slot].angle)];
+                    if (ori) ++hist[omv::rot_bin(a.mp_angle[e], kk[slot].angle)];
                 } else {
                     a.best_idx[e] = -1, a.best_dist[e] = -1;
                 }
@@ -2066,23 +2037,16 @@ __global__ void __launch_bounds__(64) kf_resolve_kernel(KfArgs a) {
             nm += ok ? 1 : 0;
             omv::wave_lds_sync();
         }
-        if (ori) {   // ComputeThreeMaxima (:2537-2573), then un-claim the matches outside the top bins
+        if (ori) {   // ComputeThreeMaxima, then un-claim the matches outside the top bins
             if (lane == 0) {
-                int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-                for (int i = 0; i < 30; i++) {
-                    const int sz = hist[i];
-                    if (sz > max1) max3 = max2, max2 = max1, max1 = sz, ind3 = ind2, ind2 = ind1, ind1 = i;
-                    else if (sz > max2) max3 = max2, max2 = sz, ind3 = ind2, ind2 = i;
-                    else if (sz > max3) max3 = sz, ind3 = i;
-                }
-                if (max2 < 0.1f * (float)max1) ind2 = -1, ind3 = -1;
-                else if (max3 < 0.1f * (float)max1) ind3 = -1;
+                int ind[3];
+                omv::three_maxima(hist, ind);
                 for (int e = J.mp_start; e < J.mp_start + J.mp_count; ++e) {
                     const int bi = a.best_idx[e];
                     if (bi < 0) continue;
                     const int slot = cam * cap + (bi - off);
-                    const int bin = kf_rot_bin(a.mp_angle[e], kk[slot].angle);
-                    if (bin == ind1 || bin == ind2 || bin == ind3) continue;
+                    const int bin = omv::rot_bin(a.mp_angle[e], kk[slot].angle);
+                    if (omv::rot_bin_kept(bin, ind)) continue;
                     claimed[slot >> 5] &= ~(1u << (slot & 31));
                     cl[slot] = -1;
                     a.best_idx[e] = -1, a.best_dist[e] = -1;
@@ -2162,8 +2126,7 @@ __global__ void __launch_bounds__(256) sbs3_cand_kernel(Sim3Args a) {
         const float maxDistance = 1.2f * maxd, minDistance = 0.8f * a.mps.min_dist[mp];
         const float dist3D = omv::sqrtf_cr(Pt[0] * Pt[0] + Pt[1] * Pt[1] + Pt[2] * Pt[2]);
         if (dist3D < minDistance || dist3D > maxDistance) break;
-        int pred = (int)ceil(log((double)(maxd / dist3D)) / (double)a.log_scale);   // MapPoint::PredictScale
-        pred = pred < 0 ? 0 : (pred >= a.n_levels ? a.n_levels - 1 : pred);
+        const int pred = omv::predict_scale(maxd / dist3D, a.log_scale, a.n_levels);
         const float radius = a.th * a.f.scale[pred];
         uint64_t dmp[4];
         omv::load_desc(a.mps.desc + (size_t)mp * 32, dmp);
@@ -2217,12 +2180,6 @@ struct InitArgs {
 
 constexpr int kInitChunk = 256;   // F1 keypoints whose speculative keys are staged in LDS at a time
 __host__ __device__ inline size_t init_lds_bytes(int cap) { return kInitChunk * 64 + (size_t)cap * 17 + 4 * 36 + 16; }
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d, 64));
-    return v;
-}
 
 constexpr uint32_t kNoKey = 0xffffffffu;
 constexpr int kInitSpec = 8;   // speculative keys kept per F1 keypoint (two uint4 of keys, two of F2 indices)
@@ -2288,7 +2245,7 @@ __device__ __forceinline__ void init_window_scan(const FrameArgs &f, const int32
     }
 #pragma unroll
     for (int t = 0; t < K; ++t) {   // K rounds of wave minimum over the lanes' heads, the winner pops its head
-        const uint32_t m = wave_min_u32(kk[0]);
+        const uint32_t m = omv::wave_min_u32(kk[0]);
         if (m == kNoKey) return;
         const int src = __ffsll((long long)__ballot(kk[0] == m)) - 1;
         ok[t] = m, oi[t] = __shfl(ii[0], src, 64);
@@ -2336,7 +2293,7 @@ __global__ void __launch_bounds__(64) init_kernel(InitArgs a) {
     int *ism = ism_raw + kInitChunk * 16;
     int *mdist = ism, *m21 = ism + cap, *m12 = ism + 2 * cap;
     int *acc2 = ism + 3 * cap;   // [n1] the F2 keypoint F1 keypoint i1 was accepted with (rotHist push), or -1
-    int *cnt = ism + 4 * cap, *ind = cnt + 30;
+    int *cnt = ism + 4 * cap, *ind = cnt + omv::kRotHistLen;
     uint8_t *bins = reinterpret_cast<uint8_t *>(ind + 4);
     const size_t fc1 = (size_t)a.pairs[2 * pr] * f.n_cams, fc2 = (size_t)a.pairs[2 * pr + 1] * f.n_cams;   // block 0
     const int n1 = f.n_kp[fc1], n2 = f.n_kp[fc2];
@@ -2347,7 +2304,7 @@ __global__ void __launch_bounds__(64) init_kernel(InitArgs a) {
     const uint4 *spec = a.spec + (size_t)pr * cap * 4;
     for (int i = lane; i < n1; i += 64) m12[i] = -1, acc2[i] = -1, bins[i] = 0xff;
     for (int i = lane; i < n2; i += 64) mdist[i] = INT_MAX, m21[i] = -1;
-    if (lane < 30) cnt[lane] = 0;
+    if (lane < omv::kRotHistLen) cnt[lane] = 0;
     __syncthreads();
     const float r = (float)a.window;
     int nm = 0;
@@ -2416,45 +2373,19 @@ __global__ void __launch_bounds__(64) init_kernel(InitArgs a) {
         for (int i = lane; i < n1; i += 64) {
             const int j = acc2[i];
             if (j < 0) continue;
-            float rot = kp1[i].angle - kp2[j].angle;   // rot = angle1 - angle2, +360 if negative
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / 30));   // bin = round(rot / 30), 30 -> 0
-            if (bin == 30) bin = 0;
+            const int bin = omv::rot_bin(kp1[i].angle, kp2[j].angle);
             bins[i] = (uint8_t)bin;
             atomicAdd(cnt + bin, 1);
         }
         __syncthreads();
-        if (lane == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < 30; i++) {
-                const int s = cnt[i];
-                if (s > max1) {
-                    max3 = max2, max2 = max1, max1 = s;
-                    ind3 = ind2, ind2 = ind1, ind1 = i;
-                } else if (s > max2) {
-                    max3 = max2, max2 = s;
-                    ind3 = ind2, ind2 = i;
-                } else if (s > max3) {
-                    max3 = s;
-                    ind3 = i;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) {
-                ind2 = -1, ind3 = -1;
-            } else if (max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-            ind[0] = ind1, ind[1] = ind2, ind[2] = ind3;
-        }
+        if (lane == 0) omv::three_maxima(cnt, ind);
         __syncthreads();
         int removed = 0;
         for (int i = lane; i < n1; i += 64) {
             const int bn = bins[i];
-            if (bn != 0xff && bn != ind[0] && bn != ind[1] && bn != ind[2] && m12[i] >= 0) m12[i] = -1, ++removed;
+            if (bn != 0xff && !omv::rot_bin_kept(bn, ind) && m12[i] >= 0) m12[i] = -1, ++removed;
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) removed += __shfl_xor(removed, d, 64);
-        nm -= removed;
+        nm -= omv::wave_sum_i32(removed);
         __syncthreads();
     }
     int32_t *out = a.m12 + (size_t)pr * cap;

@@ -37,6 +37,18 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Butterfly reductions over the 64 lanes of a wavefront (every lane active): all lanes get the result.
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
 // 1 / x by v_rcp_f64 and two Newton steps (within an ulp of the IEEE quotient on normal numbers; a zero / non-finite
 // argument is the caller's to flag)
 __device__ __forceinline__ double rcp_nr(double x) {

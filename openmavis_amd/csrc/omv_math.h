@@ -1,5 +1,6 @@
 // The pure float arithmetic under every bit-exact claim: rounding, cv::fastAtan2, the glibc sincosf / atanf / atan2f /
-// tanf restatements, the correctly rounded sqrtf and the reference's float camera models.  Nothing in the bodies is
+// tanf restatements, the correctly rounded sqrtf, the reference's float camera models, the matchers' rotation check
+// (rot_bin, three_maxima) and MapPoint::PredictScale.  Nothing in the bodies is
 // HIP-specific, so one text is compiled twice: by hipcc into every kernel (through omv_device.h / omv_camera.h), and by
 // the host compiler into the oracle library (oracle/math_host.cpp), where it is compared bit for bit with glibc
 // itself (tests/test_math_header_cpu.py) and with its own device build (omv_selftest_math,
@@ -310,6 +311,54 @@ OMV_MATH_FN void cam_unproject_f(int model, const float *k, float px, float py, 
 OMV_MATH_FN void cam_project_f(int model, const float *k, const float *X, float &u, float &v) {
     if (model == OMV_CAM_PINHOLE) pinhole_project_f(k, X, u, v);
     else kb8_project_f(k, X, u, v);
+}
+
+// ---- the matchers' rotation-consistency check and MapPoint::PredictScale: one definition for every search, tested
+// directly on both compilers (tests/test_math_header_cpu.py, tests/test_math_device_gpu.py).
+constexpr int kRotHistLen = 30;   // HISTO_LENGTH
+
+// The histogram bin of a match: rot = angle1 - angle2 (float), +360 if negative, bin = round(rot * factor) with
+// factor = 1.0f / HISTO_LENGTH and HISTO_LENGTH -> 0 (ORBmatcher.cc:475-481 and its five siblings)
+OMV_MATH_FN int rot_bin(float a1, float a2) {
+    float rot = a1 - a2;
+    if (rot < 0.0f) rot += 360.0f;
+    const int bin = (int)roundf(rot * (1.0f / kRotHistLen));
+    return bin == kRotHistLen ? 0 : bin;
+}
+
+// ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:2537-2573): the indices of the three largest bins (strict >, so the
+// first of equal bins wins), the second / third only when at least 10 % of the first; -1 for an absent index.
+OMV_MATH_FN void three_maxima(const int *hist, int ind[3]) {
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int i = 0; i < kRotHistLen; i++) {
+        const int s = hist[i];
+        if (s > max1) {
+            max3 = max2, max2 = max1, max1 = s;
+            ind3 = ind2, ind2 = ind1, ind1 = i;
+        } else if (s > max2) {
+            max3 = max2, max2 = s;
+            ind3 = ind2, ind2 = i;
+        } else if (s > max3) {
+            max3 = s;
+            ind3 = i;
+        }
+    }
+    const float tenth = 0.1f * (float)max1;
+    if (max2 < tenth) ind2 = -1, ind3 = -1;
+    else if (max3 < tenth) ind3 = -1;
+    ind[0] = ind1, ind[1] = ind2, ind[2] = ind3;
+}
+// Whether a match in `bin` survives the check.
+OMV_MATH_FN bool rot_bin_kept(int bin, const int ind[3]) { return bin == ind[0] || bin == ind[1] || bin == ind[2]; }
+
+// MapPoint::PredictScale (MapPoint.cc:624-637): ratio = mfMaxDistance / currentDist, log in double; the level before
+// and after the clamp to [0, n_levels - 1]
+OMV_MATH_FN int predict_scale_raw(float ratio, float log_scale_factor) {
+    return (int)ceil(log((double)ratio) / (double)log_scale_factor);
+}
+OMV_MATH_FN int predict_scale(float ratio, float log_scale_factor, int n_levels) {
+    const int s = predict_scale_raw(ratio, log_scale_factor);
+    return s < 0 ? 0 : (s >= n_levels ? n_levels - 1 : s);
 }
 
 }  // namespace omv

@@ -9,8 +9,8 @@
 
 namespace omv {
 
-// element sizes (bytes per element of a / b / c / out; 0: not read).  b of the camera codes is one k[8] and b of
-// PREDICT_SCALE one float, shared by every element.
+// element sizes (bytes per element of a / b / c / out; 0: not read).  b of the camera codes is one k[8], b of
+// PREDICT_SCALE one float and of PREDICT_SCALE_CLAMPED two, shared by every element.
 struct MathShape {
     int a, b, c, out;
     bool b_shared;
@@ -33,6 +33,9 @@ inline bool math_shape(int fn, MathShape *s) {
         case OMV_MATH_KB8_UNPROJECT:
         case OMV_MATH_PINHOLE_UNPROJECT: *s = {8, 32, 0, 12, true}; return true;
         case OMV_MATH_PREDICT_SCALE: *s = {4, 4, 0, 4, true}; return true;
+        case OMV_MATH_PREDICT_SCALE_CLAMPED: *s = {4, 8, 0, 4, true}; return true;
+        case OMV_MATH_ROT_BIN: *s = {4, 4, 0, 4, false}; return true;
+        case OMV_MATH_THREE_MAXIMA: *s = {4 * kRotHistLen, 0, 0, 12, false}; return true;
         default: return false;
     }
 }
@@ -42,6 +45,7 @@ OMV_MATH_FN void math_map_one(int fn, int64_t i, const void *a, const void *b, c
     const double *ad = (const double *)a, *bd = (const double *)b, *cd = (const double *)c;
     float *of = (float *)out;
     double *od = (double *)out;
+    const int32_t *ai = (const int32_t *)a;
     int32_t *oi = (int32_t *)out;
     switch (fn) {
         case OMV_MATH_SINCOSF: glibc_sincosf(af[i], of + 2 * i, of + 2 * i + 1); break;
@@ -63,8 +67,10 @@ OMV_MATH_FN void math_map_one(int fn, int64_t i, const void *a, const void *b, c
         case OMV_MATH_KB8_UNPROJECT: kb8_unproject_f(bf, af[2 * i], af[2 * i + 1], of + 3 * i); break;
         case OMV_MATH_PINHOLE_PROJECT: pinhole_project_f(bf, af + 3 * i, of[2 * i], of[2 * i + 1]); break;
         case OMV_MATH_PINHOLE_UNPROJECT: pinhole_unproject_f(bf, af[2 * i], af[2 * i + 1], of + 3 * i); break;
-        // MapPoint::PredictScale as match.hip writes it
-        case OMV_MATH_PREDICT_SCALE: oi[i] = (int)ceil(log((double)af[i]) / (double)bf[0]); break;
+        case OMV_MATH_PREDICT_SCALE: oi[i] = predict_scale_raw(af[i], bf[0]); break;
+        case OMV_MATH_PREDICT_SCALE_CLAMPED: oi[i] = predict_scale(af[i], bf[0], (int)bf[1]); break;
+        case OMV_MATH_ROT_BIN: oi[i] = rot_bin(af[i], bf[i]); break;
+        case OMV_MATH_THREE_MAXIMA: three_maxima(ai + kRotHistLen * i, oi + 3 * i); break;
         default: break;
     }
 }

@@ -50,6 +50,9 @@ extern "C" omv_status omv_selftest_math(int fn, int64_t n, const void *a, const 
         OMV_MATH_CASE(OMV_MATH_PINHOLE_PROJECT)
         OMV_MATH_CASE(OMV_MATH_PINHOLE_UNPROJECT)
         OMV_MATH_CASE(OMV_MATH_PREDICT_SCALE)
+        OMV_MATH_CASE(OMV_MATH_PREDICT_SCALE_CLAMPED)
+        OMV_MATH_CASE(OMV_MATH_ROT_BIN)
+        OMV_MATH_CASE(OMV_MATH_THREE_MAXIMA)
 #undef OMV_MATH_CASE
         default: return OMV_ERR_ARG;
     }

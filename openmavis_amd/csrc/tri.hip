@@ -42,7 +42,6 @@
 namespace {
 
 constexpr int kTriLow = 50;          // ORBmatcher::TH_LOW
-constexpr int kHisto = 30;           // HISTO_LENGTH
 constexpr int kTriMaxKp = 16384;     // keypoints of keyframe 1 (orientation bins, 1 byte each; < 2^16)
 constexpr int kTriThreads = 512;
 constexpr int kTriWaves = kTriThreads / 64;
@@ -308,6 +307,40 @@ __device__ __forceinline__ T block_scan_excl(T v, T id, Op op, T *s_w, T &total)
     return op(pre, ex);
 }
 
+// A finished row of the replay: its match and, for the rotation check, its histogram bin.
+__device__ __forceinline__ void write_row(const omv_tri_pair &P, int check_ori, uint8_t *bins, int row, int best) {
+    P.match12[row] = best;
+    if (check_ori) bins[row] = (uint8_t)omv::rot_bin(P.kf1.kps[row].angle, P.kf2.kps[best].angle);
+}
+
+// The rotation check over the rows written (every thread of the NT-thread block calls it; hist zeroed): keep the three
+// largest bins (ComputeThreeMaxima), un-match the rows in the others and take their number off thread 0's nmatch.
+template <int NT>
+__device__ __forceinline__ void rotation_filter(const omv_tri_pair &P, const uint8_t *bins, int *hist, int *s_keep,
+                                                int *s_wi, int &nmatch) {
+    const int tid = threadIdx.x, n = P.kf1.n;
+    for (int i = tid; i < n; i += NT)
+        if (bins[i] != 0xff) atomicAdd(&hist[bins[i]], 1);
+    __syncthreads();
+    if (tid == 0) {
+        int ind[3];
+        omv::three_maxima(hist, ind);
+        for (int i = 0; i < omv::kRotHistLen; ++i) s_keep[i] = omv::rot_bin_kept(i, ind) ? 1 : 0;
+    }
+    __syncthreads();
+    int removed = 0;
+    for (int i = tid; i < n; i += NT)
+        if (bins[i] != 0xff && !s_keep[bins[i]]) P.match12[i] = -1, ++removed;
+    removed = omv::wave_sum_i32(removed);
+    if ((tid & 63) == 0) s_wi[tid >> 6] = removed;
+    __syncthreads();
+    if (tid == 0) {
+        int tot = 0;
+        for (int w = 0; w < NT / 64; ++w) tot += s_wi[w];
+        nmatch -= tot;
+    }
+}
+
 // compacted candidate code: distance bits 0-5, listed bit 6, camera pair bits 8-11
 constexpr uint16_t kCodeListed = 0x40;
 
@@ -439,8 +472,8 @@ __global__ void __launch_bounds__(kTriThreads) tri_kernel(const omv_tri_pair *pa
     __shared__ int v_item[kVal + 1];
     __shared__ int s_wi[kTriWaves];
     __shared__ unsigned s_wu[kTriWaves];
-    __shared__ int hist[kHisto];
-    __shared__ int s_keep[kHisto];
+    __shared__ int hist[omv::kRotHistLen];
+    __shared__ int s_keep[omv::kRotHistLen];
     __shared__ int s_state, s_row, s_best, s_bidx, s_fin;
     if (only && !only[blockIdx.x]) return;
     if (gate_skip(gate)) return;   // the walk wrote the skipped neighbour's empty result
@@ -453,7 +486,7 @@ __global__ void __launch_bounds__(kTriThreads) tri_kernel(const omv_tri_pair *pa
         return;
     }
     for (int i = tid; i < K1.n; i += kTriThreads) bins[i] = 0xff;
-    if (tid < kHisto) hist[tid] = 0;
+    if (tid < omv::kRotHistLen) hist[tid] = 0;
     if (tid == 0) s_state = 0, s_row = -1, s_best = kTriLow, s_bidx = -1;   // camera-pair state: LL before any assignment
     __syncthreads();
     auto add = [](int x, int y) { return x + y; };
@@ -461,15 +494,8 @@ __global__ void __launch_bounds__(kTriThreads) tri_kernel(const omv_tri_pair *pa
     // the row the walk has open when it ends (its best match, if any, is written like a finished row)
     auto finish_row = [&](int row, int best) {
         if (row < 0 || best < 0) return;
-        P.match12[row] = best;
+        write_row(P, check_ori, bins, row, best);
         ++nmatch;
-        if (check_ori) {
-            float rot = K1.kps[row].angle - K2.kps[best].angle;
-            if ((double)rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / kHisto));
-            if (bin == kHisto) bin = 0;
-            bins[row] = (uint8_t)bin;
-        }
     };
     int n_valid = 0;
 #ifdef OMV_TRI_PROFILE
@@ -598,15 +624,7 @@ __global__ void __launch_bounds__(kTriThreads) tri_kernel(const omv_tri_pair *pa
         const int n_fin = s_fin;
         nmatch += n_fin;   // thread 0's count (the only one read)
         for (int i = tid; i < n_fin; i += kTriThreads) {
-            const int row = (int)((uint32_t)v_item[i] >> 16), best = v_item[i] & 0xffff;
-            P.match12[row] = best;
-            if (check_ori) {
-                float rot = K1.kps[row].angle - K2.kps[best].angle;
-                if ((double)rot < 0.0) rot += 360.0f;
-                int bin = (int)roundf(rot * (1.0f / kHisto));
-                if (bin == kHisto) bin = 0;
-                bins[row] = (uint8_t)bin;
-            }
+            write_row(P, check_ori, bins, (int)((uint32_t)v_item[i] >> 16), v_item[i] & 0xffff);
         }
         __syncthreads();
         OMV_TQ(0);
@@ -618,37 +636,7 @@ __global__ void __launch_bounds__(kTriThreads) tri_kernel(const omv_tri_pair *pa
     flush();
     if (tid == 0) finish_row(s_row, s_bidx);
     __syncthreads();
-    if (check_ori) {   // rotation histogram: keep the three largest bins (ComputeThreeMaxima, :2537-2573)
-        for (int i = tid; i < K1.n; i += kTriThreads)
-            if (bins[i] != 0xff) atomicAdd(&hist[bins[i]], 1);
-        __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < kHisto; i++) {
-                const int s = hist[i];
-                if (s > max1) {
-                    max3 = max2, max2 = max1, max1 = s;
-                    ind3 = ind2, ind2 = ind1, ind1 = i;
-                } else if (s > max2) {
-                    max3 = max2, max2 = s;
-                    ind3 = ind2, ind2 = i;
-                } else if (s > max3) {
-                    max3 = s;
-                    ind3 = i;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) ind2 = -1, ind3 = -1;
-            else if (max3 < 0.1f * (float)max1) ind3 = -1;
-            for (int i = 0; i < kHisto; ++i) s_keep[i] = (i == ind1 || i == ind2 || i == ind3) ? 1 : 0;
-        }
-        __syncthreads();
-        int removed = 0;
-        for (int i = tid; i < K1.n; i += kTriThreads)
-            if (bins[i] != 0xff && !s_keep[bins[i]]) P.match12[i] = -1, ++removed;
-        int tot;
-        block_scan_excl(removed, 0, add, s_wi, tot);
-        if (tid == 0) nmatch -= tot;
-    }
+    if (check_ori) rotation_filter<kTriThreads>(P, bins, hist, s_keep, s_wi, nmatch);
     if (tid == 0) n_matches[blockIdx.x] = nmatch;
 #ifdef OMV_TRI_PROFILE
     OMV_TQ(1);
@@ -816,7 +804,7 @@ __global__ void __launch_bounds__(kWalkThreads) tri_walk_kernel(const omv_tri_pa
     __shared__ uint8_t bins[kTriMaxKp];
     __shared__ int fin[kTriMaxKp];   // finished rows: the global entry index of the row's best (parallel replay: rows)
     __shared__ uint8_t instate[kWalkRows + 64];
-    __shared__ int hist[kHisto], s_keep[kHisto], s_wi[kWalkThreads / 64], s_fin, s_rows;
+    __shared__ int hist[omv::kRotHistLen], s_keep[omv::kRotHistLen], s_wi[kWalkThreads / 64], s_fin, s_rows;
     const int p = blockIdx.x, tid = threadIdx.x, S = ws.S;
     const omv_tri_pair &P = pairs[p];
     const omv_kf_view &K1 = P.kf1, &K2 = P.kf2;
@@ -832,7 +820,7 @@ __global__ void __launch_bounds__(kWalkThreads) tri_walk_kernel(const omv_tri_pa
         return;
     }
     for (int i = tid; i < K1.n; i += kWalkThreads) bins[i] = 0xff;
-    if (tid < kHisto) hist[tid] = 0;
+    if (tid < omv::kRotHistLen) hist[tid] = 0;
     auto add = [](int x, int y) { return x + y; };
     // rows of the pair (entries with the row-start bit)
     int nr = 0;
@@ -840,7 +828,7 @@ __global__ void __launch_bounds__(kWalkThreads) tri_walk_kernel(const omv_tri_pa
         const int slot = p * S + sl, base = slot * ws.ecap, n = ws.cnt[slot];
         for (int k = tid; k < n; k += kWalkThreads) nr += (ws.w[base + k] >> 11) & 1u;
     }
-    for (int d = 32; d >= 1; d >>= 1) nr += __shfl_xor(nr, d, 64);
+    nr = omv::wave_sum_i32(nr);
     if ((tid & 63) == 0) s_wi[tid >> 6] = nr;
     __syncthreads();
     const int R = s_wi[0] + s_wi[1] + s_wi[2] + s_wi[3];
@@ -911,17 +899,10 @@ __global__ void __launch_bounds__(kWalkThreads) tri_walk_kernel(const omv_tri_pa
 #ifdef OMV_TRI_CHECK
             if (row >= K1.n || best >= K2.n) { printf("walk bad row %d best %d bk %d r %d\n", row, best, bk, r); continue; }
 #endif
-            P.match12[row] = best;
+            write_row(P, check_ori, bins, row, best);
             ++nmatch;
-            if (check_ori) {
-                float rot = K1.kps[row].angle - K2.kps[best].angle;
-                if ((double)rot < 0.0) rot += 360.0f;
-                int bin = (int)roundf(rot * (1.0f / kHisto));
-                if (bin == kHisto) bin = 0;
-                bins[row] = (uint8_t)bin;
-            }
         }
-        for (int d = 32; d >= 1; d >>= 1) nmatch += __shfl_xor(nmatch, d, 64);
+        nmatch = omv::wave_sum_i32(nmatch);
         if ((tid & 63) == 0) s_wi[tid >> 6] = nmatch;
         __syncthreads();
         nmatch = s_wi[0] + s_wi[1] + s_wi[2] + s_wi[3];
@@ -969,54 +950,11 @@ __global__ void __launch_bounds__(kWalkThreads) tri_walk_kernel(const omv_tri_pa
     nmatch = n_fin;
     for (int i = tid; i < n_fin; i += kWalkThreads) {
         const uint32_t pk = ws.pk[fin[i]];
-        const int row = (int)(pk >> 16), best = (int)(pk & 0xffff);
-        P.match12[row] = best;
-        if (check_ori) {
-            float rot = K1.kps[row].angle - K2.kps[best].angle;
-            if ((double)rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / kHisto));
-            if (bin == kHisto) bin = 0;
-            bins[row] = (uint8_t)bin;
-        }
+        write_row(P, check_ori, bins, (int)(pk >> 16), (int)(pk & 0xffff));
     }
     }
     __syncthreads();
-    if (check_ori) {   // rotation histogram: keep the three largest bins (ComputeThreeMaxima, :2537-2573)
-        for (int i = tid; i < K1.n; i += kWalkThreads)
-            if (bins[i] != 0xff) atomicAdd(&hist[bins[i]], 1);
-        __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < kHisto; i++) {
-                const int sv = hist[i];
-                if (sv > max1) {
-                    max3 = max2, max2 = max1, max1 = sv;
-                    ind3 = ind2, ind2 = ind1, ind1 = i;
-                } else if (sv > max2) {
-                    max3 = max2, max2 = sv;
-                    ind3 = ind2, ind2 = i;
-                } else if (sv > max3) {
-                    max3 = sv;
-                    ind3 = i;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) ind2 = -1, ind3 = -1;
-            else if (max3 < 0.1f * (float)max1) ind3 = -1;
-            for (int i = 0; i < kHisto; ++i) s_keep[i] = (i == ind1 || i == ind2 || i == ind3) ? 1 : 0;
-        }
-        __syncthreads();
-        int removed = 0;
-        for (int i = tid; i < K1.n; i += kWalkThreads)
-            if (bins[i] != 0xff && !s_keep[bins[i]]) P.match12[i] = -1, ++removed;
-        for (int d = 32; d >= 1; d >>= 1) removed += __shfl_xor(removed, d, 64);
-        if ((tid & 63) == 0) s_wi[tid >> 6] = removed;
-        __syncthreads();
-        if (tid == 0) {
-            int tot = 0;
-            for (int w2 = 0; w2 < kWalkThreads / 64; ++w2) tot += s_wi[w2];
-            nmatch -= tot;
-        }
-    }
+    if (check_ori) rotation_filter<kWalkThreads>(P, bins, hist, s_keep, s_wi, nmatch);
     if (tid == 0) n_matches[p] = nmatch;
 }
 

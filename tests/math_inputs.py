@@ -309,9 +309,110 @@ def predict_scale():
     return [("all", np.concatenate([f32(around(centres, 4096)), rnd]), LSF, None)]
 
 
+N_LEVELS = 8                         # the pyramid levels PredictScale is clamped to in the clamp test
+
+
+def predict_scale_clamp_ends():
+    """Ratios at the two ends of PredictScale's clamp for LSF and N_LEVELS: the float neighbours of 1.2^k for k = -2, -1, 0
+    (raw levels below 0 up to the first kept one) and k = N_LEVELS - 2 .. N_LEVELS + 1 (the last unclamped level, then at
+    and above N_LEVELS), and ratios far outside (raw -12 and 25)."""
+    k = np.array([-2, -1, 0, N_LEVELS - 2, N_LEVELS - 1, N_LEVELS, N_LEVELS + 1], np.float64)
+    return np.concatenate([f32(around(bits((1.2 ** k).astype(F32)), 8)), np.array([0.1, 90.0], F32)])
+
+
+@functools.lru_cache(None)
+def rot_angles():
+    """The angles whose every ordered pair goes through rot_bin: a 0.5 degree grid over [0, 360); the two float
+    neighbours of every rot in (0, 360) at which rot / 30 is a half-integer (15, 45, ..., 345; paired with 0 they are
+    the difference itself); 0, the largest float below 360, and the smallest denormal and FLT_MIN, whose pairs with 0
+    give the smallest negative differences, which + 360 round to exactly 360."""
+    grid = np.arange(0, 720, dtype=np.float64) * 0.5
+    half = (np.arange(12, dtype=np.float64) * 30 + 15).astype(F32)
+    nb = np.concatenate([np.nextafter(half, F32(0)), np.nextafter(half, F32(360))])
+    edge = np.concatenate([f32([0x00000000, 0x00000001, 0x00800000]), [np.nextafter(F32(360), F32(0))]])
+    a = np.unique(np.concatenate([grid.astype(F32), nb, edge]).astype(F32))
+    assert a.min() == 0 and a.max() < 360 and 700 < len(a) < 800
+    return a
+
+
+@functools.lru_cache(None)
+def rot_bin():
+    """(name, angle1, angle2): all ordered pairs of rot_angles()."""
+    a = rot_angles()
+    a1, a2 = (g.ravel().copy() for g in np.meshgrid(a, a, indexing="ij"))
+    return [("all pairs", a1, a2, None)]
+
+
+def rot_bin_ref(a1, a2):
+    """ORBmatcher.cc:475-481 in float32, one IEEE operation per step; round() is half away from zero (the products
+    are >= 0 and far below 2^23, so floor(v + 0.5) in float64 is exact)."""
+    rot = a1 - a2
+    rot = np.where(rot < 0, rot + F32(360.0), rot)
+    v = rot * (F32(1.0) / F32(30))
+    assert rot.dtype == F32 and v.dtype == F32
+    b = np.floor(v.astype(np.float64) + 0.5).astype(np.int32)
+    return np.where(b == 30, 0, b).astype(np.int32)
+
+
+@functools.lru_cache(None)
+def three_maxima():
+    """About 2,000 histograms [n][30] int32: all zero; one non-empty bin at each position; equal counts in two, three
+    and all bins; for max1 in {10, 20, 30, 100, 1000} the second and third counts at max1 / 10 - 1, max1 / 10 and
+    max1 / 10 + 1 (the 10 % rule at its boundary), the three bins in every order of position; 800 random histograms
+    with counts 0..3 (many ties); 800 with counts up to 2^20."""
+    rng = np.random.default_rng(20240213)
+    n = st.ROT_HIST_LEN
+    h = [np.zeros((1, n), np.int32), np.eye(n, dtype=np.int32) * 7]
+    for k in (2, 3):
+        e = np.zeros((40, n), np.int32)
+        for r in e:
+            r[rng.choice(n, k, replace=False)] = 5
+        h.append(e)
+    h.append(np.full((1, n), 4, np.int32))
+    rule = []
+    for max1 in (10, 20, 30, 100, 1000):
+        for s2 in (max1 // 10 - 1, max1 // 10, max1 // 10 + 1):
+            for s3 in (max1 // 10 - 1, max1 // 10, max1 // 10 + 1):
+                for order in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)):
+                    r = np.zeros(n, np.int32)
+                    pos = np.sort(rng.choice(n, 3, replace=False))
+                    r[pos[list(order)]] = (max1, s2, s3)
+                    rule.append(r)
+    h.append(np.array(rule))
+    h.append(rng.integers(0, 4, (800, n)).astype(np.int32))
+    h.append(rng.integers(0, (1 << 20) + 1, (800, n)).astype(np.int32))
+    h = np.ascontiguousarray(np.concatenate(h))
+    assert 1900 <= len(h) <= 2100
+    return [("all", h, None, None)]
+
+
+def three_maxima_ref(hists):
+    """ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:2537-2573), the literal loop; the 10 % products in float32."""
+    out = np.empty((len(hists), 3), np.int32)
+    for r, hist in enumerate(hists.tolist()):
+        max1 = max2 = max3 = 0
+        ind1 = ind2 = ind3 = -1
+        for i, s in enumerate(hist):
+            if s > max1:
+                max3, max2, max1 = max2, max1, s
+                ind3, ind2, ind1 = ind2, ind1, i
+            elif s > max2:
+                max3, max2 = max2, s
+                ind3, ind2 = ind2, i
+            elif s > max3:
+                max3, ind3 = s, i
+        if F32(max2) < F32(0.1) * F32(max1):
+            ind2 = ind3 = -1
+        elif F32(max3) < F32(0.1) * F32(max1):
+            ind3 = -1
+        out[r] = (ind1, ind2, ind3)
+    return out
+
+
 # fn -> the calls of its input set, for the functions with plain [n] arguments
 SETS = {st.SINCOSF: trig, st.TANF: trig, st.ATANF: atanf, st.ATAN2F: atan2, st.FAST_ATAN2_DEG: fast_atan2,
-        st.SQRTF: sqrtf, st.DIVF: divf, st.ROUND_EVEN: round_even, st.RCP_NR: rcp_nr, st.PREDICT_SCALE: predict_scale}
+        st.SQRTF: sqrtf, st.DIVF: divf, st.ROUND_EVEN: round_even, st.RCP_NR: rcp_nr, st.PREDICT_SCALE: predict_scale,
+        st.ROT_BIN: rot_bin, st.THREE_MAXIMA: three_maxima}
 
 
 def camera_sets(fn):

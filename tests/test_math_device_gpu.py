@@ -16,7 +16,7 @@ from openmavis_amd import _lib, selftest as st
 pytestmark = pytest.mark.gpu
 
 IEEE_ONLY = [st.SINCOSF, st.ATANF, st.ATAN2F, st.TANF, st.SQRTF, st.FAST_ATAN2_DEG, st.ROUND_EVEN, st.DIVF,
-             st.KB8_UNPROJECT, st.PINHOLE_PROJECT, st.PINHOLE_UNPROJECT]
+             st.KB8_UNPROJECT, st.PINHOLE_PROJECT, st.PINHOLE_UNPROJECT, st.ROT_BIN, st.THREE_MAXIMA]
 CAMERA = [st.KB8_PROJECT, st.KB8_UNPROJECT, st.PINHOLE_PROJECT, st.PINHOLE_UNPROJECT]
 
 
@@ -37,7 +37,9 @@ def test_device_equals_host_build(torch_cuda, oracle, fn):
     """selftest.math == oracle.math_map, bit for bit (NaN == NaN), on the whole input set of each function whose body
     uses IEEE operations only.  sincosf / tanf: |y| < 120, the restatement's domain (no large-argument reduction;
     orb_extract.hip's angles are in [0, 2 pi), imu.hip's arguments dt * theta, tri.hip's go through cosf_glibc).
-    DIVF, SQRTF and ROUND_EVEN are also held to numpy's IEEE float32 divide, sqrt and rint."""
+    DIVF, SQRTF and ROUND_EVEN are also held to numpy's IEEE float32 divide, sqrt and rint.  ROT_BIN and THREE_MAXIMA
+    are the matchers' rotation check (omv::rot_bin on all pairs of ~750 angles, omv::three_maxima on ~2,000
+    histograms); tests/test_math_header_cpu.py holds their host build to the reference's lines."""
     total = 0
     for name, a, b, c in _calls(fn):
         got, want = st.math(fn, a, b, c), oracle.math_map(fn, a, b, c)
@@ -108,13 +110,29 @@ def test_predict_scale(torch_cuda, oracle):
     assert not bad and len(idx) <= 2, (len(idx), bad[:5])
 
 
+def test_predict_scale_clamp(torch_cuda, oracle):
+    """omv::predict_scale, the function the kernels call, is the clamp to [0, n_levels - 1] of the device's own
+    unclamped level, on the PredictScale set and around both ends of the clamp (raw levels below 0 and at or above
+    n_levels; the CPU test asserts the set holds them); the unclamped level of the added ratios is held to the host
+    build by test_predict_scale's rule."""
+    (_, ratio, lsf, _), = mi.predict_scale()
+    ratio = np.concatenate([mi.predict_scale_clamp_ends(), ratio])
+    raw = st.math(st.PREDICT_SCALE, ratio, lsf)
+    got = st.math(st.PREDICT_SCALE_CLAMPED, ratio, np.array([lsf[0], mi.N_LEVELS], np.float32))
+    assert np.array_equal(got, np.clip(raw, 0, mi.N_LEVELS - 1))
+    assert raw.min() < 0 and raw.max() >= mi.N_LEVELS
+    idx = mi.mismatches(raw, oracle.math_map(st.PREDICT_SCALE, ratio, lsf))
+    ties, bad = mi.judge_predict_scale(ratio, lsf[0], raw, idx[:50])
+    assert not bad and len(idx) <= 2, (len(idx), bad[:5])
+
+
 def test_hook_argument_checks(torch_cuda):
     """An unknown fn or a null pointer with n > 0: OMV_ERR_ARG before any launch; n == 0: OMV_OK."""
     torch = torch_cuda
     lib = _lib.load()
     buf = torch.zeros(64, dtype=torch.float32, device="cuda")
     p = _lib.ptr(buf)
-    for fn in (-1, 16, 1000):
+    for fn in (-1, len(st.MATH_NAMES), 1000):
         assert lib.omv_selftest_math(fn, 4, p, p, p, p, None) == _lib.OMV_ERR_ARG
         assert lib.omv_selftest_math(fn, 0, p, p, p, p, None) == _lib.OMV_ERR_ARG
     assert lib.omv_selftest_math(st.ATANF, -1, p, None, None, p, None) == _lib.OMV_ERR_ARG
@@ -123,7 +141,7 @@ def test_hook_argument_checks(torch_cuda):
     assert lib.omv_selftest_math(st.ATAN2F, 4, p, None, None, p, None) == _lib.OMV_ERR_ARG
     assert lib.omv_selftest_math(st.MULADD_F32, 4, p, p, None, p, None) == _lib.OMV_ERR_ARG
     assert lib.omv_selftest_math(st.KB8_PROJECT, 4, p, None, None, p, None) == _lib.OMV_ERR_ARG
-    for fn in range(16):
+    for fn in range(len(st.MATH_NAMES)):
         assert lib.omv_selftest_math(fn, 0, None, None, None, None, None) == _lib.OMV_OK
     assert lib.omv_selftest_math(st.ATANF, 4, p, None, None, p, None) == _lib.OMV_OK   # b, c unused: may be NULL
     torch.cuda.synchronize()

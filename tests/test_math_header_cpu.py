@@ -159,6 +159,49 @@ def test_numpy_restatements_agree_with_the_host_header(oracle):
         assert np.array_equal(oracle.math_map(st.ROUND_EVEN, a), np.rint(a).astype(np.int32)), name
 
 
+def test_rot_bin_against_the_reference_lines(oracle):
+    """omv::rot_bin (host build) against ORBmatcher.cc:475-481 restated in numpy float32 with round half away from
+    zero, on every ordered pair of math_inputs.rot_angles().  The set reaches every bin the formula can give (0..12:
+    rot <= 360 and the factor is 1 / 30), both sides of every half-integer of rot / 30, and rot == 360 exactly."""
+    (name, a1, a2, _), = mi.rot_bin()
+    got, want = oracle.math_map(st.ROT_BIN, a1, a2), mi.rot_bin_ref(a1, a2)
+    bad = mi.mismatches(got, want)
+    assert len(bad) == 0, _describe(st.ROT_BIN, name, a1, a2, got, want, bad)
+    assert sorted(np.unique(got)) == list(range(13))
+    tiny = (a1 == 0) & (a2 > 0) & (a2 < 1e-30)
+    assert tiny.sum() == 2 and np.all(got[tiny] == 12)   # the smallest negative differences: rot == 360
+
+
+def test_three_maxima_against_the_reference_loop(oracle):
+    """omv::three_maxima (host build) against the literal loop of ORBmatcher::ComputeThreeMaxima in Python with the
+    10 % products in float32: the empty histogram (-1, -1, -1), a single bin, ties between bins (the first wins), and
+    the 10 % rule one count below, at and one above max1 / 10 for the second and the third bin."""
+    (name, h, _, _), = mi.three_maxima()
+    got, want = oracle.math_map(st.THREE_MAXIMA, h), mi.three_maxima_ref(h)
+    bad = mi.mismatches(got, want)
+    assert len(bad) == 0, (len(bad), h[bad[0]], got[bad[0]], want[bad[0]])
+    assert np.array_equal(got[0], [-1, -1, -1]) and not h[0].any()
+    assert np.array_equal(got[1:31], np.stack([np.arange(30), np.full(30, -1), np.full(30, -1)], 1))
+    full = np.flatnonzero((h == 4).all(axis=1))
+    assert len(full) == 1 and np.array_equal(got[full[0]], [0, 1, 2])
+    # the boundary rows: the second / third index is dropped exactly when its count is below a tenth of the first
+    dropped2, dropped3 = (got[:, 1] < 0) & (got[:, 0] >= 0), (got[:, 2] < 0) & (got[:, 1] >= 0)
+    assert dropped2.sum() >= 30 and dropped3.sum() >= 30 and (got[:, 2] >= 0).sum() >= 30
+
+
+def test_predict_scale_clamp(oracle):
+    """omv::predict_scale is predict_scale_raw (the PREDICT_SCALE code, held to libm and to 50 digits above) clamped to
+    [0, n_levels - 1]: on the PredictScale set and on ratios around both ends of the clamp, raw levels below 0 and at
+    or above n_levels included."""
+    (_, ratio, lsf, _), = mi.predict_scale()
+    ratio = np.concatenate([mi.predict_scale_clamp_ends(), ratio])
+    raw = oracle.math_map(st.PREDICT_SCALE, ratio, lsf)
+    got = oracle.math_map(st.PREDICT_SCALE_CLAMPED, ratio, np.array([lsf[0], mi.N_LEVELS], np.float32))
+    assert np.array_equal(got, np.clip(raw, 0, mi.N_LEVELS - 1))
+    for level in (-12, -2, -1, 0, 1, mi.N_LEVELS - 2, mi.N_LEVELS - 1, mi.N_LEVELS, mi.N_LEVELS + 1, 25):
+        assert (raw == level).any(), level
+
+
 def test_host_build_does_not_contract(oracle):
     """The host build of the probes returns the unfused a * b + c on >= 10^5 triples each whose fused value differs
     (-ffp-contract=off in oracle/Makefile)."""
