@@ -466,7 +466,9 @@ typedef struct omv_lba omv_lba;
 omv_status omv_lba_create(int max_kf, int max_cams, int max_pts, int max_mono, int max_imu, omv_lba **out);
 omv_status omv_lba_destroy(omv_lba *h);
 /* Upload a problem (host arrays); the structure (point -> keyframe slots, reduced-system layout,
- * block fill pattern) is analysed on the host once here. */
+ * block fill pattern) is analysed on the host once here.  A failed call: OMV_ERR_ARG leaves the handle's
+ * previous problem intact, OMV_ERR_HIP leaves it with none; without a problem omv_lba_optimize, _evaluate,
+ * _evaluate_stereo, _reset and _debug_solve return OMV_ERR_ARG before any launch. */
 omv_status omv_lba_set_problem(omv_lba *h, const omv_lba_problem *p);
 /* Run the optimisation on the uploaded problem; on return the state arrays of `p` (Rwb, twb, Rcw,
  * tcw, vel, bg, ba, pts) hold the optimised state and `r` the outcome.  Synchronous. */

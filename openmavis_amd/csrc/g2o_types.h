@@ -8,6 +8,7 @@
 
 #include "../../include/omv.h"
 #include "omv_device.h"
+#include "omv_inv3.h"
 
 namespace omv_g2o {
 
@@ -81,23 +82,6 @@ __device__ __forceinline__ void tr3(const double *a, double *r) {
 // double: the optimizer edges; imu.hip's hat3 is the float one of the preintegration
 __device__ __forceinline__ void hat3(const double *w, double *W) {
     W[0] = 0, W[1] = -w[2], W[2] = w[1], W[3] = w[2], W[4] = 0, W[5] = -w[0], W[6] = -w[1], W[7] = w[0], W[8] = 0;
-}
-template <typename T>
-__host__ __device__ inline bool inv3(const T *a, T *r) {
-    T c[9];
-    c[0] = a[4] * a[8] - a[5] * a[7];
-    c[1] = a[2] * a[7] - a[1] * a[8];
-    c[2] = a[1] * a[5] - a[2] * a[4];
-    c[3] = a[5] * a[6] - a[3] * a[8];
-    c[4] = a[0] * a[8] - a[2] * a[6];
-    c[5] = a[2] * a[3] - a[0] * a[5];
-    c[6] = a[3] * a[7] - a[4] * a[6];
-    c[7] = a[1] * a[6] - a[0] * a[7];
-    c[8] = a[0] * a[4] - a[1] * a[3];
-    const T det = a[0] * c[0] + a[1] * c[3] + a[2] * c[6];
-    const T id = T(1) / det;
-    for (int k = 0; k < 9; ++k) r[k] = c[k] * id;
-    return det != T(0);
 }
 // NormalizeRotation (Eigen JacobiSVD U V^T) = polar factor, by Newton iteration X <- (X + X^-T)/2
 template <typename T>

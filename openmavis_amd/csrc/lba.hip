@@ -34,24 +34,22 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
-#include <map>
-#include <numeric>
-#include <set>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/omv.h"
 #include "g2o_types.h"
+#include "lba_plan.h"
 #include "omv_device.h"
 #include "omv_host.h"
 
 namespace {
 
 using namespace omv_g2o;
-
-constexpr int kGrpEdges = 256;   // edges per buildSystem landmark group / pose chunk (one per thread)
-
-
+using namespace omv_lba_plan;   // the group and LDS limits, LbaPlan / plan_lba (host-only: lba_plan.h)
+static_assert(sizeof(Int2) == sizeof(int2) && alignof(Int2) == alignof(int2), "the plan's records are the kernels' int2");
+static_assert(sizeof(Int4) == sizeof(int4) && alignof(Int4) == alignof(int4), "the plan's records are the kernels' int4");
+static_assert(kPreintCov == PreView::C, "the plan reads the covariance where the kernels do");
 
 
 // Device-resident Levenberg-Marquardt control (optimization_algorithm_levenberg.cpp:61-169), for the
@@ -492,16 +490,10 @@ __device__ __forceinline__ void m_of(const double *Hpl, const double Ri[6], doub
     }
 }
 
-constexpr int kGrpLand = 128;    // landmarks per group (one thread each, threads 0..127)
-constexpr int kGrpSlots = 128;   // slots per group (one thread each, threads 128..255)
-constexpr int kGrpW = 32;        // optimisable keyframes per group (rows of the Schur product: 8 each)
-// LDS of one landmark group (doubles, edge / slot / landmark-major rows)
-constexpr int kSE = 22;                   // per edge: JP (3 x 6) | w | -W e (3)
-constexpr int kLdsE = kSE * kGrpEdges;    // edges; then per slot its 27 diagonal terms; then the MFMA operand panels
+// LDS of one landmark group (doubles, edge / slot / landmark-major rows): kLdsE (lba_plan.h) per edge JP | w | -W e
 constexpr int kLdsX = 9 * kGrpEdges;      // per edge JX (3 x 3)
 constexpr int kLdsL = 3 * kGrpLand + 27 * kGrpW;   // per landmark y (3); per landmark R^-1 (6), then per keyframe
                                                    //   the group's 27 diagonal terms
-constexpr int kPanel = kLdsE / 16;        // operand panels: ceil(w / 2) * kpad <= kPanel (a group-planning bound)
 constexpr size_t kBuildLds = (size_t)(kLdsE + kLdsX + kLdsL) * 8 + kGrpLand * kGrpW;
 static_assert(6 * kGrpLand <= 27 * kGrpW, "R^-1 rows fit under the diagonal terms");
 static_assert(27 * kGrpSlots <= kLdsE, "the slots' diagonal terms fit the edge region");
@@ -1214,7 +1206,6 @@ __device__ __forceinline__ void update16(double *Sij, const double *Sik, const d
 }
 
 constexpr int kLdltThreads = 512;
-constexpr size_t kLdltLds = 160 * 1024 - 512;   // dynamic LDS of the solver (the static part is one int)
 
 // Forward substitution of one column (one wavefront): z_i = Dinv_i (y_i - sum_k S_ik z_k) over the row structure
 // (descendants, final by then); lane group grp takes the terms m = 4 grp .. 4 grp + 3 of every block (four loads of
@@ -1652,133 +1643,17 @@ __global__ void mono_jac_kernel(Rig rig, State s, Edges E, double *jx, double *j
             jp[18 * e + 6 * r + q] = pr[3 * r] * se3[q] + pr[3 * r + 1] * se3[6 + q] + pr[3 * r + 2] * se3[12 + q];
 }
 
-// ---- host-side analysis ------------------------------------------------------------------------------
-void host_inv(std::vector<double> &A, int n) {   // Gauss-Jordan with partial pivoting
-    std::vector<double> I(n * n, 0.0);
-    for (int i = 0; i < n; ++i) I[i * n + i] = 1;
-    for (int c = 0; c < n; ++c) {
-        int p = c;
-        for (int r = c + 1; r < n; ++r)
-            if (std::fabs(A[r * n + c]) > std::fabs(A[p * n + c])) p = r;
-        if (p != c)
-            for (int k = 0; k < n; ++k) std::swap(A[p * n + k], A[c * n + k]), std::swap(I[p * n + k], I[c * n + k]);
-        const double d = A[c * n + c];
-        for (int k = 0; k < n; ++k) A[c * n + k] /= d, I[c * n + k] /= d;
-        for (int r = 0; r < n; ++r)
-            if (r != c && A[r * n + c] != 0) {
-                const double f = A[r * n + c];
-                for (int k = 0; k < n; ++k) A[r * n + k] -= f * A[c * n + k], I[r * n + k] -= f * I[c * n + k];
-            }
-    }
-    A = I;
-}
-void host_sym_eig(std::vector<double> A, int n, std::vector<double> &w, std::vector<double> &V) {
-    V.assign(n * n, 0.0);
-    for (int i = 0; i < n; ++i) V[i * n + i] = 1;
-    for (int sweep = 0; sweep < 100; ++sweep) {
-        double off = 0, dg = 0;   // converged: off-diagonal mass below 1e-32 of the diagonal's
-        for (int p = 0; p < n; ++p) {
-            dg += A[p * n + p] * A[p * n + p];
-            for (int q = p + 1; q < n; ++q) off += A[p * n + q] * A[p * n + q];
-        }
-        if (off <= 1e-32 * dg || off < 1e-300) break;
-        for (int p = 0; p < n; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = A[p * n + q];
-                if (apq == 0) continue;
-                const double th = (A[q * n + q] - A[p * n + p]) / (2 * apq);
-                const double t = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1));
-                const double c = 1 / std::sqrt(t * t + 1), s = t * c;
-                for (int k = 0; k < n; ++k) {
-                    const double akp = A[k * n + p], akq = A[k * n + q];
-                    A[k * n + p] = c * akp - s * akq, A[k * n + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double apk = A[p * n + k], aqk = A[q * n + k];
-                    A[p * n + k] = c * apk - s * aqk, A[q * n + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double vkp = V[k * n + p], vkq = V[k * n + q];
-                    V[k * n + p] = c * vkp - s * vkq, V[k * n + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    w.resize(n);
-    for (int i = 0; i < n; ++i) w[i] = A[i * n + i];
-}
-
-// Symbolic block LDL^T of the keyframe adjacency `adj` (nb x nb, symmetric) in the elimination order `perm`
-// (position -> keyframe): the filled lower pattern in positions and each position's elimination-tree level
-// (leaves 0, a parent above all its children).  Returns the number of levels (the factorisation's critical
-// path in diagonal-block steps) and the number of stored blocks.
-int symbolic_ldlt(int nb, const std::vector<uint8_t> &adj, const std::vector<int> &perm, std::vector<uint8_t> &pat,
-                  std::vector<int> &level, int &n_slots) {
-    pat.assign((size_t)nb * nb, 0);
-    for (int i = 0; i < nb; ++i)
-        for (int j = 0; j <= i; ++j) pat[(size_t)i * nb + j] = i == j || adj[(size_t)perm[i] * nb + perm[j]];
-    for (int k = 0; k < nb; ++k)
-        for (int i = k + 1; i < nb; ++i)
-            if (pat[(size_t)i * nb + k])
-                for (int j = k + 1; j <= i; ++j)
-                    if (pat[(size_t)j * nb + k]) pat[(size_t)i * nb + j] = 1;
-    level.assign(nb, 0);
-    n_slots = 0;
-    int top = 0;
-    for (int k = 0; k < nb; ++k) {
-        for (int i = k; i < nb; ++i) n_slots += pat[(size_t)i * nb + k];
-        for (int i = k + 1; i < nb; ++i)
-            if (pat[(size_t)i * nb + k]) {   // the parent: the first block below the diagonal
-                level[i] = std::max(level[i], level[k] + 1);
-                break;
-            }
-        top = std::max(top, level[k]);
-    }
-    return nb > 0 ? top + 1 : 0;
-}
-
-// The elimination order of the reduced system's keyframe blocks.  Candidates: the keyframe order, and every
-// two-way dissection of it -- a cut c, the separator S = the keyframes before c adjacent to one at or after c,
-// then [before c minus S, in order] [from c, reversed] [S]: the two sides share no block, so their columns
-// factor concurrently, and each side is eliminated away from the separator (no fill beyond it).  The one with
-// the fewest elimination-tree levels whose blocks fit `max_slots` wins (ties: fewer blocks, then earlier).
-// The solution of the damped system does not depend on the order beyond rounding (SimplicialLDLT's own AMD
-// ordering is a different one again, linear_solver_eigen.h:60).
-std::vector<int> plan_order(int nb, const std::vector<uint8_t> &adj, int max_slots) {
-    std::vector<int> best(nb);
-    std::iota(best.begin(), best.end(), 0);
-    std::vector<uint8_t> pat;
-    std::vector<int> lev;
-    int best_slots = 0;
-    int best_h = symbolic_ldlt(nb, adj, best, pat, lev, best_slots);
-    for (int cut = 1; cut < nb; ++cut) {
-        std::vector<int> order, sep;
-        for (int v = 0; v < cut; ++v) {
-            bool s = false;
-            for (int w = cut; w < nb && !s; ++w) s = adj[(size_t)v * nb + w] != 0;
-            (s ? sep : order).push_back(v);
-        }
-        if (sep.size() * 2 > (size_t)nb) continue;
-        for (int w = nb - 1; w >= cut; --w) order.push_back(w);
-        order.insert(order.end(), sep.begin(), sep.end());
-        int ns = 0;
-        const int h = symbolic_ldlt(nb, adj, order, pat, lev, ns);
-        if (ns > max_slots) continue;
-        if (h < best_h || (h == best_h && ns < best_slots)) best = order, best_h = h, best_slots = ns;
-    }
-    return best;
-}
-
 }  // namespace
 
 // =============================================================================================
-struct omv_lba {
-    int max_kf, max_cams, max_pts, max_mono, max_imu;
-    omv::DeviceArena mem;    // the handle's own blocks: h_out, h_ctl, d_ctl
-    omv::DeviceArena prob;   // the current problem's device buffers and h_stage
-    ~omv_lba();
-    // problem
+// What omv_lba_set_problem fills: the host plan, the counts and every pointer into the problem arena.  One value, so
+// that a handle without a problem is this struct's default.
+struct LbaDeviceProblem {
     Rig rig{};
-    int n_kf = 0, n_opt = 0, n_pts = 0, n_mono = 0, n_imu = 0, n_red = 0, n_slots = 0;
+    LbaPlan plan;   // the host plan (lba_plan.h): orders, pattern, schedule, groups, LDS mode
+    int n_kf = 0, n_opt = 0, n_pts = 0, n_mono = 0, n_imu = 0;
+    int n_mono_all = 0, n_stereo_all = 0;   // caller edge counts (perm_edge >= n_mono_all: EdgeStereo)
+    bool imu_here = false;     // this rank evaluates the inertial edges (rank 0)
     State st[3]{};   // current / trial (push-pop double buffer) / the uploaded initial state
     int cur = 0;
     Edges E{};
@@ -1788,12 +1663,10 @@ struct omv_lba {
     BlockPat BP{};
     Gather G{};
     double *d_imu_contrib = nullptr;   // [n_imu][30 x 30 + 30] per-edge inertial contributions
-    int n_lgrp = 0;   // landmark groups (build, errors, back-substitution)
-    int n_big = 0;             // one-landmark groups of the scalar build path
     const int16_t *d_e_lkf = nullptr;   // per edge: its keyframe's index in the group's list (-1: fixed)
     const int *d_lkf_kf = nullptr;      // per (group, local keyframe): the keyframe
     const int *d_big = nullptr;
-    // device epilogue (single rank): perm_edge / perm_pt / trackDepth in device order, one staging block
+    // device epilogue (single rank): the plan's perm_edge / order / track_depth on the device, one staging block
     // [state without points | points in caller order | chi2 in caller order | outlier flags in caller order]
     int *d_perm_edge = nullptr, *d_perm_pt = nullptr;
     float *d_track_depth = nullptr;
@@ -1802,11 +1675,22 @@ struct omv_lba {
     bool epi_ready = false;    // the staging block holds this optimize()'s final result
     bool epi_chi2 = false;     //   including the chi2
     int *d_offP = nullptr, *d_offV = nullptr, *d_offG = nullptr, *d_offA = nullptr;
-    double *d_err = nullptr, *d_chi2 = nullptr, *d_err9 = nullptr;
+    double *d_err = nullptr, *d_chi2 = nullptr, *d_err9 = nullptr, *d_err3 = nullptr;
     double *d_err_b = nullptr, *d_chi2_b = nullptr, *d_err9_b = nullptr, *d_err3_b = nullptr;   // the second error buffer
     ErrBufs eb(int i) const { return i ? ErrBufs{d_err_b, d_err3_b, d_chi2_b, d_err9_b} : ErrBufs{d_err, d_err3, d_chi2, d_err9}; }
     double *d_partial = nullptr, *d_imu_partial = nullptr, *d_scale_partial = nullptr, *d_out = nullptr;
     double *d_partial0 = nullptr, *d_imu_partial0 = nullptr;   // optimize()'s initial errors (device driver)
+    double *d_S = nullptr, *d_coef = nullptr, *d_x = nullptr, *d_scratch = nullptr;
+    int *d_fail = nullptr;
+    double *d_bb = nullptr;    // the trial's copy of b (all-reduced with the packed system when sharded)
+    size_t state_doubles() const { return (size_t)n_kf * (24 + 12 * rig.n_cams) + 3 * (size_t)n_pts; }
+};
+
+struct omv_lba : LbaDeviceProblem {
+    int max_kf, max_cams, max_pts, max_mono, max_imu;
+    omv::DeviceArena mem;    // the handle's own blocks: h_out, h_ctl, d_ctl
+    omv::DeviceArena prob;   // the current problem's device buffers and h_stage
+    ~omv_lba();
     double *h_out = nullptr;   // pinned host copy of d_out: the per-trial 24-byte read-back
     LmCtl *d_ctl = nullptr;    // device-resident LM control (single-rank path)
     LmCtl *h_ctl = nullptr;    // pinned copy: the one read-back per optimize()
@@ -1821,33 +1705,29 @@ struct omv_lba {
     hipGraphExec_t step4e_exec[2] = {nullptr, nullptr};
     bool timing = false;       // direct launches with per-stage events instead of the captured step
     bool host_lm = false;      // force the host-driven LM loop (parity checks of the device control)
-    double *d_S = nullptr, *d_coef = nullptr, *d_x = nullptr, *d_scratch = nullptr;
-    int *d_fail = nullptr;
-    double *d_bb = nullptr;    // the trial's copy of b (all-reduced with the packed system when sharded)
-    size_t n_reduce = 0;
     int rank = 0, world = 1;   // landmark sharding (omv_lba_set_comm)
     omv_allreduce_fn allreduce = nullptr;
     void *ar_ctx = nullptr;
-    bool imu_here = false;     // this rank evaluates the inertial edges (rank 0)
-    size_t ldlt_lds = 0;
-    int use_lds = 0;
     bool lds_ok = false;
-    std::vector<int> perm_pt;     // device point index -> caller index
-    std::vector<int> perm_edge;   // device edge index -> caller index
-    double delta_mono, dsqr_mono, delta_st, dsqr_st, delta_imu, dsqr_imu;
-    int n_mono_all = 0, n_stereo_all = 0;   // caller edge counts (perm_edge >= n_mono_all: EdgeStereo)
-    double *d_err3 = nullptr;
+    // Huber deltas; thHuberMono / thHuberStereo are floats (:3028-3031)
+    const double delta_mono = (double)(float)std::sqrt(5.991), dsqr_mono = delta_mono * delta_mono;
+    const double delta_st = (double)(float)std::sqrt(7.815), dsqr_st = delta_st * delta_st;
+    const double delta_imu = std::sqrt(16.92), dsqr_imu = delta_imu * delta_imu;
     hipStream_t stream = nullptr;
     hipEvent_t ev[8] = {};
     double stage_ms[4] = {0, 0, 0, 0};
     int last_trials = 0;
     int host_syncs = 0;        // host waits of the last optimize()'s LM loop (the device driver: one per batch)
-    size_t state_doubles() const { return (size_t)n_kf * (24 + 12 * rig.n_cams) + 3 * (size_t)n_pts; }
 };
 
+// Has a problem: omv_lba_set_problem succeeded and nothing has freed it since.
+static bool has_problem(const omv_lba *h) { return h->st[2].pts != nullptr; }
+
+// The handle without a problem: the arena reset, the captured steps destroyed, the counts zero and every pointer into
+// the arena null -- also where a failed upload ends.
 static void free_problem(omv_lba *h) {
     h->prob.reset();
-    h->h_stage = nullptr, h->stage_bytes = 0;
+    static_cast<LbaDeviceProblem &>(*h) = LbaDeviceProblem{};
     hipGraphExec_t *execs[] = {&h->step_exec, &h->step4_exec, &h->step4e_exec[0], &h->step4e_exec[1]};
     hipGraph_t *graphs[] = {&h->step_graph, &h->step4_graph, &h->step4e_graph[0], &h->step4e_graph[1]};
     for (int q = 0; q < 4; ++q) {   // the captured steps hold the old problem's pointers
@@ -1862,6 +1742,105 @@ omv_lba::~omv_lba() {   // `mem` frees h_out, h_ctl and d_ctl after this body
     for (auto &e : ev)
         if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
+}
+
+// The device side of omv_lba_set_problem: h->plan (already checked) and the caller's state, rig and preintegrations
+// into the problem arena, one allocation per array; the state blocks first, the pinned staging block last.  On
+// OMV_ERR_HIP the caller frees the partial problem.
+static omv_status upload_problem(omv_lba *h, const omv_lba_problem *p) {
+    const LbaPlan &pl = h->plan;
+    const int C = p->n_cams, K = p->n_kf, NI = p->n_imu, nb = p->n_opt;
+    const int P = (int)pl.order.size(), E = (int)pl.perm_edge.size(), nred = pl.n_red, n_slots = pl.n_slots;
+    const size_t ni = (size_t)std::max(NI, 0);
+    h->n_kf = K, h->n_opt = nb, h->n_imu = NI, h->n_pts = P, h->n_mono = E;
+    h->n_mono_all = p->n_mono, h->n_stereo_all = std::max(p->n_stereo, 0);
+    h->imu_here = NI > 0 && h->rank == 0;
+    Rig &rig = h->rig;
+    rig.n_cams = C, rig.bf = (double)p->bf;
+    for (int c = 0; c < C; ++c) {
+        for (int q = 0; q < 8; ++q) rig.cam[c][q] = p->cam[8 * c + q];
+        rig.model[c] = p->cam_model ? p->cam_model[c] : OMV_CAM_KB8;
+        for (int q = 0; q < 9; ++q) rig.Rcb[c][q] = p->Rcb[9 * c + q], rig.Rbc[c][q] = p->Rbc[9 * c + q];
+        for (int q = 0; q < 3; ++q) rig.tcb[c][q] = p->tcb[3 * c + q], rig.tbc[c][q] = p->tbc[3 * c + q];
+    }
+    omv::DeviceArena &mem = h->prob;
+    bool ok = true;   // cleared by the first allocation or copy that fails
+    auto upn = [&](const auto *src, size_t n) {   // a device copy of n host elements; null on failure
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(src)>>;
+        T *d = nullptr;
+        if (ok && (!mem.alloc(&d, n) || (n > 0 && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)))
+            ok = false, d = nullptr;
+        return d;
+    };
+    auto upv = [&](const auto &v) { return upn(v.data(), v.size()); };   // a host vector's device copy
+    auto buf = [&](auto **d, size_t n) { ok = ok && mem.alloc(d, n); };  // an uninitialised work buffer
+    {   // one contiguous block per state: Rwb | twb | Rcw | tcw | vel | bg | ba | pts (device order): one copy to read back
+        std::vector<double> init;
+        auto add = [&](const double *src, size_t n) { init.insert(init.end(), src, src + n); };
+        add(p->Rwb, 9 * (size_t)K), add(p->twb, 3 * (size_t)K), add(p->Rcw, 9 * (size_t)K * C), add(p->tcw, 3 * (size_t)K * C);
+        add(p->vel, 3 * (size_t)K), add(p->bg, 3 * (size_t)K), add(p->ba, 3 * (size_t)K);
+        for (int q : pl.order) add(p->pts + 3 * (size_t)q, 3);
+        init.resize(h->state_doubles());
+        for (State &s : h->st) {
+            s.Rwb = upv(init);
+            if (!ok) return OMV_ERR_HIP;
+            s.twb = s.Rwb + 9 * K, s.Rcw = s.twb + 3 * K, s.tcw = s.Rcw + 9 * K * C;
+            s.vel = s.tcw + 3 * K * C, s.bg = s.vel + 3 * K, s.ba = s.bg + 3 * K, s.pts = s.ba + 3 * K;
+        }
+    }
+    h->E = Edges{upv(pl.e_pt), upv(pl.e_kf), upv(pl.e_cam), upv(pl.e_slot), upv(pl.e_obs), upv(pl.e_w), upv(pl.e_ur), E};
+    {
+        Land &L = h->L;
+        L.edge_start = upv(pl.pt_edge), L.slot_start = upv(pl.pt_slot), L.slot_kf = upv(pl.slot_kf);
+        L.slot_edge = upv(pl.slot_edge), L.slot_lkf = upv(pl.slot_lkf);
+        buf(&L.lnd, 12 * (size_t)P), buf(&L.M, 18 * (size_t)pl.n_pt_slots);
+        buf(&L.rec, 36 * (size_t)pl.blk_start[n_slots]), buf(&L.rec_rhs, 12 * (size_t)pl.rhs_start[nb]);
+        L.n = P;
+        L.grp_pt = upv(pl.grp_pt), L.grp_w = upv(pl.grp_w), L.grp_tp = upv(pl.grp_tp), L.tp = upv(pl.tp);
+        L.grp_blk = upv(pl.grp_blk), L.blkoff = upv(pl.blkoff), L.grp_kf = upv(pl.grp_kf), L.rhsoff = upv(pl.rhsoff);
+        h->d_big = upv(pl.big_grp), h->d_e_lkf = upv(pl.e_lkf), h->d_lkf_kf = upv(pl.lkf_kf);
+    }
+    h->d_offP = upv(pl.offP), h->d_offV = upv(pl.offV), h->d_offG = upv(pl.offG), h->d_offA = upv(pl.offA);
+    h->R = Red{nred, h->d_offP, K};
+    // inertial edges, then the reduction work lists
+    std::vector<uint8_t> rob(ni, 0);
+    if (p->imu_robust) std::copy(p->imu_robust, p->imu_robust + ni, rob.begin());
+    h->I = Imu{NI, upn(p->imu_kf1, ni), upn(p->imu_kf2, ni), upn(p->preint, ni * kPF), upv(pl.info9), upv(pl.infoG),
+               upv(pl.infoA), upv(rob), h->d_offP, h->d_offV, h->d_offG, h->d_offA};
+    buf(&h->d_imu_contrib, ni * kImuContrib);
+    h->G = Gather{upv(pl.blk_start), upv(pl.rhs_start), (const int4 *)upv(pl.imu_blk), upv(pl.ib_start),
+                  (const int2 *)upv(pl.imu_vec), upv(pl.iv_start), h->d_imu_contrib};
+    {   // block pattern + level schedule (one blob: LbaPlan::blob)
+        const int *kr = upv(pl.slot_kr), *kc = upv(pl.slot_kc), *d = upv(pl.blob);
+        if (!ok) return OMV_ERR_HIP;
+        const LbaPlan::BlobOff &o = pl.off;
+        h->BP = BlockPat{nb, n_slots, pl.n_lev, pl.n_lds, d + o.perm, kr, kc, d + o.dslot, d + o.lev_start, d + o.lev_col,
+                         d + o.ug_start, d + o.ug_split, d + o.crit_grp, d + o.ug_task_start, (const int4 *)(d + o.ug),
+                         (const int4 *)(d + o.inv_rec), d + o.rs_start, (const int2 *)(d + o.rs), d + o.cs_start,
+                         (const int2 *)(d + o.cs), d, pl.blob_ints};
+    }
+    // work buffers
+    // d_err9: [9n errors | n chi2 | 9n rotation errors eR]; the *_b set: the device driver's second (double-buffered) one
+    // d_S: [packed blocks | b | coef], contiguous, the one buffer a sharded solve all-reduces per trial
+    buf(&h->d_err, 2 * (size_t)E), buf(&h->d_chi2, E), buf(&h->d_err3, E), buf(&h->d_err9, 19 * ni);
+    buf(&h->d_err_b, 2 * (size_t)E), buf(&h->d_chi2_b, E), buf(&h->d_err3_b, E), buf(&h->d_err9_b, 19 * ni);
+    buf(&h->d_partial, pl.n_lgrp), buf(&h->d_imu_partial, 1), buf(&h->d_partial0, pl.n_lgrp), buf(&h->d_imu_partial0, 1);
+    buf(&h->d_scale_partial, pl.n_lgrp + 1), buf(&h->d_out, 4), buf(&h->d_S, pl.n_reduce), buf(&h->d_x, nred);
+    buf(&h->d_scratch, pl.use_lds == 1 ? 8 : pl.n_reduce + 8), buf(&h->d_fail, 1);
+    if (!ok) return OMV_ERR_HIP;
+    h->d_bb = h->d_S + (size_t)n_slots * 256;
+    h->d_coef = h->d_bb + nred;
+    HIP_OK(hipMemset(h->d_imu_partial, 0, sizeof(double)));
+    HIP_OK(hipMemset(h->d_imu_partial0, 0, sizeof(double)));
+    // device epilogue (single rank): caller-order permutations, trackDepth in device order, the staging block
+    if (h->world == 1) {
+        const size_t head = (size_t)(h->st[0].pts - h->st[0].Rwb);
+        h->stage_bytes = (head + 3 * (size_t)P + ((size_t)E + 7) / 8 + (size_t)E) * sizeof(double);
+        h->d_perm_edge = upv(pl.perm_edge), h->d_perm_pt = upv(pl.order), h->d_track_depth = upv(pl.track_depth);
+        buf(&h->d_stage, (h->stage_bytes + 7) / 8);
+        if (!ok || !mem.alloc_pinned(&h->h_stage, h->stage_bytes / sizeof(double))) return OMV_ERR_HIP;
+    }
+    return OMV_OK;
 }
 
 extern "C" {
@@ -1901,557 +1880,16 @@ omv_status omv_lba_destroy(omv_lba *h) {
 
 omv_status omv_lba_set_problem(omv_lba *h, const omv_lba_problem *p) {
     if (!h || !p) return OMV_ERR_ARG;
-    if (p->n_cams <= 0 || p->n_cams > h->max_cams || p->n_kf > h->max_kf || p->n_pts < 0 || p->n_mono < 0 ||
-        p->n_imu > h->max_imu || p->n_opt > p->n_kf || p->n_opt < 1)
-        return OMV_ERR_ARG;
+    // validate and plan on the host first: a rejected problem leaves the handle and its current problem as they were
+    LbaPlan plan;
+    const LbaLimits lim{h->max_kf, h->max_cams, h->max_pts, h->max_mono, h->max_imu};
+    const omv_status planned = plan_lba(*p, h->rank, h->world, lim, h->lds_ok, plan);
+    if (planned != OMV_OK) return planned;
     free_problem(h);
-    const int C = p->n_cams, K = p->n_kf, P_all = p->n_pts, NI = p->n_imu;
-    const int EM = p->n_mono, ES = p->n_stereo > 0 ? p->n_stereo : 0, E_all = EM + ES;
-    if (ES > 0 && (!p->stereo_pt || !p->stereo_kf || !p->stereo_obs || !p->stereo_inv_sigma2)) return OMV_ERR_ARG;
-    for (int e = 0; e < ES; ++e)   // an EdgeStereo exists only where mvuRight >= 0 (Optimizer.cc:3075, :3108)
-        if (!(p->stereo_obs[3 * (size_t)e + 2] >= 0.0)) return OMV_ERR_ARG;
-    h->n_mono_all = EM, h->n_stereo_all = ES;
-    // visual edge e < EM: EdgeMono e; e >= EM: EdgeStereo e - EM (camera 0, EdgeStereo(0) at :3118)
-    auto e_pt_of = [&](int e) { return e < EM ? p->mono_pt[e] : p->stereo_pt[e - EM]; };
-    auto e_kf_of = [&](int e) { return e < EM ? p->mono_kf[e] : p->stereo_kf[e - EM]; };
-    auto e_cam_of = [&](int e) { return e < EM ? p->mono_cam[e] : 0; };
-    h->n_kf = K, h->n_opt = p->n_opt, h->n_imu = NI;
-    h->imu_here = NI > 0 && h->rank == 0;
-    // rig
-    Rig &rig = h->rig;
-    rig.n_cams = C;
-    for (int c = 0; c < C; ++c) {
-        for (int q = 0; q < 8; ++q) rig.cam[c][q] = p->cam[8 * c + q];
-        rig.model[c] = p->cam_model ? p->cam_model[c] : OMV_CAM_KB8;
-        if (rig.model[c] != OMV_CAM_KB8 && rig.model[c] != OMV_CAM_PINHOLE) return OMV_ERR_ARG;
-        for (int q = 0; q < 9; ++q) rig.Rcb[c][q] = p->Rcb[9 * c + q], rig.Rbc[c][q] = p->Rbc[9 * c + q];
-        for (int q = 0; q < 3; ++q) rig.tcb[c][q] = p->tcb[3 * c + q], rig.tbc[c][q] = p->tbc[3 * c + q];
-    }
-    // reduced-system layout: per optimisable keyframe pose (6) [+ v bg ba (9)]
-    // keyframe block k occupies reduced indices 16k .. 16k+15: pose 0-5, v 6-8, bg 9-11, ba 12-14, pad 15
-    std::vector<int> offP(K, -1), offV(K, -1), offG(K, -1), offA(K, -1);
-    const int nred = 16 * p->n_opt;
-    for (int k = 0; k < p->n_opt; ++k) {
-        offP[k] = 16 * k;
-        if (p->kf_imu[k]) offV[k] = 16 * k + 6, offG[k] = 16 * k + 9, offA[k] = 16 * k + 12;
-    }
-    h->n_red = nred;
-    // landmark order: by the first optimisable keyframe observing them (workgroup keyframe spans stay small)
-    std::vector<std::vector<int>> pe(P_all);
-    for (int e = 0; e < E_all; ++e) {
-        if (e_pt_of(e) < 0 || e_pt_of(e) >= P_all || e_kf_of(e) < 0 || e_kf_of(e) >= K || e_cam_of(e) < 0 ||
-            e_cam_of(e) >= C)
-            return OMV_ERR_ARG;
-        pe[e_pt_of(e)].push_back(e);
-    }
-    std::vector<int> key(P_all, 1 << 30);
-    for (int q = 0; q < P_all; ++q)
-        for (int e : pe[q]) key[q] = std::min(key[q], e_kf_of(e) < p->n_opt ? e_kf_of(e) : (1 << 29) + e_kf_of(e));
-    std::vector<int> order(P_all);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
-    // block pattern of the reduced system (keyframe blocks) from ALL landmarks: every rank of a
-    // sharded solve lays out the identical packed system
-    const int nb = p->n_opt;
-    std::vector<uint8_t> adj((size_t)nb * nb, 0);   // keyframe adjacency (symmetric)
-    for (int q = 0; q < P_all; ++q)
-        for (int a : pe[q])
-            for (int b : pe[q]) {
-                const int i = e_kf_of(a), j = e_kf_of(b);
-                if (i < nb && j < nb && i != j) adj[(size_t)i * nb + j] = 1;
-            }
-    // this rank's landmarks: a contiguous share of the landmark order
-    if (h->world > 1) {
-        const size_t lo = (size_t)P_all * h->rank / h->world, hi = (size_t)P_all * (h->rank + 1) / h->world;
-        order = std::vector<int>(order.begin() + lo, order.begin() + hi);
-    }
-    const int P = (int)order.size();
-    int E = 0;
-    for (int q : order) E += (int)pe[q].size();
-    if (P > h->max_pts || E > h->max_mono) return OMV_ERR_ARG;
-    h->n_pts = P, h->n_mono = E;
-    h->perm_pt = order;
-    std::vector<int> e_pt, e_kf, e_cam, e_slot, pt_edge(P + 1, 0), pt_slot(P + 1, 0), slot_kf;
-    std::vector<double> e_obs;
-    std::vector<float> e_w, e_ur;
-    h->perm_edge.clear();
-    for (int q = 0; q < P; ++q) {
-        std::vector<int> es = pe[order[q]];
-        std::stable_sort(es.begin(), es.end(), [&](int a, int b) { return e_kf_of(a) < e_kf_of(b); });
-        pt_edge[q] = (int)e_pt.size();
-        pt_slot[q] = (int)slot_kf.size();
-        int last_kf = -1;
-        for (int e : es) {
-            const int kf = e_kf_of(e);
-            if (kf != last_kf) slot_kf.push_back(kf), last_kf = kf;
-            e_pt.push_back(q), e_kf.push_back(kf), e_cam.push_back(e_cam_of(e));
-            e_slot.push_back((int)slot_kf.size() - 1);
-            if (e < EM) {
-                e_obs.push_back(p->mono_obs[2 * e]), e_obs.push_back(p->mono_obs[2 * e + 1]);
-                e_w.push_back(p->mono_inv_sigma2[e]);
-                e_ur.push_back(-1.f);
-            } else {
-                const double *o = p->stereo_obs + 3 * (size_t)(e - EM);
-                e_obs.push_back(o[0]), e_obs.push_back(o[1]);
-                e_w.push_back(p->stereo_inv_sigma2[e - EM]);
-                // the reference stores mvuRight (a float >= 0) in the double measurement
-                e_ur.push_back((float)o[2]);
-            }
-            h->perm_edge.push_back(e);
-        }
-    }
-    pt_edge[P] = (int)e_pt.size();
-    pt_slot[P] = (int)slot_kf.size();
-    h->n_slots = (int)slot_kf.size();
-    // inertial edges: ids checked, and their blocks in the keyframe adjacency
-    for (int i = 0; i < NI; ++i) {
-        if (p->imu_kf1[i] < 0 || p->imu_kf1[i] >= K || p->imu_kf2[i] < 0 || p->imu_kf2[i] >= K ||
-            p->imu_kf1[i] == p->imu_kf2[i])
-            return OMV_ERR_ARG;
-        const int a = p->imu_kf1[i], b = p->imu_kf2[i];
-        if (a < nb && b < nb) adj[(size_t)a * nb + b] = adj[(size_t)b * nb + a] = 1;
-    }
-    // elimination order (every rank of a sharded solve plans from the same full pattern) and its symbolic LDL^T
-    const size_t vec_bytes = 2 * (size_t)nred * sizeof(double);
-    const int lds_slots = h->lds_ok && kLdltLds > vec_bytes ? (int)((kLdltLds - vec_bytes) / (256 * sizeof(double))) : 0;
-    const std::vector<int> perm = plan_order(nb, adj, std::max(lds_slots, 1));
-    std::vector<int> ipos(nb);
-    for (int q = 0; q < nb; ++q) ipos[perm[q]] = q;
-    std::vector<uint8_t> pat;
-    std::vector<int> level;
-    int n_slots = 0;
-    const int n_lev = symbolic_ldlt(nb, adj, perm, pat, level, n_slots);
-    std::vector<int> slot((size_t)nb * nb, -1), slot_kr, slot_kc, dslot(nb);
-    for (int j = 0; j < nb; ++j)   // column-major in positions: a column's panel blocks sit together
-        for (int i = j; i < nb; ++i)
-            if (pat[(size_t)i * nb + j]) {
-                slot[(size_t)i * nb + j] = (int)slot_kr.size();
-                slot_kr.push_back(perm[i]), slot_kc.push_back(perm[j]);
-            }
-    for (int k = 0; k < nb; ++k) dslot[k] = slot[(size_t)k * nb + k];
-    // level schedule: columns per level; trailing updates grouped by target block (ascending k)
-    std::vector<int> lev_start(n_lev + 1, 0), lev_col, ug_start(n_lev + 1, 0), ug_split(std::max(n_lev, 1), 0),
-        ug_task_start(1, 0), crit_grp(nb, -1);
-    std::vector<int> slot_kr_pos(n_slots), slot_kc_pos(n_slots);   // block positions of each slot
-    for (int j = 0; j < nb; ++j)
-        for (int i = j; i < nb; ++i)
-            if (slot[(size_t)i * nb + j] >= 0) slot_kr_pos[slot[(size_t)i * nb + j]] = i, slot_kc_pos[slot[(size_t)i * nb + j]] = j;
-    std::vector<int4> ug;
-    for (int l = 0; l < n_lev; ++l) {
-        lev_start[l] = (int)lev_col.size();
-        ug_start[l] = (int)ug_task_start.size() - 1;
-        std::map<int, std::vector<int4>> by_target;   // target slot -> updates in ascending k
-        for (int k = 0; k < nb; ++k) {
-            if (level[k] != l) continue;
-            lev_col.push_back(k);
-            std::vector<int> col;
-            for (int i = k + 1; i < nb; ++i)
-                if (pat[(size_t)i * nb + k]) col.push_back(i);
-            for (size_t a = 0; a < col.size(); ++a)
-                for (size_t c = 0; c <= a; ++c) {
-                    const int i = col[a], j = col[c];
-                    by_target[slot[(size_t)i * nb + j]].push_back(
-                        make_int4(slot[(size_t)i * nb + j], slot[(size_t)i * nb + k], slot[(size_t)j * nb + k], dslot[k]));
-                }
-        }
-        // the diagonal blocks of level l + 1 first: their inverses wait only for these groups, the rest of the level's
-        // updates run beside those inverses
-        for (int pass = 0; pass < 2; ++pass) {
-            for (auto &kv : by_target) {
-                const int kr = slot_kr_pos[kv.first], kc = slot_kc_pos[kv.first];
-                const bool crit = kr == kc && level[kr] == l + 1;
-                if (crit != (pass == 0)) continue;
-                if (crit) crit_grp[kr] = (int)ug_task_start.size() - 1;
-                ug.insert(ug.end(), kv.second.begin(), kv.second.end());
-                ug_task_start.push_back((int)ug.size());
-            }
-            if (pass == 0) ug_split[l] = (int)ug_task_start.size() - 1;
-        }
-    }
-    lev_start[n_lev] = (int)lev_col.size();
-    ug_start[n_lev] = (int)ug_task_start.size() - 1;
-    std::vector<int4> inv_rec(2 * (size_t)std::max(nb, 1), make_int4(0, 0, 0, 0));
-    for (size_t c = 0; c < lev_col.size(); ++c) {
-        const int col = lev_col[c], g = crit_grp[col];
-        const int u0 = g >= 0 ? ug_task_start[g] : 0, u1 = g >= 0 ? ug_task_start[g + 1] : 0;
-        inv_rec[2 * c] = make_int4(dslot[col], u0, u1, 0);
-        if (u0 < u1) inv_rec[2 * c + 1] = ug[u0];
-    }
-    std::vector<int> rs_start(nb + 1, 0), cs_start(nb + 1, 0);
-    std::vector<int2> rs, cs;
-    for (int i = 0; i < nb; ++i) {
-        rs_start[i] = (int)rs.size();
-        for (int k = 0; k < i; ++k)
-            if (pat[(size_t)i * nb + k]) rs.push_back(make_int2(slot[(size_t)i * nb + k], k));
-    }
-    rs_start[nb] = (int)rs.size();
-    for (int k = 0; k < nb; ++k) {
-        cs_start[k] = (int)cs.size();
-        for (int i = k + 1; i < nb; ++i)
-            if (pat[(size_t)i * nb + k]) cs.push_back(make_int2(slot[(size_t)i * nb + k], i));
-    }
-    cs_start[nb] = (int)cs.size();
-    // buildSystem landmark groups (land_group): whole landmarks in landmark order, at most kGrpEdges edges, kGrpLand
-    // landmarks, kGrpSlots slots and kGrpW optimisable keyframes; a landmark past one of those alone forms a group of
-    // its own built by the scalar path (land_group_big).  Per group: its keyframes in elimination order (local index a),
-    // its record (w(w+1)/2 blocks a >= b of 36, then w rows of [gradient 6 | Schur rhs 6]), the 16x16 output tiles that
-    // hold a co-observed keyframe pair, and per diagonal tile the residual rows of its keyframes' edges.
-    std::vector<int> slot_edge(h->n_slots + 1, 0);
-    for (int e = E - 1; e >= 0; --e) slot_edge[e_slot[e]] = e;
-    slot_edge[h->n_slots] = E;
-    std::vector<int16_t> slot_lkf(h->n_slots, -1);
-    std::vector<int> grp_pt(1, 0), grp_w, grp_tp(1, 0), grp_blk, blkoff, grp_kf, rhsoff, lkf_kf;
-    std::vector<int> blk_start(n_slots + 1, 0), rhs_start(nb + 1, 0);
-    std::vector<uint8_t> tp;
-    {
-        // per reduced-system block / keyframe: the (blkoff / rhsoff index) of each contributing group, in group order
-        std::vector<std::vector<int>> by_blk(n_slots), by_kf(nb);
-        auto opt_kfs = [&](int q0, int q1) {   // distinct optimisable keyframes of landmarks [q0, q1)
-            std::set<int> k;
-            for (int q = q0; q < q1; ++q)
-                for (int a = pt_slot[q]; a < pt_slot[q + 1]; ++a)
-                    if (slot_kf[a] < nb) k.insert(slot_kf[a]);
-            return k;
-        };
-        auto panel_ok = [&](int n_land, int n_kf) {   // the MFMA operand panels fit their LDS region
-            return (n_kf + 1) / 2 * ((3 * n_land + 3) & ~3) <= kPanel;
-        };
-        auto fits = [&](int q0, int q1) {
-            const int nk = (int)opt_kfs(q0, q1).size();
-            return pt_edge[q1] - pt_edge[q0] <= kGrpEdges && q1 - q0 <= kGrpLand && pt_slot[q1] - pt_slot[q0] <= kGrpSlots &&
-                   nk <= kGrpW && panel_ok(q1 - q0, nk);
-        };
-        for (int q = 0; q < P;) {
-            int r = q + 1;
-            const bool big = !fits(q, r);
-            if (!big) {
-                std::set<int> k = opt_kfs(q, r);
-                while (r < P && r - q < kGrpLand && pt_edge[r + 1] - pt_edge[q] <= kGrpEdges &&
-                       pt_slot[r + 1] - pt_slot[q] <= kGrpSlots) {
-                    std::set<int> k2 = k;
-                    for (int a = pt_slot[r]; a < pt_slot[r + 1]; ++a)
-                        if (slot_kf[a] < nb) k2.insert(slot_kf[a]);
-                    if ((int)k2.size() > kGrpW || !panel_ok(r + 1 - q, (int)k2.size())) break;
-                    k.swap(k2);
-                    ++r;
-                }
-            }
-            // the group's keyframes in elimination order
-            std::set<int> ks = opt_kfs(q, r);
-            std::vector<int> kl(ks.begin(), ks.end());
-            std::sort(kl.begin(), kl.end(), [&](int x, int y) { return ipos[x] < ipos[y]; });
-            const int w = (int)kl.size(), nblk = w * (w + 1) / 2;
-            std::vector<int> lk(nb, -1);
-            for (int a = 0; a < w; ++a) lk[kl[a]] = a;
-            for (int a = pt_slot[q]; a < pt_slot[r]; ++a) slot_lkf[a] = (int16_t)(slot_kf[a] < nb ? lk[slot_kf[a]] : -1);
-            const int g = (int)grp_w.size();
-            grp_w.push_back(big ? -w - 1 : w);
-            grp_blk.push_back((int)blkoff.size());
-            grp_kf.push_back((int)rhsoff.size());
-            blkoff.resize(blkoff.size() + nblk, -1);
-            rhsoff.resize(rhsoff.size() + w, -1);
-            lkf_kf.insert(lkf_kf.end(), kl.begin(), kl.end());
-            // co-observed keyframe pairs (a >= b): the group's blocks
-            std::vector<uint8_t> co((size_t)std::max(w, 1) * std::max(w, 1), 0);
-            for (int x = q; x < r; ++x) {
-                std::vector<int> loc;
-                for (int a = pt_slot[x]; a < pt_slot[x + 1]; ++a)
-                    if (slot_kf[a] < nb) loc.push_back(lk[slot_kf[a]]);
-                for (int u : loc)
-                    for (int v : loc)
-                        if (u >= v) co[(size_t)u * w + v] = 1;
-            }
-            for (int u = 0; u < w; ++u) {
-                by_kf[kl[u]].push_back(grp_kf[g] + u);
-                for (int v = 0; v <= u; ++v)
-                    if (co[(size_t)u * w + v])
-                        by_blk[slot[(size_t)ipos[kl[u]] * nb + ipos[kl[v]]]].push_back(grp_blk[g] + u * (u + 1) / 2 + v);
-            }
-            if (!big) {
-                const int nt = (w + 1) / 2;
-                for (int ti = 0; ti < nt; ++ti)
-                    for (int tj = 0; tj <= ti; ++tj) {
-                        bool any = false;
-                        for (int u = 2 * ti; u < std::min(w, 2 * ti + 2) && !any; ++u)
-                            for (int v = 2 * tj; v < std::min(w, 2 * tj + 2) && !any; ++v) any = u >= v && co[(size_t)u * w + v];
-                        if (any) tp.push_back((uint8_t)ti), tp.push_back((uint8_t)tj);
-                    }
-            }
-            grp_tp.push_back((int)tp.size() / 2);
-            grp_pt.push_back(r);
-            (void)g;
-            q = r;
-        }
-        // records contiguous per block (per keyframe), in group order: assemble_kernel reads them as one run
-        for (int t = 0; t < n_slots; ++t) {
-            blk_start[t + 1] = blk_start[t] + (int)by_blk[t].size();
-            for (size_t i = 0; i < by_blk[t].size(); ++i) blkoff[by_blk[t][i]] = blk_start[t] + (int)i;
-        }
-        for (int k = 0; k < nb; ++k) {
-            rhs_start[k + 1] = rhs_start[k] + (int)by_kf[k].size();
-            for (size_t i = 0; i < by_kf[k].size(); ++i) rhsoff[by_kf[k][i]] = rhs_start[k] + (int)i;
-        }
-    }
-    h->n_lgrp = (int)grp_w.size();
-    std::vector<int> big_grp;
-    for (int g = 0; g < h->n_lgrp; ++g)
-        if (grp_w[g] < 0) big_grp.push_back(g);
-    h->n_big = (int)big_grp.size();
-    // inertial edges per block (edge, side of the row keyframe, side of the column keyframe; side 0 = kf1) and per
-    // keyframe (edge, side), in edge order; only the rank that evaluates them
-    std::vector<int> ib_start(n_slots + 1, 0), iv_start(nb + 1, 0);
-    std::vector<int4> imu_blk;
-    std::vector<int2> imu_vec;
-    {
-        std::vector<std::vector<int4>> bl(n_slots);
-        std::vector<std::vector<int2>> vl(nb);
-        if (h->imu_here)
-            for (int i = 0; i < NI; ++i) {
-                const int kk[2] = {p->imu_kf1[i], p->imu_kf2[i]};
-                for (int sr = 0; sr < 2; ++sr) {
-                    if (kk[sr] >= nb) continue;
-                    vl[kk[sr]].push_back(make_int2(i, sr));
-                    for (int sc = 0; sc < 2; ++sc) {
-                        if (kk[sc] >= nb || ipos[kk[sr]] < ipos[kk[sc]]) continue;
-                        bl[slot[(size_t)ipos[kk[sr]] * nb + ipos[kk[sc]]]].push_back(make_int4(i, sr, sc, 0));
-                    }
-                }
-            }
-        for (int t = 0; t < n_slots; ++t) {
-            ib_start[t] = (int)imu_blk.size();
-            imu_blk.insert(imu_blk.end(), bl[t].begin(), bl[t].end());
-        }
-        ib_start[n_slots] = (int)imu_blk.size();
-        for (int k = 0; k < nb; ++k) {
-            iv_start[k] = (int)imu_vec.size();
-            imu_vec.insert(imu_vec.end(), vl[k].begin(), vl[k].end());
-        }
-        iv_start[nb] = (int)imu_vec.size();
-    }
-    const size_t ldlt_bytes = ((size_t)n_slots * 256 + 2 * (size_t)nred) * sizeof(double);
-    // the solver's storage: 1 every block in LDS; 2 (the pattern does not fit) the vectors, the schedule and the first
-    // blocks in LDS, the rest in global scratch; 0 (no LDS attribute, or a test build) every block in global scratch
-    h->use_lds = !h->lds_ok ? 0 : ldlt_bytes <= kLdltLds ? 1 : kLdltLds > 2 * (size_t)nred * sizeof(double) + 8 * 256 * sizeof(double) ? 2 : 0;
-#ifdef OMV_LBA_FORCE_G
-    h->use_lds = 0;
-#endif
-    h->ldlt_lds = h->use_lds == 1 ? ldlt_bytes : 0;
-    // inertial information (EdgeInertial ctor :486-495) and random-walk information
-    std::vector<double> info9((size_t)NI * 81), infoG((size_t)NI * 9), infoA((size_t)NI * 9);
-    for (int i = 0; i < NI; ++i) {
-        const float *pr = p->preint + (size_t)i * kPF + PreView::C;
-        std::vector<double> A(81);
-        for (int r = 0; r < 9; ++r)
-            for (int c = 0; c < 9; ++c) A[r * 9 + c] = (double)pr[r * 15 + c];
-        host_inv(A, 9);
-        for (int r = 0; r < 9; ++r)
-            for (int c = r + 1; c < 9; ++c) A[r * 9 + c] = A[c * 9 + r] = (A[r * 9 + c] + A[c * 9 + r]) / 2;
-        std::vector<double> w, V;
-        host_sym_eig(A, 9, w, V);
-        for (double &x : w)
-            if (x < 1e-12) x = 0;
-        const double sc = p->imu_info_scale ? (double)p->imu_info_scale[i] : 1.0;
-        for (int r = 0; r < 9; ++r)
-            for (int c = 0; c < 9; ++c) {
-                double s = 0;
-                for (int k = 0; k < 9; ++k) s += V[r * 9 + k] * w[k] * V[c * 9 + k];
-                info9[(size_t)i * 81 + r * 9 + c] = s * sc;
-            }
-        double g[9], a[9];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) g[3 * r + c] = pr[(9 + r) * 15 + 9 + c], a[3 * r + c] = pr[(12 + r) * 15 + 12 + c];
-        inv3(g, &infoG[(size_t)9 * i]);
-        inv3(a, &infoA[(size_t)9 * i]);
-    }
-    h->delta_mono = (double)(float)std::sqrt(5.991);   // thHuberMono / thHuberStereo are floats (:3028-3031)
-    h->dsqr_mono = h->delta_mono * h->delta_mono;
-    h->delta_st = (double)(float)std::sqrt(7.815);
-    h->dsqr_st = h->delta_st * h->delta_st;
-    rig.bf = (double)p->bf;
-    h->delta_imu = std::sqrt(16.92);
-    h->dsqr_imu = h->delta_imu * h->delta_imu;
-    // ---- device allocations + uploads
-    omv::DeviceArena &mem = h->prob;
-    auto up = [&](auto *dst, const auto *src, size_t n) {
-        return hipMemcpy(dst, src, n * sizeof(*src), hipMemcpyHostToDevice);
-    };
-    auto upv = [&](const auto &v) {   // a host vector's device copy; null on failure
-        using T = typename std::decay_t<decltype(v)>::value_type;
-        T *d = nullptr;
-        if (mem.alloc(&d, v.size()) && !v.empty() && up(d, v.data(), v.size()) != hipSuccess) d = nullptr;
-        return (const T *)d;
-    };
-    for (int b = 0; b < 3; ++b) {
-        // one contiguous block per state: Rwb | twb | Rcw | tcw | vel | bg | ba | pts (one copy to read back)
-        State &s = h->st[b];
-        double *blk = nullptr;
-        if (!mem.alloc(&blk, h->state_doubles())) return OMV_ERR_HIP;
-        s.Rwb = blk, s.twb = s.Rwb + 9 * K, s.Rcw = s.twb + 3 * K, s.tcw = s.Rcw + 9 * K * C;
-        s.vel = s.tcw + 3 * K * C, s.bg = s.vel + 3 * K, s.ba = s.bg + 3 * K, s.pts = s.ba + 3 * K;
-        HIP_OK(up(s.Rwb, p->Rwb, 9 * K));
-        HIP_OK(up(s.twb, p->twb, 3 * K));
-        HIP_OK(up(s.Rcw, p->Rcw, 9 * K * C));
-        HIP_OK(up(s.tcw, p->tcw, 3 * K * C));
-        HIP_OK(up(s.vel, p->vel, 3 * K));
-        HIP_OK(up(s.bg, p->bg, 3 * K));
-        HIP_OK(up(s.ba, p->ba, 3 * K));
-        std::vector<double> pts((size_t)3 * P);
-        for (int q = 0; q < P; ++q)
-            for (int d = 0; d < 3; ++d) pts[3 * q + d] = p->pts[3 * (size_t)order[q] + d];
-        HIP_OK(up(s.pts, pts.data(), pts.size()));
-    }
-    h->cur = 0;
-    int *d_e_pt, *d_e_kf, *d_e_cam, *d_e_slot;
-    double *d_e_obs;
-    float *d_e_w, *d_e_ur;
-    if (!mem.alloc(&d_e_pt, E) || !mem.alloc(&d_e_kf, E) || !mem.alloc(&d_e_cam, E) || !mem.alloc(&d_e_slot, E) ||
-        !mem.alloc(&d_e_obs, 2 * (size_t)E) || !mem.alloc(&d_e_w, E) || !mem.alloc(&d_e_ur, E))
-        return OMV_ERR_HIP;
-    HIP_OK(up(d_e_pt, e_pt.data(), E));
-    HIP_OK(up(d_e_kf, e_kf.data(), E));
-    HIP_OK(up(d_e_cam, e_cam.data(), E));
-    HIP_OK(up(d_e_slot, e_slot.data(), E));
-    HIP_OK(up(d_e_obs, e_obs.data(), 2 * (size_t)E));
-    HIP_OK(up(d_e_w, e_w.data(), E));
-    HIP_OK(up(d_e_ur, e_ur.data(), E));
-    h->E = Edges{d_e_pt, d_e_kf, d_e_cam, d_e_slot, d_e_obs, d_e_w, d_e_ur, E};
-    int *d_pt_edge, *d_pt_slot, *d_slot_kf, *d_slot_edge;
-    int16_t *d_slot_lkf;
-    double *d_lnd, *d_M, *d_rec, *d_rec_rhs;
-    if (!mem.alloc(&d_pt_edge, P + 1) || !mem.alloc(&d_pt_slot, P + 1) || !mem.alloc(&d_slot_kf, h->n_slots) ||
-        !mem.alloc(&d_slot_edge, h->n_slots + 1) || !mem.alloc(&d_slot_lkf, h->n_slots) ||
-        !mem.alloc(&d_lnd, 12 * (size_t)P) || !mem.alloc(&d_M, 18 * (size_t)h->n_slots) ||
-        !mem.alloc(&d_rec, 36 * (size_t)blk_start[n_slots]) || !mem.alloc(&d_rec_rhs, 12 * (size_t)rhs_start[nb]))
-        return OMV_ERR_HIP;
-    HIP_OK(up(d_pt_edge, pt_edge.data(), P + 1));
-    HIP_OK(up(d_pt_slot, pt_slot.data(), P + 1));
-    HIP_OK(up(d_slot_edge, slot_edge.data(), h->n_slots + 1));
-    if (h->n_slots > 0) HIP_OK(up(d_slot_kf, slot_kf.data(), h->n_slots));
-    if (h->n_slots > 0) HIP_OK(up(d_slot_lkf, slot_lkf.data(), h->n_slots));
-    {
-        Land &L = h->L;
-        L = Land{d_pt_edge, d_pt_slot, d_slot_kf, d_slot_edge, d_slot_lkf, d_lnd, d_M, P,
-                 upv(grp_pt), upv(grp_w), upv(grp_tp), upv(tp),
-                 upv(grp_blk), upv(blkoff), upv(grp_kf), upv(rhsoff), d_rec, d_rec_rhs};
-        if (!L.grp_pt || !L.grp_w || !L.grp_tp || !L.tp || !L.grp_blk || !L.blkoff ||
-            !L.grp_kf || !L.rhsoff)
-            return OMV_ERR_HIP;
-        h->d_big = upv(big_grp);
-        std::vector<int16_t> e_lkf(E);
-        for (int e = 0; e < E; ++e) e_lkf[e] = slot_lkf[e_slot[e]];
-        h->d_e_lkf = upv(e_lkf);
-        h->d_lkf_kf = upv(lkf_kf);
-        if (!h->d_big || !h->d_e_lkf || !h->d_lkf_kf) return OMV_ERR_HIP;
-    }
-    if (!mem.alloc(&h->d_offP, K) || !mem.alloc(&h->d_offV, K) || !mem.alloc(&h->d_offG, K) || !mem.alloc(&h->d_offA, K))
-        return OMV_ERR_HIP;
-    HIP_OK(up(h->d_offP, offP.data(), K));
-    HIP_OK(up(h->d_offV, offV.data(), K));
-    HIP_OK(up(h->d_offG, offG.data(), K));
-    HIP_OK(up(h->d_offA, offA.data(), K));
-    h->R = Red{nred, h->d_offP, K};
-    // inertial
-    int *d_k1, *d_k2;
-    float *d_pre;
-    double *d_i9, *d_iG, *d_iA;
-    uint8_t *d_rob;
-    if (!mem.alloc(&d_k1, NI) || !mem.alloc(&d_k2, NI) || !mem.alloc(&d_pre, (size_t)NI * kPF) ||
-        !mem.alloc(&d_i9, (size_t)NI * 81) || !mem.alloc(&d_iG, (size_t)NI * 9) || !mem.alloc(&d_iA, (size_t)NI * 9) ||
-        !mem.alloc(&d_rob, NI) || !mem.alloc(&h->d_imu_contrib, (size_t)NI * kImuContrib))
-        return OMV_ERR_HIP;
-    if (NI > 0) {
-        HIP_OK(up(d_k1, p->imu_kf1, NI));
-        HIP_OK(up(d_k2, p->imu_kf2, NI));
-        HIP_OK(up(d_pre, p->preint, (size_t)NI * kPF));
-        HIP_OK(up(d_i9, info9.data(), info9.size()));
-        HIP_OK(up(d_iG, infoG.data(), infoG.size()));
-        HIP_OK(up(d_iA, infoA.data(), infoA.size()));
-        std::vector<uint8_t> rob(NI, 0);
-        if (p->imu_robust) std::copy(p->imu_robust, p->imu_robust + NI, rob.begin());
-        HIP_OK(up(d_rob, rob.data(), NI));
-    }
-    h->I = Imu{NI, d_k1, d_k2, d_pre, d_i9, d_iG, d_iA, d_rob, h->d_offP, h->d_offV, h->d_offG, h->d_offA};
-    // reduction work lists
-    {
-        Gather &g = h->G;
-        g.blk_start = upv(blk_start), g.rhs_start = upv(rhs_start);
-        g.imu_blk = upv(imu_blk), g.ib_start = upv(ib_start), g.imu_vec = upv(imu_vec), g.iv_start = upv(iv_start);
-        g.contrib = h->d_imu_contrib;
-        if (!g.blk_start || !g.rhs_start || !g.imu_blk || !g.ib_start || !g.imu_vec || !g.iv_start) return OMV_ERR_HIP;
-    }
-    // block pattern + level schedule
-    {
-        BlockPat &B = h->BP;
-        B.nb = nb, B.n_slots = n_slots, B.n_lev = n_lev;
-        B.slot_kr = upv(slot_kr), B.slot_kc = upv(slot_kc);
-        std::vector<int> blob;
-        auto put = [&](const auto &v) {   // 16-byte aligned sub-array
-            const size_t off = blob.size(), n = v.size() * sizeof(v[0]) / sizeof(int);
-            blob.resize(off + ((n + 3) & ~(size_t)3));
-            if (n) std::memcpy(blob.data() + off, v.data(), n * sizeof(int));
-            return off;
-        };
-        const size_t o_perm = put(perm), o_dslot = put(dslot), o_ls = put(lev_start), o_lc = put(lev_col);
-        const size_t o_us = put(ug_start), o_usp = put(ug_split), o_cg = put(crit_grp), o_uts = put(ug_task_start);
-        const size_t o_ug = put(ug), o_rss = put(rs_start), o_rs = put(rs), o_css = put(cs_start), o_cs = put(cs);
-        const size_t o_ir = put(inv_rec);
-        const int *d_blob = upv(blob);
-        if (!B.slot_kr || !B.slot_kc || !d_blob) return OMV_ERR_HIP;
-        B.blob = d_blob;
-        B.perm = d_blob + o_perm, B.dslot = d_blob + o_dslot, B.lev_start = d_blob + o_ls, B.lev_col = d_blob + o_lc;
-        B.ug_start = d_blob + o_us, B.ug_split = d_blob + o_usp, B.crit_grp = d_blob + o_cg;
-        B.ug_task_start = d_blob + o_uts, B.ug = (const int4 *)(d_blob + o_ug);
-        B.rs_start = d_blob + o_rss, B.rs = (const int2 *)(d_blob + o_rs);
-        B.cs_start = d_blob + o_css, B.cs = (const int2 *)(d_blob + o_cs);
-        B.inv_rec = (const int4 *)(d_blob + o_ir);
-        // stage the schedule in LDS when it fits beside the blocks and vectors
-        const size_t sched_bytes = blob.size() * sizeof(int);
-        B.blob_ints = 0;
-        B.n_lds = n_slots;
-        if (h->use_lds == 2) {   // hybrid: the vectors and the schedule in LDS, then as many blocks as fit
-            const size_t vb = 2 * (size_t)nred * sizeof(double);
-            const bool sch = vb + sched_bytes + 8 * 256 * sizeof(double) <= kLdltLds;
-            B.n_lds = std::min(n_slots, (int)((kLdltLds - vb - (sch ? sched_bytes : 0)) / (256 * sizeof(double))));
-            h->ldlt_lds = (size_t)B.n_lds * 256 * sizeof(double) + vb + (sch ? sched_bytes : 0);
-            B.blob_ints = sch ? (int)blob.size() : 0;
-        } else if (h->use_lds && h->ldlt_lds + sched_bytes <= kLdltLds) {
-            h->ldlt_lds += sched_bytes;
-            B.blob_ints = (int)blob.size();
-        }
-    }
-    // work buffers
-    // d_err9: [9n errors | n chi2 | 9n rotation errors eR]; the *_b set: the device driver's second (double-buffered) one
-    // d_S: [packed blocks | b | coef], contiguous, the one buffer a sharded solve all-reduces per trial
-    h->n_reduce = (size_t)n_slots * 256 + 2 * (size_t)nred;
-    if (!mem.alloc(&h->d_err, 2 * (size_t)E) || !mem.alloc(&h->d_chi2, E) || !mem.alloc(&h->d_err3, E) ||
-        !mem.alloc(&h->d_err9, 19 * (size_t)NI) || !mem.alloc(&h->d_err_b, 2 * (size_t)E) ||
-        !mem.alloc(&h->d_chi2_b, E) || !mem.alloc(&h->d_err3_b, E) || !mem.alloc(&h->d_err9_b, 19 * (size_t)NI) ||
-        !mem.alloc(&h->d_partial, h->n_lgrp) || !mem.alloc(&h->d_imu_partial, 1) ||
-        !mem.alloc(&h->d_partial0, h->n_lgrp) || !mem.alloc(&h->d_imu_partial0, 1) ||
-        !mem.alloc(&h->d_scale_partial, h->n_lgrp + 1) || !mem.alloc(&h->d_out, 4) || !mem.alloc(&h->d_S, h->n_reduce) ||
-        !mem.alloc(&h->d_x, nred) || !mem.alloc(&h->d_scratch, h->use_lds == 1 ? 8 : h->n_reduce + 8) ||
-        !mem.alloc(&h->d_fail, 1))
-        return OMV_ERR_HIP;
-    h->d_bb = h->d_S + (size_t)n_slots * 256;
-    h->d_coef = h->d_bb + nred;
-    HIP_OK(hipMemset(h->d_imu_partial, 0, sizeof(double)));
-    HIP_OK(hipMemset(h->d_imu_partial0, 0, sizeof(double)));
-    // device epilogue (single rank): caller-order permutations, trackDepth in device order, the staging block
-    if (h->world == 1) {
-        std::vector<float> td(P, 1e30f);
-        if (p->pt_track_depth)
-            for (int q = 0; q < P; ++q) td[q] = p->pt_track_depth[order[q]];
-        const size_t head = (size_t)(h->st[0].pts - h->st[0].Rwb);
-        h->stage_bytes = (head + 3 * (size_t)P + ((size_t)E + 7) / 8 + (size_t)E) * sizeof(double);
-        if (!mem.alloc(&h->d_perm_edge, E) || !mem.alloc(&h->d_perm_pt, P) || !mem.alloc(&h->d_track_depth, P) ||
-            !mem.alloc(&h->d_stage, (h->stage_bytes + 7) / 8))
-            return OMV_ERR_HIP;
-        if (E > 0) HIP_OK(up(h->d_perm_edge, h->perm_edge.data(), E));
-        if (P > 0) HIP_OK(up(h->d_perm_pt, order.data(), P));
-        if (P > 0) HIP_OK(up(h->d_track_depth, td.data(), P));
-        if (!mem.alloc_pinned(&h->h_stage, h->stage_bytes / sizeof(double))) return OMV_ERR_HIP;
-    }
-    return OMV_OK;
+    h->plan = std::move(plan);
+    const omv_status rs = upload_problem(h, p);
+    if (rs != OMV_OK) free_problem(h);   // a failed upload leaves no problem
+    return rs;
 }
 
 }  // extern "C"
@@ -2466,7 +1904,7 @@ omv_status omv_lba_set_problem(omv_lba *h, const omv_lba_problem *p) {
 static omv_status launch_errors(omv_lba *h, const State &s0, const State &s1, const LmCtl *ctl, int gate, int role,
                                 LmReset reset = LmReset{}, bool init_partials = false, const double *xp = nullptr,
                                 double lambda = 0.0, bool one_buffer = false, int n_acc = 0) {
-    const int ng = h->n_mono > 0 || xp ? h->n_lgrp : 0;
+    const int ng = h->n_mono > 0 || xp ? h->plan.n_lgrp : 0;
     const int lead = xp || h->imu_here ? 1 : 0;
     const int blocks = (ng > 0 ? omv::xcd_grid(ng) : 0) + lead;
     const ErrTrial T{xp, n_acc % 3 == 2 ? 1 : 0, h->d_bb, lambda, h->d_offV, h->d_offG, h->d_offA, h->n_opt, h->d_e_lkf,
@@ -2482,7 +1920,7 @@ static omv_status launch_errors(omv_lba *h, const State &s0, const State &s1, co
                                                     reset);
     return hipGetLastError() == hipSuccess ? OMV_OK : OMV_ERR_HIP;
 }
-static int n_grp_err(const omv_lba *h) { return h->n_mono > 0 ? h->n_lgrp : 0; }
+static int n_grp_err(const omv_lba *h) { return h->n_mono > 0 ? h->plan.n_lgrp : 0; }
 static omv_status lba_errors(omv_lba *h, const State &s) { return launch_errors(h, s, s, nullptr, kGateAlways, 0); }
 // the device driver's trial: back-substitution + errors into the trial buffer (role 1)
 static omv_status lba_trial_errors(omv_lba *h, const LmCtl *c) {
@@ -2518,7 +1956,7 @@ static omv_status lba_read_scalars(omv_lba *h, int n_scale, double out[3], bool 
 // rows go to the mono_* arrays (2 rows), EdgeStereo rows to the stereo_* arrays (3 rows).
 static omv_status lba_eval(omv_lba *h, double *mono_err, double *mono_jx, double *mono_jp, double *imu_err,
                            double *st_err, double *st_jx, double *st_jp) {
-    if (!h) return OMV_ERR_ARG;
+    if (!h || !has_problem(h)) return OMV_ERR_ARG;
     const State &s = h->st[h->cur];
     omv_status r = lba_errors(h, s);
     if (r != OMV_OK) return r;
@@ -2545,7 +1983,7 @@ static omv_status lba_eval(omv_lba *h, double *mono_err, double *mono_jx, double
     }
     const int EM = h->n_mono_all;
     for (int e = 0; e < E; ++e) {   // back to the caller's edge order
-        const int o = h->perm_edge[e];
+        const int o = h->plan.perm_edge[e];
         if (o < EM) {
             if (mono_err) mono_err[2 * o] = err[2 * e], mono_err[2 * o + 1] = err[2 * e + 1];
             if (mono_jx) std::memcpy(mono_jx + 6 * (size_t)o, &jx[9 * (size_t)e], 48);
@@ -2582,13 +2020,13 @@ static omv_status lba_enqueue_epilogue(omv_lba *h, bool want_chi2);
 // every trial; on a sharded solve lambda enters the pose diagonal once (rank 0), every rank damps its own landmarks.
 static omv_status launch_build(omv_lba *h, const State &A, const State &B, const LmCtl *c, double lambda) {
     const int n_imu = h->imu_here ? h->n_imu : 0, n_imu_pad = (n_imu + 7) & ~7;
-    const int grid = n_imu_pad + (h->n_lgrp > 0 ? omv::xcd_grid(h->n_lgrp) : 0);
+    const int grid = n_imu_pad + (h->plan.n_lgrp > 0 ? omv::xcd_grid(h->plan.n_lgrp) : 0);
     if (grid > 0)
         build_all_kernel<<<grid, kGrpEdges, kBuildLds, h->stream>>>(
-            h->rig, A, B, h->E, h->L, h->n_lgrp, h->I, n_imu, n_imu_pad, lambda, h->delta_mono, h->dsqr_mono,
+            h->rig, A, B, h->E, h->L, h->plan.n_lgrp, h->I, n_imu, n_imu_pad, lambda, h->delta_mono, h->dsqr_mono,
             h->delta_st, h->dsqr_st, h->delta_imu, h->dsqr_imu, h->eb(0), h->eb(1), h->d_imu_contrib, c);
-    if (h->n_big > 0)
-        build_big_kernel<<<h->n_big, kGrpEdges, kBuildLds, h->stream>>>(h->rig, A, B, h->E, h->L, h->d_big, h->n_big,
+    if (h->plan.n_big > 0)
+        build_big_kernel<<<h->plan.n_big, kGrpEdges, kBuildLds, h->stream>>>(h->rig, A, B, h->E, h->L, h->d_big, h->plan.n_big,
                                                                         lambda, h->delta_mono, h->dsqr_mono, h->delta_st,
                                                                         h->dsqr_st, h->eb(0), h->eb(1), c);
     HIP_OK(hipGetLastError());
@@ -2603,11 +2041,11 @@ static omv_status launch_assemble(omv_lba *h, double lambda, const LmCtl *c) {
 }
 
 static void launch_ldlt(omv_lba *h, const LmCtl *c) {
-    if (h->use_lds == 1)
-        ldlt_kernel<0><<<1, kLdltThreads, h->ldlt_lds, h->stream>>>(h->d_S, h->BP, h->d_bb, h->d_coef, h->d_x,
+    if (h->plan.use_lds == 1)
+        ldlt_kernel<0><<<1, kLdltThreads, h->plan.ldlt_lds, h->stream>>>(h->d_S, h->BP, h->d_bb, h->d_coef, h->d_x,
                                                                     h->d_scratch, h->d_fail, c);
-    else if (h->use_lds == 2)
-        ldlt_kernel<2><<<1, kLdltThreads, h->ldlt_lds, h->stream>>>(h->d_S, h->BP, h->d_bb, h->d_coef, h->d_x,
+    else if (h->plan.use_lds == 2)
+        ldlt_kernel<2><<<1, kLdltThreads, h->plan.ldlt_lds, h->stream>>>(h->d_S, h->BP, h->d_bb, h->d_coef, h->d_x,
                                                                     h->d_scratch, h->d_fail, c);
     else
         ldlt_kernel<1><<<1, kLdltThreads, 0, h->stream>>>(h->d_S, h->BP, h->d_bb, h->d_coef, h->d_x, h->d_scratch,
@@ -2628,12 +2066,12 @@ static omv_status lba_step(omv_lba *h, hipEvent_t *ev) {
     if (ev) HIP_OK(hipEventRecord(ev[1], st));
     if ((rs = launch_assemble(h, 0.0, c)) != OMV_OK) return rs;
     // sharded: one in-place SUM of this rank's partial reduced system [blocks | b | Schur rhs], ordered on the stream
-    if ((rs = lba_allreduce(h, h->d_S, h->n_reduce)) != OMV_OK) return rs;
+    if ((rs = lba_allreduce(h, h->d_S, h->plan.n_reduce)) != OMV_OK) return rs;
     if (ev) HIP_OK(hipEventRecord(ev[2], st));
     launch_ldlt(h, c);
     if (ev) HIP_OK(hipEventRecord(ev[3], st));
     if ((rs = lba_trial_errors(h, c)) != OMV_OK) return rs;
-    const int nmb = n_grp_err(h), nsc = 1 + h->n_lgrp;
+    const int nmb = n_grp_err(h), nsc = 1 + h->plan.n_lgrp;
     const double *pre = nullptr;
     if (lba_collective(h)) {   // [chi(A), chi, computeScale] of this rank's edges / landmarks, summed over the ranks
         const int s0 = h->rank > 0 ? 1 : 0;   // the keyframe part of computeScale enters once (rank 0)
@@ -2785,7 +2223,7 @@ static omv_status lba_optimize_device(omv_lba *h, const omv_lba_opts *o, omv_lba
 }
 
 omv_status omv_lba_optimize(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *p, omv_lba_result *res) {
-    if (!h || !o || !p || !res) return OMV_ERR_ARG;
+    if (!h || !o || !p || !res || !has_problem(h)) return OMV_ERR_ARG;
     hipStream_t st = h->stream;
     double sc[3];
     omv_status rs;
@@ -2833,7 +2271,7 @@ omv_status omv_lba_optimize(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *
             HIP_OK(hipEventRecord(h->ev[2], st));
             if ((rs = launch_assemble(h, lambda, nullptr)) != OMV_OK) return rs;
             // one exchange: sum the partial reduced systems [blocks | b | Schur rhs] of the landmark shards
-            if ((rs = lba_allreduce(h, h->d_S, h->n_reduce)) != OMV_OK) return rs;
+            if ((rs = lba_allreduce(h, h->d_S, h->plan.n_reduce)) != OMV_OK) return rs;
             HIP_OK(hipEventRecord(h->ev[3], st));
             launch_ldlt(h, nullptr);
             HIP_OK(hipEventRecord(h->ev[4], st));
@@ -2842,7 +2280,7 @@ omv_status omv_lba_optimize(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *
             if ((rs = launch_errors(h, A, B, nullptr, kGateAlways, 1, LmReset{}, false, h->d_x, lambda, true, n_acc)) !=
                 OMV_OK)
                 return rs;
-            if ((rs = lba_read_scalars(h, 1 + h->n_lgrp, sc, true)) != OMV_OK) return rs;
+            if ((rs = lba_read_scalars(h, 1 + h->plan.n_lgrp, sc, true)) != OMV_OK) return rs;
             const int fail = sc[2] != 0.0;
             HIP_OK(hipEventRecord(h->ev[5], st));
             HIP_OK(hipEventSynchronize(h->ev[5]));
@@ -2969,10 +2407,10 @@ static omv_status lba_finish_result(omv_lba *h, const omv_lba_opts *o, omv_lba_p
     {
         const double *q = stg.data() + (s.pts - s.Rwb);
         for (int i = 0; i < P; ++i)
-            for (int d = 0; d < 3; ++d) p->pts[3 * (size_t)h->perm_pt[i] + d] = q[3 * (size_t)i + d];
+            for (int d = 0; d < 3; ++d) p->pts[3 * (size_t)h->plan.order[i] + d] = q[3 * (size_t)i + d];
     }
     for (int e = 0; e < E; ++e) {
-        const int oe = h->perm_edge[e];
+        const int oe = h->plan.perm_edge[e];
         if (oe >= h->n_mono_all) {   // EdgeStereo: chi2 > chi2Stereo2 (:3299-3311)
             const int q = oe - h->n_mono_all;
             if (res->stereo_chi2) res->stereo_chi2[q] = chi2[e];
@@ -2994,7 +2432,7 @@ static omv_status lba_finish_result(omv_lba *h, const omv_lba_opts *o, omv_lba_p
 }
 
 omv_status omv_lba_reset(omv_lba *h) {
-    if (!h || !h->st[2].pts) return OMV_ERR_ARG;
+    if (!h || !has_problem(h)) return OMV_ERR_ARG;
     for (int b = 0; b < 2; ++b)
         HIP_OK(hipMemcpyAsync(h->st[b].Rwb, h->st[2].Rwb, h->state_doubles() * sizeof(double), hipMemcpyDeviceToDevice,
                               h->stream));
@@ -3013,7 +2451,7 @@ omv_status omv_lba_shard(omv_lba *h, int32_t *n_pts, int32_t *n_mono, int32_t *p
     if (!h) return OMV_ERR_ARG;
     if (n_pts) *n_pts = h->n_pts;
     if (n_mono) *n_mono = h->n_mono;
-    if (pt_index) std::copy(h->perm_pt.begin(), h->perm_pt.end(), pt_index);
+    if (pt_index) std::copy(h->plan.order.begin(), h->plan.order.end(), pt_index);
     return OMV_OK;
 }
 
@@ -3073,7 +2511,7 @@ omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda,
     if (!h || !o || !S || !rhs || !x || !fail || !plan || !(lambda > 0.0) || !std::isfinite(lambda)) return OMV_ERR_ARG;
     const BlockPat &B = h->BP;
     const int nb = B.nb, n = 16 * nb;
-    if (nb <= 0 || h->world != 1 || !h->d_S || plan_cap < 4 + B.n_lev) return OMV_ERR_ARG;
+    if (!has_problem(h) || h->world != 1 || plan_cap < 4 + B.n_lev) return OMV_ERR_ARG;
     const State &A = h->st[h->cur];
     omv_status rs;
     if ((rs = lba_errors(h, A)) != OMV_OK) return rs;
@@ -3083,14 +2521,11 @@ omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda,
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(h->stream));
     std::vector<double> blocks((size_t)B.n_slots * 256), bb(n), coef(n);
-    std::vector<int> kr(B.n_slots), kc(B.n_slots), lev(B.n_lev + 1);
+    const std::vector<int> &kr = h->plan.slot_kr, &kc = h->plan.slot_kc, &lev = h->plan.lev_start;
     HIP_OK(hipMemcpy(blocks.data(), h->d_S, blocks.size() * sizeof(double), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(bb.data(), h->d_bb, n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(coef.data(), h->d_coef, n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(x, h->d_x, n * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(kr.data(), B.slot_kr, kr.size() * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(kc.data(), B.slot_kc, kc.size() * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(lev.data(), B.lev_start, lev.size() * sizeof(int), hipMemcpyDeviceToHost));
     int f = 0;
     HIP_OK(hipMemcpy(&f, h->d_fail, sizeof(int), hipMemcpyDeviceToHost));
     *fail = f;
@@ -3106,7 +2541,7 @@ omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda,
             }
     }
     for (int q = 0; q < n; ++q) rhs[q] = bb[q] - coef[q];
-    plan[0] = h->use_lds, plan[1] = B.n_slots, plan[2] = B.n_lds, plan[3] = B.n_lev;
+    plan[0] = h->plan.use_lds, plan[1] = B.n_slots, plan[2] = B.n_lds, plan[3] = B.n_lev;
     for (int l = 0; l < B.n_lev; ++l) plan[4 + l] = lev[l + 1] - lev[l];
     return OMV_OK;
 }

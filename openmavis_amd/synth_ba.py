@@ -298,6 +298,42 @@ def make_lba_problem(n_kf=50, n_opt=25, n_pts=20000, seed=5, obs_noise=0.7, pt_n
     )
 
 
+# ---- variations of a problem that take the planner and the build off their common path ---------------
+def with_edgeless_points(prob, extra=700, seed=21):
+    """`extra` landmarks without edges appended (more than one build group's worth at the default)."""
+    prob = dict(prob)
+    rng = np.random.default_rng(seed)
+    n0 = len(prob["pts"])
+    new = np.asarray(prob["pts"])[rng.integers(0, n0, extra)] + rng.normal(0, 0.5, (extra, 3))
+    prob["pts"] = np.concatenate([prob["pts"], new])
+    prob["pt_track_depth"] = np.concatenate([prob["pt_track_depth"], rng.uniform(1, 60, extra).astype(np.float32)])
+    return prob
+
+
+def visual_only_with_fixed_only_points(prob, n_fixed_only=20):
+    """No inertial edges (kf_imu off), 6-dof pose blocks only; points 0 .. n_fixed_only-1 seen only by fixed keyframes."""
+    prob = dict(prob)
+    prob["kf_imu"] = np.zeros(prob["n_kf"], np.uint8)
+    for k in ("imu_kf1", "imu_kf2", "preint", "imu_robust", "imu_info_scale"):
+        prob[k] = prob[k][:0]
+    keep = ~((prob["mono_pt"] < n_fixed_only) & (prob["mono_kf"] < prob["n_opt"]))
+    for k in ("mono_pt", "mono_kf", "mono_cam", "mono_obs", "mono_inv_sigma2"):
+        prob[k] = prob[k][keep]
+    return prob
+
+
+def with_heavy_landmark(prob, times=60, seed=5):
+    """Landmark 0's observations repeated `times` x with noise: more edges than a build group holds (> 256)."""
+    prob = dict(prob)
+    rng = np.random.default_rng(seed)
+    rep = np.tile(np.flatnonzero(np.asarray(prob["mono_pt"]) == 0), times)
+    for k in ("mono_pt", "mono_kf", "mono_cam", "mono_inv_sigma2"):
+        prob[k] = np.concatenate([prob[k], np.asarray(prob[k])[rep]])
+    obs = np.asarray(prob["mono_obs"], np.float64)
+    prob["mono_obs"] = np.concatenate([obs, obs[rep] + rng.normal(0, 0.5, (len(rep), 2))])
+    return prob
+
+
 # ---- ctypes view (shared by the product binding and the oracle wrapper) -----------------------------
 DOUBLE_FIELDS = ("Rcb", "tcb", "Rbc", "tbc", "Rwb", "twb", "Rcw", "tcw", "vel", "bg", "ba", "pts", "mono_obs")
 

@@ -322,6 +322,38 @@ def lba_optimize(prob, opt_it=4, lambda_init=1e-2, max_trials=10, large=True, lo
     return res, read_state(keep), log[:r.trials].copy()
 
 
+def lba_plan(prob, rank=0, world=1, lds_ok=True, limits=None, edit=None):
+    """The product's own plan of an omv_lba_set_problem (openmavis_amd/csrc/lba_plan.h, built for the host by
+    lba_plan_host.cpp): (status, dict of every LbaPlan array and scalar, plus the limits kGrp* / kPanel / kLdltLds).
+    limits: (max_kf, max_cams, max_pts, max_mono, max_imu) of the handle; default: the problem's own sizes.
+    edit(struct): a last change to the omv_lba_problem that no problem dict expresses (a negative count, a null)."""
+    from openmavis_amd.synth_ba import as_struct
+    s, keep = as_struct(prob, LbaProblem)
+    if edit is not None:
+        edit(s)
+    if limits is None:
+        limits = (s.n_kf, s.n_cams, len(prob["pts"]), len(prob["mono_pt"]) + s.n_stereo, max(1, s.n_imu))
+    lim = np.asarray(limits, np.int32)
+    need = ctypes.c_int64(0)
+    args = (ctypes.byref(s), int(rank), int(world), int(bool(lds_ok)), _p(lim))
+    st = lib().oracle_lba_plan(*args, None, ctypes.c_int64(0), ctypes.byref(need))
+    if st != 0:
+        return st, None
+    buf = np.zeros(need.value, np.uint8)
+    st = lib().oracle_lba_plan(*args, _p(buf), ctypes.c_int64(len(buf)), ctypes.byref(need))
+    out, at = {}, 0
+    while at < len(buf):
+        name = bytes(buf[at:at + 22]).split(b"\0")[0].decode()
+        kind, elem = chr(buf[at + 22]), int(buf[at + 23])
+        count = int(buf[at + 24:at + 32].view(np.int64)[0])
+        a = buf[at + 32:at + 32 + count * elem].view(np.dtype(f"{kind}{elem}")).copy()
+        out[name] = int(a[0]) if (kind, elem, count) == ("i", 8, 1) else a
+        at += 32 + ((count * elem + 7) & ~7)
+    for k, w in (("ug", 4), ("inv_rec", 4), ("imu_blk", 4), ("rs", 2), ("cs", 2), ("imu_vec", 2)):
+        out[k] = out[k].reshape(-1, w)
+    return st, out
+
+
 # ---- PoseInertialOptimizationLastKeyFrame ---------------------------------------------------------
 def pose_last_kf(batch, rec_init=False):
     """Restated Optimizer::PoseInertialOptimizationLastKeyFrame on every frame of a synth_pose batch.

@@ -151,6 +151,64 @@ def test_lba_set_problem_failure_leaves_a_usable_handle(lib):
     assert _live(lib) == base
 
 
+def _same_bits(got, got_state, want, want_state):
+    for key in ("err", "err_end", "lambda_", "iterations", "trials", "status"):
+        assert got[key] == want[key], (key, got[key], want[key])
+    assert np.array_equal(got["mono_chi2"].view(np.uint64), want["mono_chi2"].view(np.uint64))
+    for key in ("Rwb", "twb", "Rcw", "tcw", "vel", "bg", "ba", "pts"):
+        assert np.array_equal(np.asarray(got_state[key]).view(np.uint64),
+                              np.asarray(want_state[key]).view(np.uint64)), key
+
+
+def test_lba_rejected_problem_leaves_the_previous_one(lib):
+    """OMV_ERR_ARG from omv_lba_set_problem: planned and rejected on the host before the handle is touched, so the
+    previous problem, its device memory and its captured steps stay valid."""
+    prob = synth_ba.make_lba_problem(n_kf=12, n_opt=4, n_pts=800, seed=3, n_cams=3)
+    kw = dict(opt_it=4, lambda_init=1e-2, max_trials=10, large=True)
+    ba = _lba(prob).set_problem(prob)
+    want, want_state = ba.optimize(**kw)
+    held = _live(lib)
+    bad = dict(prob, mono_kf=np.array(prob["mono_kf"], copy=True))
+    bad["mono_kf"][7] = prob["n_kf"]
+    s, keep = synth_ba.as_struct(bad, _lib.LbaProblem)
+    assert lib.omv_lba_set_problem(ba._h, ctypes.byref(s)) == _lib.OMV_ERR_ARG
+    assert _live(lib) == held
+    got, got_state = ba.reset().optimize(**kw)
+    _same_bits(got, got_state, want, want_state)
+
+
+def test_lba_failed_upload_leaves_no_problem(lib):
+    """OMV_ERR_HIP from omv_lba_set_problem: the handle ends without a problem, and every call that needs one says
+    OMV_ERR_ARG before it launches anything; a later set_problem makes the handle whole again."""
+    prob = synth_ba.make_lba_problem(n_kf=12, n_opt=4, n_pts=800, seed=3, n_cams=3)
+    kw = dict(opt_it=4, lambda_init=1e-2, max_trials=10, large=True)
+    base = _live(lib)
+    ba = _lba(prob)
+    own = _live(lib)
+    assert own == base + HANDLES["lba"][2]
+    want, want_state = ba.set_problem(prob).optimize(**kw)
+    _arm(lib, 1)   # the first state block
+    _fails_with_hip(lambda: ba.set_problem(prob))
+    _arm(lib, 0)
+    assert _live(lib) == own
+    s, keep = synth_ba.as_struct(prob, _lib.LbaProblem)
+    E, n = s.n_mono, 16 * s.n_opt
+    o, r = _lib.LbaOpts(4, 1e-2, 10, 1), _lib.LbaResult()
+    buf = np.zeros(max(18 * E, n * n))
+    fail, plan = ctypes.c_int(-1), np.zeros(4 + s.n_opt, np.int32)
+    assert lib.omv_lba_optimize(ba._h, ctypes.byref(o), ctypes.byref(s), ctypes.byref(r)) == _lib.OMV_ERR_ARG
+    assert lib.omv_lba_evaluate(ba._h, _lib.ptr(buf), None, None, None) == _lib.OMV_ERR_ARG
+    assert lib.omv_lba_evaluate_stereo(ba._h, _lib.ptr(buf), None, None) == _lib.OMV_ERR_ARG
+    assert lib.omv_lba_reset(ba._h) == _lib.OMV_ERR_ARG
+    assert lib.omv_lba_debug_solve(ba._h, ctypes.byref(o), ctypes.c_double(1.0), _lib.ptr(buf), _lib.ptr(buf[:n].copy()),
+                                   _lib.ptr(buf[:n].copy()), ctypes.byref(fail), _lib.ptr(plan), len(plan)) == _lib.OMV_ERR_ARG
+    assert _live(lib) == own
+    got, got_state = ba.set_problem(prob).optimize(**kw)
+    _same_bits(got, got_state, want, want_state)
+    ba.__del__()
+    assert _live(lib) == base
+
+
 # ---- buffers that grow on demand -------------------------------------------------------------------------------------
 W, H, C, NF = 720, 540, 5, 1200
 LAP = np.array([[0, 720], [0, 720], [0, 0], [0, 0], [0, 0]], np.int32)

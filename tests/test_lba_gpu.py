@@ -160,16 +160,8 @@ def test_optimize_with_stereo_edges(small_st, oracle, large):
 
 def test_optimize_visual_only_with_fixed_only_points(oracle):
     """No inertial edges (kf_imu off), 6-dof pose blocks only; some points seen only by fixed keyframes."""
-    prob = synth_ba.make_lba_problem(n_kf=12, n_opt=4, n_pts=800, seed=3, n_cams=3)
-    prob = dict(prob)
-    prob["kf_imu"] = np.zeros(prob["n_kf"], np.uint8)
-    for k in ("imu_kf1", "imu_kf2"):
-        prob[k] = prob[k][:0]
-    for k in ("preint", "imu_robust", "imu_info_scale"):
-        prob[k] = prob[k][:0]
-    keep = ~((prob["mono_pt"] < 20) & (prob["mono_kf"] < prob["n_opt"]))   # points 0..19: fixed views only
-    for k in ("mono_pt", "mono_kf", "mono_cam", "mono_obs", "mono_inv_sigma2"):
-        prob[k] = prob[k][keep]
+    prob = synth_ba.visual_only_with_fixed_only_points(   # points 0..19: fixed views only
+        synth_ba.make_lba_problem(n_kf=12, n_opt=4, n_pts=800, seed=3, n_cams=3))
     ro, so, _ = oracle.lba_optimize(prob, opt_it=10, lambda_init=1e0, max_trials=10, large=False)
     rg, sg = _solver(prob).set_problem(prob).optimize(opt_it=10, lambda_init=1e0, max_trials=10, large=False)
     _compare_result(prob, rg, ro)
@@ -179,12 +171,7 @@ def test_optimize_visual_only_with_fixed_only_points(oracle):
 def test_optimize_with_edgeless_points(small, oracle):
     """More than one build group's worth (> 256) of landmarks without edges, interleaved with observed ones: each
     still gets its (zero) Hll / bl, so the back-substitution and computeScale see no stale values."""
-    prob = dict(small)
-    rng = np.random.default_rng(21)
-    n0, extra = len(prob["pts"]), 700
-    new = np.asarray(prob["pts"])[rng.integers(0, n0, extra)] + rng.normal(0, 0.5, (extra, 3))
-    prob["pts"] = np.concatenate([prob["pts"], new])
-    prob["pt_track_depth"] = np.concatenate([prob["pt_track_depth"], rng.uniform(1, 60, extra).astype(np.float32)])
+    n0, prob = len(small["pts"]), synth_ba.with_edgeless_points(small, extra=700)
     for large in (True, False):
         kw = dict(opt_it=4, lambda_init=1e-2) if large else dict(opt_it=10, lambda_init=1e0)
         ro, so, _ = oracle.lba_optimize(prob, max_trials=10, large=large, **kw)
@@ -197,15 +184,8 @@ def test_optimize_with_edgeless_points(small, oracle):
 def test_optimize_with_heavy_landmark(small, oracle):
     """A landmark with more edges than a build group holds (> 256: its observations repeated 60x with noise) goes to the
     scalar one-landmark path (build_big_kernel) beside the MFMA groups; same bar against the oracle."""
-    prob = dict(small)
-    rng = np.random.default_rng(5)
-    sel = np.flatnonzero(np.asarray(prob["mono_pt"]) == 0)
-    rep = np.tile(sel, 60)
-    assert len(rep) > 256
-    for k in ("mono_pt", "mono_kf", "mono_cam", "mono_inv_sigma2"):
-        prob[k] = np.concatenate([prob[k], np.asarray(prob[k])[rep]])
-    obs = np.asarray(prob["mono_obs"], np.float64)
-    prob["mono_obs"] = np.concatenate([obs, obs[rep] + rng.normal(0, 0.5, (len(rep), 2))])
+    prob = synth_ba.with_heavy_landmark(small, times=60)
+    assert len(prob["mono_pt"]) - len(small["mono_pt"]) > 256
     for large in (True, False):
         kw = dict(opt_it=4, lambda_init=1e-2) if large else dict(opt_it=10, lambda_init=1e0)
         ro, so, _ = oracle.lba_optimize(prob, max_trials=10, large=large, **kw)
