@@ -297,6 +297,147 @@ __device__ __forceinline__ double rw_entry(int i, int j, bool acc, const double 
     return ((i < 15) == (j < 15)) ? O[3 * gi + gj] : -O[3 * gi + gj];
 }
 
+// ---- The g2o blocks both optimisation kernels are built from (pose_opt_kernel: one workgroup per frame;
+// pose_lat_kernel: the grouped latency path).  The formulas below stand here once; the kernels keep their own control
+// flow, wave roles, barriers and exchanges, and every sum keeps the operand order and nesting the parity tests were set
+// on.  Still written out in each kernel, because as shared functions they moved a kernel's spill / scratch / AGPR counts
+// (all four sit at the register ceiling; profiles/pose_blocks_ab.log has the figures): the robust visual accumulation,
+// the outlier rule (its cuts are copied from the constants below into per-kernel arrays), ImuCamPose::Update of a
+// vertex (its camera part is shared), the state load / write-back, and in the grouped kernel Info J and the un-weighted
+// accumulation. ----
+
+// Outlier thresholds of the four rounds (:5432 / :5992), the Huber deltas of the visual edges, and the cuts of the
+// "recover not too bad points" pass (:5503-5526 / :6074-6098).
+constexpr float kChi2Mono[2][4] = {{12.f, 7.5f, 5.991f, 5.991f}, {5.991f, 5.991f, 5.991f, 5.991f}};   // [kLF][round]
+constexpr float kChi2Stereo[4] = {15.6f, 9.8f, 7.815f, 7.815f};
+constexpr double kHuberMono2 = 5.991, kHuberStereo2 = 7.815;   // the visual edges' Huber deltas, squared
+constexpr float kRecoverMono = 18.f, kRecoverStereo = 24.f;
+
+// Entry (a, b), a <= b, of the visual 6x6 block in reduce_normal's upper-triangle layout.
+__device__ __forceinline__ double visual_entry(const double *nrm, int a, int b) {
+    return nrm[a * 6 - a * (a - 1) / 2 + (b - a)];
+}
+
+// The Hessian terms of one inlier visual edge without robust weights (the final information matrices, :5529-5571 /
+// :6112-6156).
+__device__ __forceinline__ void accumulate_edge_hessian(const Rig &rig, const double *Rcw, const double *tcw,
+                                                        const VEdge &v, double *acc) {
+    double r[3], Xc[3], JP[18];
+    edge_error_jac(rig, Rcw, tcw, v, r, Xc, JP);
+    const double om[3] = {0, 0, 0};
+    edge_normal(JP, v.stereo, v.w, om, acc);
+}
+
+// Entry q of EdgeInertial's Info J over NI Jacobian columns starting at column JO of J [9][JS].
+template <int NI, int JS = NI, int JO = 0>
+__device__ __forceinline__ double info_times_J(const double *info9, const double *J, int q) {
+    const int r = q / NI, c = q % NI;
+    double t = 0;
+    for (int k = 0; k < 9; ++k) t += info9[r * 9 + k] * J[k * JS + JO + c];
+    return t;
+}
+
+// EdgePriorPoseImu: entry q of H_prior J (15x15) and entry k of H_prior e.
+__device__ __forceinline__ double prior_times_J(const double *pH, const double *JPr, int q) {
+    const int k = q / 15, j = q % 15;
+    double t = 0;
+    for (int l = 0; l < 15; ++l) t += pH[k * 15 + l] * JPr[l * 15 + j];
+    return t;
+}
+__device__ __forceinline__ double prior_times_e(const double *pH, const double *eP, int k) {
+    double t = 0;
+    for (int l = 0; l < 15; ++l) t += pH[k * 15 + l] * eP[l];
+    return t;
+}
+
+// LastFrame: (J^T Info J) between EdgeInertial columns ci, cj, and (JPr^T w H_prior JPr) between the previous frame's
+// states i, j >= 15.
+__device__ __forceinline__ double lf_inertial_term(int ci, int cj, const double *J, const double *WJ) {
+    double t = 0;
+    for (int k = 0; k < 9; ++k) t += J[k * 24 + ci] * WJ[k * 24 + cj];
+    return t;
+}
+__device__ __forceinline__ double lf_prior_term(int i, int j, const double *JPr, const double *PJ, double w) {
+    double t = 0;
+    for (int k = 0; k < 15; ++k) t += JPr[k * 15 + i - 15] * (w * PJ[k * 15 + j - 15]);
+    return t;
+}
+
+// LastKeyFrame's 15x15 entry: the visual 6x6, EdgeInertial's J^T Info J over pose + velocity (J [9][JS] from column
+// JO, WJ [9][9]) and the random walks' information on the bias blocks.
+template <int JS, int JO>
+__device__ __forceinline__ double lkf_entry(int i, int j, const double *nrm, const double *J, const double *WJ,
+                                            const double *infoG, const double *infoA) {
+    double h = 0;
+    if (i < 6 && j < 6) h = visual_entry(nrm, min(i, j), max(i, j));   // symmetric from the upper triangle
+    if (i < 9 && j < 9) {
+        double t = 0;
+        for (int k = 0; k < 9; ++k) t += J[k * JS + JO + i] * WJ[k * 9 + j];
+        h += t;
+    }
+    if (i >= 9 && j >= 9 && (i < 12) == (j < 12)) h += (i < 12 ? infoG : infoA)[3 * ((i - 9) % 3) + (j - 9) % 3];
+    return h;
+}
+
+// LastFrame's 30x30 entry without robust weights, in the reference's order: EdgeInertial, EdgeGyroRW, EdgeAccRW,
+// EdgePriorPoseImu, visual.
+__device__ __forceinline__ double lf_entry_final(int i, int j, const double *nrm, const double *J, const double *WJ,
+                                                 const double *JPr, const double *PJ, const double *infoG,
+                                                 const double *infoA) {
+    double h = 0;
+    const int ci = ei_col(i), cj = ei_col(j);
+    if (ci >= 0 && cj >= 0) h += lf_inertial_term(ci, cj, J, WJ);
+    h += rw_entry(i, j, false, infoG);
+    h += rw_entry(i, j, true, infoA);
+    if (i >= 15 && j >= 15) h += lf_prior_term(i, j, JPr, PJ, 1.0);   // (1.0 * x is x)
+    if (i < 6 && j < 6) h += visual_entry(nrm, min(i, j), max(i, j));
+    return h;
+}
+
+// Optimizer::Marginalize(H, 0, 14) (:3388-3455) of the previous frame out of LastFrame's 30x30 Hs (frame 0-14, previous
+// 15-29): H_ff - H_fp pinv(H_pp) H_pf into Hout [225], JacobiSVD's pseudo-inverse of the symmetric H_pp as
+// V diag(1/w) V^T over |w| > 1e-6.  Workgroup-uniform (barriers inside); Hs must be complete on entry; PJ and JPr are
+// scratch.  Precondition: lane == tid & 63 (only wave 0, where it equals tid, uses it).  It is a parameter because
+// pinv15_wave is an out-of-line function shared with pose_constraint_kernel's helpers: each kernel hands it the value
+// it already holds (`tid` under tid < 64, or its `lane`), which keeps that function's code as it was.
+template <int Threads>
+__device__ __forceinline__ void marginalize_prev(const double *Hs, double *Am, double *Vm, double *PJ, double *JPr,
+                                                 double *ecs, int *epq, double *Hout, int tid, int lane) {
+    for (int q = tid; q < 225; q += Threads) Am[q] = Hs[(15 + q / 15) * 30 + 15 + q % 15];
+    __syncthreads();
+    if (tid < 64) pinv15_wave(Am, Vm, PJ, ecs, epq, lane);   // pinv(H_pp) -> PJ
+    __syncthreads();
+    for (int q = tid; q < 225; q += Threads) {   // T = H_fp pinv(H_pp) -> JPr
+        const int i = q / 15, j = q % 15;
+        double s = 0;
+        for (int k = 0; k < 15; ++k) s += Hs[i * 30 + 15 + k] * PJ[k * 15 + j];
+        JPr[q] = s;
+    }
+    __syncthreads();
+    for (int q = tid; q < 225; q += Threads) {
+        const int i = q / 15, j = q % 15;
+        double s = 0;
+        for (int k = 0; k < 15; ++k) s += JPr[i * 15 + k] * Hs[(15 + k) * 30 + j];
+        Hout[q] = Hs[i * 30 + j] - s;
+    }
+}
+
+// ImuCamPose::Update's camera part (G2oTypes.cc:226-234): Tbw, the inverse of the updated body pose, then camera c's
+// Rcw = Rcb Rbw, tcw = Rcb tbw + tcb.
+__device__ __forceinline__ void body_inverse(const double *Rwb, const double *twb, double *Rbw, double *tbw) {
+    tr3(Rwb, Rbw);
+    mv3(Rbw, twb, tbw);
+    for (int q = 0; q < 3; ++q) tbw[q] = -tbw[q];
+}
+__device__ __forceinline__ void refresh_camera(const Rig &rig, int c, const double *Rbw, const double *tbw, double *Rcw,
+                                               double *tcw) {
+    double Rc[9], tc[3];
+    mm3(rig.Rcb[c], Rbw, Rc);
+    mv3(rig.Rcb[c], tbw, tc);
+    for (int q = 0; q < 9; ++q) Rcw[9 * c + q] = Rc[q];
+    for (int q = 0; q < 3; ++q) tcw[3 * c + q] = tc[q] + rig.tcb[c][q];
+}
+
 // kLF = false: PoseInertialOptimizationLastKeyFrame (15 free states, the keyframe's vertices fixed);
 // kLF = true: PoseInertialOptimizationLastFrame (30 free states, EdgePriorPoseImu on the previous frame).
 template <bool kLF>
@@ -365,9 +506,9 @@ __global__ void __launch_bounds__(kPoseThreads, 2) pose_opt_kernel(Rig rig, Pose
     State st{sRwb, stwb, nullptr, nullptr, svel, sbg, sba, nullptr};
     Imu imu{};
     imu.n = 1, imu.kf1 = &k1s, imu.kf2 = &k2s, imu.pre = pre;
-    const double dmono = (double)(float)sqrt(5.991), dst = (double)(float)sqrt(7.815);
-    const float chi2Mono[4] = {kLF ? 5.991f : 12.f, kLF ? 5.991f : 7.5f, 5.991f, 5.991f};   // :5992 / :5432
-    const float chi2Stereo[4] = {15.6f, 9.8f, 7.815f, 7.815f};
+    const double dmono = (double)(float)sqrt(kHuberMono2), dst = (double)(float)sqrt(kHuberStereo2);
+    const float chi2Mono[4] = {kChi2Mono[kLF][0], kChi2Mono[kLF][1], kChi2Mono[kLF][2], kChi2Mono[kLF][3]};
+    const float chi2Stereo[4] = {kChi2Stereo[0], kChi2Stereo[1], kChi2Stereo[2], kChi2Stereo[3]};
     int nBad = 0, nIn = 0;
     // ImuCamPose::its of the pose vertex this thread updates (thread 0 the frame, thread 1 the previous frame): 0 at
     // the vertex's creation (G2oTypes.cc:74), Rwb normalised after every third Update (:220-225)
@@ -406,32 +547,12 @@ __global__ void __launch_bounds__(kPoseThreads, 2) pose_opt_kernel(Rig rig, Pose
             }
             reduce_normal(acc, red, nrm);   // (its barriers also publish J / e9 / eP / JPr)
             if constexpr (kLF) {
-                for (int q = tid; q < 216; q += kPoseThreads) {   // Info J over all 24 columns
-                    const int r = q / 24, c = q % 24;
-                    double t = 0;
-                    for (int k = 0; k < 9; ++k) t += info9[r * 9 + k] * J[k * 24 + c];
-                    WJ[q] = t;
-                }
-                for (int q = tid; q < 225; q += kPoseThreads) {   // H_prior J
-                    const int k = q / 15, j = q % 15;
-                    double t = 0;
-                    for (int l = 0; l < 15; ++l) t += pH[k * 15 + l] * JPr[l * 15 + j];
-                    PJ[q] = t;
-                }
-                if (tid >= 64 && tid < 79) {   // H_prior e
-                    const int k = tid - 64;
-                    double t = 0;
-                    for (int l = 0; l < 15; ++l) t += pH[k * 15 + l] * eP[l];
-                    OeP[k] = t;
-                }
+                for (int q = tid; q < 216; q += kPoseThreads) WJ[q] = info_times_J<24>(info9, J, q);   // all 24 columns
+                for (int q = tid; q < 225; q += kPoseThreads) PJ[q] = prior_times_J(pH, JPr, q);
+                if (tid >= 64 && tid < 79) OeP[tid - 64] = prior_times_e(pH, eP, tid - 64);
             } else {
                 // EdgeInertial: free columns 15-20 (frame pose) and 21-23 (frame velocity) -> state 0..8
-                for (int q = tid; q < 81; q += kPoseThreads) {
-                    const int r = q / 9, c = q % 9;
-                    double t = 0;
-                    for (int k = 0; k < 9; ++k) t += info9[r * 9 + k] * J[k * 24 + 15 + c];
-                    WJ[q] = t;
-                }
+                for (int q = tid; q < 81; q += kPoseThreads) WJ[q] = info_times_J<9, 24, 15>(info9, J, q);
             }
             if (tid < 9) {
                 double t = 0;
@@ -449,20 +570,12 @@ __global__ void __launch_bounds__(kPoseThreads, 2) pose_opt_kernel(Rig rig, Pose
                     const int i = q / N, j = q % N;
                     if (j > i) continue;
                     double h = 0;
-                    if (i < 6) h = nrm[j * 6 - j * (j - 1) / 2 + (i - j)];
+                    if (i < 6) h = visual_entry(nrm, j, i);
                     const int ci = ei_col(i), cj = ei_col(j);
-                    if (ci >= 0 && cj >= 0) {
-                        double t = 0;
-                        for (int k = 0; k < 9; ++k) t += J[k * 24 + ci] * WJ[k * 24 + cj];
-                        h += t;
-                    }
+                    if (ci >= 0 && cj >= 0) h += lf_inertial_term(ci, cj, J, WJ);
                     h += rw_entry(i, j, false, infoG);
                     h += rw_entry(i, j, true, infoA);
-                    if (i >= 15 && j >= 15) {
-                        double t = 0;
-                        for (int k = 0; k < 15; ++k) t += JPr[k * 15 + i - 15] * (w1p * PJ[k * 15 + j - 15]);
-                        h += t;
-                    }
+                    if (i >= 15 && j >= 15) h += lf_prior_term(i, j, JPr, PJ, w1p);
                     Hs[i * N + j] = h;
                     Hs[j * N + i] = h;
                 }
@@ -495,21 +608,8 @@ __global__ void __launch_bounds__(kPoseThreads, 2) pose_opt_kernel(Rig rig, Pose
                     bs[i] = t;
                 }
             } else {
-                for (int q = tid; q < 225; q += kPoseThreads) {
-                    const int i = q / 15, j = q % 15;
-                    double h = 0;
-                    if (i < 6 && j < 6) {   // visual 6x6 (symmetric from the upper triangle)
-                        const int a = min(i, j), b = max(i, j);
-                        h = nrm[a * 6 - a * (a - 1) / 2 + (b - a)];
-                    }
-                    if (i < 9 && j < 9) {
-                        double t = 0;
-                        for (int k = 0; k < 9; ++k) t += J[k * 24 + 15 + i] * WJ[k * 9 + j];
-                        h += t;
-                    }
-                    if (i >= 9 && j >= 9 && (i < 12) == (j < 12)) h += (i < 12 ? infoG : infoA)[3 * ((i - 9) % 3) + (j - 9) % 3];
-                    Hs[q] = h;
-                }
+                for (int q = tid; q < 225; q += kPoseThreads)
+                    Hs[q] = lkf_entry<24, 15>(q / 15, q % 15, nrm, J, WJ, infoG, infoA);
                 if (tid < 15) {
                     double t = tid < 6 ? nrm[21 + tid] : 0.0;
                     if (tid < 9) {
@@ -553,16 +653,8 @@ __global__ void __launch_bounds__(kPoseThreads, 2) pose_opt_kernel(Rig rig, Pose
                     for (int q = 0; q < 9; ++q) Rw[q] = Rn[q];
                     if (tid == 0) {
                         double Rbw[9], tbw[3];
-                        tr3(Rn, Rbw);
-                        mv3(Rbw, tw, tbw);
-                        for (int q = 0; q < 3; ++q) tbw[q] = -tbw[q];
-                        for (int c = 0; c < C; ++c) {
-                            double Rc[9], tc[3];
-                            mm3(rig.Rcb[c], Rbw, Rc);
-                            mv3(rig.Rcb[c], tbw, tc);
-                            for (int q = 0; q < 9; ++q) sRcw[9 * c + q] = Rc[q];
-                            for (int q = 0; q < 3; ++q) stcw[3 * c + q] = tc[q] + rig.tcb[c][q];
-                        }
+                        body_inverse(Rn, tw, Rbw, tbw);
+                        for (int c = 0; c < C; ++c) refresh_camera(rig, c, Rbw, tbw, sRcw, stcw);
                     }
                     for (int q = 0; q < 3; ++q)
                         svel[3 * v + q] += xv[6 + q], sbg[3 * v + q] += xv[9 + q], sba[3 * v + q] += xv[12 + q];
@@ -617,7 +709,7 @@ __global__ void __launch_bounds__(kPoseThreads, 2) pose_opt_kernel(Rig rig, Pose
             double r[3], Xc[3];
             const double c2 = edge_error(rig, sRcw, stcw, v, r, Xc);
             (stq ? A.chi2_s : A.chi2_m)[e] = c2;
-            if (c2 < (stq ? 24.f : 18.f)) kpo[v.kp] = 0;
+            if (c2 < (stq ? kRecoverStereo : kRecoverMono)) kpo[v.kp] = 0;
             else ++bad;
         }
         nBad = block_count(bad, cnt);
@@ -637,67 +729,18 @@ __global__ void __launch_bounds__(kPoseThreads, 2) pose_opt_kernel(Rig rig, Pose
                 const int e = stq ? s0 + q - nm : m0 + q;
                 const VEdge v = load_edge(A, stq, e);
                 if (kpo[v.kp]) continue;
-                double r[3], Xc[3], JP[18];
-                edge_error_jac(rig, sRcw, stcw, v, r, Xc, JP);
-                const double om[3] = {0, 0, 0};
-                edge_normal(JP, stq, v.w, om, acc);
+                accumulate_edge_hessian(rig, sRcw, stcw, v, acc);
             }
             if (tid == 0) imu_jacobian(st, imu, 0, J);
             if (tid == 64) prior_error_jac(sPr, sRwb, stwb, svel, sbg, sba, eP, JPr);
             reduce_normal(acc, red, nrm);
-            for (int q = tid; q < 216; q += kPoseThreads) {
-                const int r = q / 24, c = q % 24;
-                double t = 0;
-                for (int k = 0; k < 9; ++k) t += info9[r * 9 + k] * J[k * 24 + c];
-                WJ[q] = t;
-            }
-            for (int q = tid; q < 225; q += kPoseThreads) {
-                const int k = q / 15, j = q % 15;
-                double t = 0;
-                for (int l = 0; l < 15; ++l) t += pH[k * 15 + l] * JPr[l * 15 + j];
-                PJ[q] = t;
-            }
+            for (int q = tid; q < 216; q += kPoseThreads) WJ[q] = info_times_J<24>(info9, J, q);
+            for (int q = tid; q < 225; q += kPoseThreads) PJ[q] = prior_times_J(pH, JPr, q);
             __syncthreads();
-            for (int q = tid; q < N * N; q += kPoseThreads) {   // the reference's order: ei, egr, ear, ep, visual
-                const int i = q / N, j = q % N;
-                double h = 0;
-                const int ci = ei_col(i), cj = ei_col(j);
-                if (ci >= 0 && cj >= 0) {
-                    double t = 0;
-                    for (int k = 0; k < 9; ++k) t += J[k * 24 + ci] * WJ[k * 24 + cj];
-                    h += t;
-                }
-                h += rw_entry(i, j, false, infoG);
-                h += rw_entry(i, j, true, infoA);
-                if (i >= 15 && j >= 15) {
-                    double t = 0;
-                    for (int k = 0; k < 15; ++k) t += JPr[k * 15 + i - 15] * PJ[k * 15 + j - 15];
-                    h += t;
-                }
-                if (i < 6 && j < 6) {
-                    const int a = min(i, j), b = max(i, j);
-                    h += nrm[a * 6 - a * (a - 1) / 2 + (b - a)];
-                }
-                Hs[q] = h;
-            }
+            for (int q = tid; q < N * N; q += kPoseThreads)
+                Hs[q] = lf_entry_final(q / N, q % N, nrm, J, WJ, JPr, PJ, infoG, infoA);
             __syncthreads();
-            for (int q = tid; q < 225; q += kPoseThreads) Am[q] = Hs[(15 + q / 15) * N + 15 + q % 15];
-            __syncthreads();
-            if (tid < 64) pinv15_wave(Am, Vm, PJ, ecs, epq, tid);   // pinv(H_pp) -> PJ
-            __syncthreads();
-            for (int q = tid; q < 225; q += kPoseThreads) {   // T = H_fp pinv(H_pp) -> JPr
-                const int i = q / 15, j = q % 15;
-                double s = 0;
-                for (int k = 0; k < 15; ++k) s += Hs[i * N + 15 + k] * PJ[k * 15 + j];
-                JPr[q] = s;
-            }
-            __syncthreads();
-            for (int q = tid; q < 225; q += kPoseThreads) {
-                const int i = q / 15, j = q % 15;
-                double s = 0;
-                for (int k = 0; k < 15; ++k) s += JPr[i * 15 + k] * Hs[(15 + k) * N + j];
-                A.H[(size_t)f * 225 + q] = Hs[i * N + j] - s;
-            }
+            marginalize_prev<kPoseThreads>(Hs, Am, Vm, PJ, JPr, ecs, epq, A.H + (size_t)f * 225, tid, tid);
         }
     } else if (A.H) {
         // ConstraintPoseImu's Hessian (:5529-5571): information without robust weights, inlier edges only
@@ -708,35 +751,14 @@ __global__ void __launch_bounds__(kPoseThreads, 2) pose_opt_kernel(Rig rig, Pose
             const int e = stq ? s0 + q - nm : m0 + q;
             const VEdge v = load_edge(A, stq, e);
             if (kpo[v.kp]) continue;
-            double r[3], Xc[3], JP[18];
-            edge_error_jac(rig, sRcw, stcw, v, r, Xc, JP);
-            const double om[3] = {0, 0, 0};
-            edge_normal(JP, stq, v.w, om, acc);
+            accumulate_edge_hessian(rig, sRcw, stcw, v, acc);
         }
         if (tid == 0) imu_error_jac_p2v2(st, imu, 0, e9, J);
         reduce_normal(acc, red, nrm);
-        for (int q = tid; q < 81; q += kPoseThreads) {
-            const int r = q / 9, c = q % 9;
-            double t = 0;
-            for (int k = 0; k < 9; ++k) t += info9[r * 9 + k] * J[k * 24 + 15 + c];
-            WJ[q] = t;
-        }
+        for (int q = tid; q < 81; q += kPoseThreads) WJ[q] = info_times_J<9, 24, 15>(info9, J, q);
         __syncthreads();
-        for (int q = tid; q < 225; q += kPoseThreads) {
-            const int i = q / 15, j = q % 15;
-            double h = 0;
-            if (i < 6 && j < 6) {
-                const int a = min(i, j), b = max(i, j);
-                h = nrm[a * 6 - a * (a - 1) / 2 + (b - a)];
-            }
-            if (i < 9 && j < 9) {
-                double t = 0;
-                for (int k = 0; k < 9; ++k) t += J[k * 24 + 15 + i] * WJ[k * 9 + j];
-                h += t;
-            }
-            if (i >= 9 && j >= 9 && (i < 12) == (j < 12)) h += (i < 12 ? infoG : infoA)[3 * ((i - 9) % 3) + (j - 9) % 3];
-            A.H[(size_t)f * 225 + q] = h;
-        }
+        for (int q = tid; q < 225; q += kPoseThreads)
+            A.H[(size_t)f * 225 + q] = lkf_entry<24, 15>(q / 15, q % 15, nrm, J, WJ, infoG, infoA);
     }
     // state back
     if (tid == 0) {
@@ -1289,17 +1311,8 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
             if (lane == 0) prior_error_jac(sPr, sRwb, stwb, svel, sbg, sba, eP, JPr);
             omv::wave_lds_sync();
             for (int q = lane; q < 240; q += 64) {
-                if (q < 225) {
-                    const int k = q / 15, j = q % 15;
-                    double t = 0;
-                    for (int l = 0; l < 15; ++l) t += pH[k * 15 + l] * JPr[l * 15 + j];
-                    PJ[q] = t;
-                } else if (sys) {
-                    const int k = q - 225;
-                    double t = 0;
-                    for (int l = 0; l < 15; ++l) t += pH[k * 15 + l] * eP[l];
-                    OeP[k] = t;
-                }
+                if (q < 225) PJ[q] = prior_times_J(pH, JPr, q);
+                else if (sys) OeP[q - 225] = prior_times_e(pH, eP, q - 225);
             }
             if (!sys) return;
             omv::wave_lds_sync();
@@ -1317,9 +1330,9 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
     __syncthreads();
     if (s_abort) goto fail;
     {
-        const double dmono = (double)(float)sqrt(5.991), dst = (double)(float)sqrt(7.815);
-        const float chi2Mono[4] = {kLF ? 5.991f : 12.f, kLF ? 5.991f : 7.5f, 5.991f, 5.991f};   // :5992 / :5432
-        const float chi2Stereo[4] = {15.6f, 9.8f, 7.815f, 7.815f};
+        const double dmono = (double)(float)sqrt(kHuberMono2), dst = (double)(float)sqrt(kHuberStereo2);
+        const float chi2Mono[4] = {kChi2Mono[kLF][0], kChi2Mono[kLF][1], kChi2Mono[kLF][2], kChi2Mono[kLF][3]};
+        const float chi2Stereo[4] = {kChi2Stereo[0], kChi2Stereo[1], kChi2Stereo[2], kChi2Stereo[3]};
         double nBad = 0, nIn = 0;
         // ImuCamPose::its of the pose vertex this lane updates (lane 0 the frame, lane 1 the previous frame): 0 at the
         // vertex's creation (G2oTypes.cc:74), Rwb normalised after every third Update (:220-225)
@@ -1407,20 +1420,11 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
                     const int j = q - i * (i + 1) / 2;
                     const int fi = red_full(i), fj = red_full(j);
                     double h = 0;
-                    if (fi < 6) h = nrm[fj * 6 - fj * (fj - 1) / 2 + (fi - fj)];
+                    if (fi < 6) h = visual_entry(nrm, fj, fi);
                     if constexpr (kLF) {
                         const int ci = ei_col(fi), cj = ei_col(fj);
-                        if (ci >= 0 && cj >= 0) {   // (J^T Info J)_ci,cj
-                            double t = 0;
-                            for (int k = 0; k < 9; ++k) t += J[k * 24 + ci] * WJ[k * 24 + cj];
-                            h += t;
-                        }
-                        if (fi >= 15 && fj >= 15) {   // (JPr^T w H_prior JPr)_i,j
-                            const double w1p = s_w1p;
-                            double t = 0;
-                            for (int k = 0; k < 15; ++k) t += JPr[k * 15 + fi - 15] * (w1p * PJ[k * 15 + fj - 15]);
-                            h += t;
-                        }
+                        if (ci >= 0 && cj >= 0) h += lf_inertial_term(ci, cj, J, WJ);
+                        if (fi >= 15 && fj >= 15) h += lf_prior_term(fi, fj, JPr, PJ, s_w1p);
                     } else {
                         double t = 0;
                         for (int k = 0; k < 9; ++k) t += J[k * 9 + fi] * WJ[k * 9 + fj];
@@ -1476,15 +1480,9 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
                     }
                     omv::wave_lds_sync();
                     if (lane < C) {
-                        const int c = lane;
-                        double Rbw[9], tbw[3], Rc[9], tc[3];
-                        tr3(sRwb + 9, Rbw);
-                        mv3(Rbw, stwb + 3, tbw);
-                        for (int q = 0; q < 3; ++q) tbw[q] = -tbw[q];
-                        mm3(rig.Rcb[c], Rbw, Rc);
-                        mv3(rig.Rcb[c], tbw, tc);
-                        for (int q = 0; q < 9; ++q) sRcw[9 * c + q] = Rc[q];
-                        for (int q = 0; q < 3; ++q) stcw[3 * c + q] = tc[q] + rig.tcb[c][q];
+                        double Rbw[9], tbw[3];
+                        body_inverse(sRwb + 9, stwb + 3, Rbw, tbw);
+                        refresh_camera(rig, lane, Rbw, tbw, sRcw, stcw);
                     }
                 }
                 __syncthreads();
@@ -1558,7 +1556,7 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
                     double r[3], Xc[3];
                     const double c2 = edge_error(rig, sRcw, stcw, v, r, Xc);
                     E.c2[q] = c2;
-                    if (c2 < (v.stereo ? 24.f : 18.f)) E.kpo[v.kp] = 0;
+                    if (c2 < (v.stereo ? kRecoverStereo : kRecoverMono)) E.kpo[v.kp] = 0;
                     else bad += 1;
                 }
             double cnt1[1] = {bad};
@@ -1616,64 +1614,13 @@ __global__ void __launch_bounds__(kLatThreads) pose_lat_kernel(Rig rig_in, PoseA
             if (s_abort) goto fail;
             if (g == 0) {
                 if constexpr (kLF) {
-                    for (int q = tid; q < N * N; q += kLatThreads) {   // the reference's order: ei, egr, ear, ep, visual
-                        const int i = q / N, j = q % N;
-                        double h = 0;
-                        const int ci = ei_col(i), cj = ei_col(j);
-                        if (ci >= 0 && cj >= 0) {
-                            double t = 0;
-                            for (int k = 0; k < 9; ++k) t += J[k * 24 + ci] * WJ[k * 24 + cj];
-                            h += t;
-                        }
-                        h += rw_entry(i, j, false, infoG);
-                        h += rw_entry(i, j, true, infoA);
-                        if (i >= 15 && j >= 15) {
-                            double t = 0;
-                            for (int k = 0; k < 15; ++k) t += JPr[k * 15 + i - 15] * PJ[k * 15 + j - 15];
-                            h += t;
-                        }
-                        if (i < 6 && j < 6) {
-                            const int a = min(i, j), b = max(i, j);
-                            h += nrm[a * 6 - a * (a - 1) / 2 + (b - a)];
-                        }
-                        Hs[q] = h;
-                    }
+                    for (int q = tid; q < N * N; q += kLatThreads)
+                        Hs[q] = lf_entry_final(q / N, q % N, nrm, J, WJ, JPr, PJ, infoG, infoA);
                     __syncthreads();
-                    // Marginalize(H, 0, 14) (:3388-3455) of the previous frame: H_ff - H_fp pinv(H_pp) H_pf
-                    for (int q = tid; q < 225; q += kLatThreads) Am[q] = Hs[(15 + q / 15) * N + 15 + q % 15];
-                    __syncthreads();
-                    if (wave == 0) pinv15_wave(Am, Vm, PJ, ecs, epq, lane);   // pinv(H_pp) -> PJ
-                    __syncthreads();
-                    for (int q = tid; q < 225; q += kLatThreads) {   // T = H_fp pinv(H_pp) -> JPr
-                        const int i = q / 15, j = q % 15;
-                        double s = 0;
-                        for (int k = 0; k < 15; ++k) s += Hs[i * N + 15 + k] * PJ[k * 15 + j];
-                        JPr[q] = s;
-                    }
-                    __syncthreads();
-                    for (int q = tid; q < 225; q += kLatThreads) {
-                        const int i = q / 15, j = q % 15;
-                        double s = 0;
-                        for (int k = 0; k < 15; ++k) s += JPr[i * 15 + k] * Hs[(15 + k) * N + j];
-                        A.H[(size_t)f * 225 + q] = Hs[i * N + j] - s;
-                    }
+                    marginalize_prev<kLatThreads>(Hs, Am, Vm, PJ, JPr, ecs, epq, A.H + (size_t)f * 225, tid, lane);
                 } else {
-                    for (int q = tid; q < 225; q += kLatThreads) {
-                        const int i = q / 15, j = q % 15;
-                        double h = 0;
-                        if (i < 6 && j < 6) {
-                            const int a = min(i, j), b = max(i, j);
-                            h = nrm[a * 6 - a * (a - 1) / 2 + (b - a)];
-                        }
-                        if (i < 9 && j < 9) {
-                            double t = 0;
-                            for (int k = 0; k < 9; ++k) t += J[k * 9 + i] * WJ[k * 9 + j];
-                            h += t;
-                        }
-                        if (i >= 9 && j >= 9 && (i < 12) == (j < 12))
-                            h += (i < 12 ? infoG : infoA)[3 * ((i - 9) % 3) + (j - 9) % 3];
-                        A.H[(size_t)f * 225 + q] = h;
-                    }
+                    for (int q = tid; q < 225; q += kLatThreads)
+                        A.H[(size_t)f * 225 + q] = lkf_entry<9, 0>(q / 15, q % 15, nrm, J, WJ, infoG, infoA);
                 }
             }
         }
@@ -2364,37 +2311,88 @@ omv_status omv_pose_last_error(omv_pose *h, int32_t *err, void *stream) {
 
 namespace {
 
-// Both optimisations: validate, fill the kernel arguments, launch the information kernel and the
-// one-workgroup-per-frame optimisation.  prior == nullptr: LastKeyFrame.
-omv_status launch_pose(omv_pose *h, const omv_pose_batch *b, const omv_pose_prior *prior, int rec_init,
-                       uint8_t *kp_outlier, int32_t *n_good, double *H, void *stream) {
-    if (!h || !b || !kp_outlier || !n_good) return OMV_ERR_ARG;
-    if (b->n_frames <= 0 || b->n_frames > h->max_frames || b->n_cams <= 0 || b->n_cams > kMaxCams ||
-        b->n_mono < 0 || b->n_stereo < 0 || b->n_mono > h->max_edges || b->n_stereo > h->max_edges || b->kp_cap <= 0)
-        return OMV_ERR_ARG;
-    if (prior && (!prior->Rwb || !prior->twb || !prior->vel || !prior->bg || !prior->ba || !prior->H ||
-                  !prior->preint_kf))
-        return OMV_ERR_ARG;
-    if (!b->cam || !b->Rcb || !b->tcb || !b->Rbc || !b->tbc || !b->Rwb || !b->twb || !b->Rcw || !b->tcw || !b->vel ||
-        !b->bg || !b->ba || !b->kf_Rwb || !b->kf_twb || !b->kf_vel || !b->kf_bg || !b->kf_ba || !b->preint ||
-        !b->mono_start || !b->stereo_start)
-        return OMV_ERR_ARG;
+// The batch's counts against the handle's capacity, and its camera / edge-offset arrays.
+bool batch_ok(const omv_pose *h, const omv_pose_batch *b) {
+    return b->n_frames > 0 && b->n_frames <= h->max_frames && b->n_cams > 0 && b->n_cams <= kMaxCams && b->n_mono >= 0 &&
+           b->n_stereo >= 0 && b->n_mono <= h->max_edges && b->n_stereo <= h->max_edges && b->kp_cap > 0 && b->cam &&
+           b->mono_start && b->stereo_start;
+}
+
+// Every edge array the kernel reads must be present when its kind has edges (the Python binding leaves absent keys
+// NULL): an error on the host instead of a fault on the device.  need_cam_and_close: the inertial optimisations also
+// read mono_close and stereo_cam.
+bool edge_arrays_ok(const omv_pose_batch *b, bool need_cam_and_close) {
     if (b->n_mono > 0 && (!b->mono_cam || !b->mono_kp || !b->mono_obs || !b->mono_inv_sigma2 || !b->mono_xw ||
-                          !b->mono_close))
-        return OMV_ERR_ARG;
-    if (b->n_stereo > 0 && (!b->stereo_cam || !b->stereo_kp || !b->stereo_obs || !b->stereo_inv_sigma2 ||
-                            !b->stereo_xw))
-        return OMV_ERR_ARG;
-    Rig rig{};
+                          (need_cam_and_close && !b->mono_close)))
+        return false;
+    if (b->n_stereo > 0 && ((need_cam_and_close && !b->stereo_cam) || !b->stereo_kp || !b->stereo_obs ||
+                            !b->stereo_inv_sigma2 || !b->stereo_xw))
+        return false;
+    return true;
+}
+
+// What every pose call reads of the batch's rig: the camera count, intrinsics and models (nothing else of `b`);
+// false on a camera model other than KB8 / pinhole.
+bool fill_rig(const omv_pose_batch *b, Rig &rig) {
     rig.n_cams = b->n_cams;
     for (int c = 0; c < b->n_cams; ++c) {
         for (int q = 0; q < 8; ++q) rig.cam[c][q] = b->cam[8 * c + q];
         rig.model[c] = b->cam_model ? b->cam_model[c] : OMV_CAM_KB8;
-        if (rig.model[c] != OMV_CAM_KB8 && rig.model[c] != OMV_CAM_PINHOLE) return OMV_ERR_ARG;
+        if (rig.model[c] != OMV_CAM_KB8 && rig.model[c] != OMV_CAM_PINHOLE) return false;
+    }
+    return true;
+}
+
+// Path: the grouped kernel (G workgroups per frame, latency) for a few frames, the one-workgroup-per-frame kernel for
+// batches.  A part holds at most kLatCap edges and a frame's edges are split over its G parts, so G is sized from the
+// largest frame the batch can hold: no frame has more than ne_tot edges (the per-frame counts live on the device).
+// AUTO takes the grouped kernel only when that bound fits kLatMaxParts parts.  parts == 0: one visual edge per
+// edge-wave thread of the mean frame (parts hold ne / G edges up to one keypoint's two, lat_bound_wave).
+struct PosePath {
+    omv_status status;
+    bool grouped;
+    int G;
+};
+PosePath choose_path(int mode, int parts, int F, long long ne_tot, int kp_cap, bool last_frame) {
+    const long long g_need = (ne_tot + kLatCap - 3) / (kLatCap - 2);
+    const bool grouped_ok = kp_cap <= kLatFlagCap;
+    const bool grouped = mode == OMV_POSE_GROUPED ||
+                         (mode == OMV_POSE_AUTO && F <= kLatAutoFrames && grouped_ok && g_need <= kLatMaxParts);
+    if (mode == OMV_POSE_GROUPED && !grouped_ok) return {OMV_ERR_ARG, false, 0};
+    int G = parts;
+    const int et = lat_edge_threads(last_frame);
+    if (G == 0) {
+        G = (int)std::min<long long>(kLatMaxParts, std::max<long long>(1, (ne_tot / F + et - 3) / (et - 2)));
+        G = (int)std::min<long long>(kLatMaxParts, std::max<long long>(G, g_need));
+    }
+    return {OMV_OK, grouped, G};
+}
+
+// Both inertial optimisations: validate, choose the path, launch (the one-workgroup-per-frame kernel after its
+// information kernel, or the grouped kernel).  prior == nullptr: LastKeyFrame.
+omv_status launch_pose(omv_pose *h, const omv_pose_batch *b, const omv_pose_prior *prior, int rec_init,
+                       uint8_t *kp_outlier, int32_t *n_good, double *H, void *stream) {
+    if (!h || !b || !kp_outlier || !n_good || !batch_ok(h, b)) return OMV_ERR_ARG;
+    if (prior && (!prior->Rwb || !prior->twb || !prior->vel || !prior->bg || !prior->ba || !prior->H ||
+                  !prior->preint_kf))
+        return OMV_ERR_ARG;
+    if (!b->Rcb || !b->tcb || !b->Rbc || !b->tbc || !b->Rwb || !b->twb || !b->Rcw || !b->tcw || !b->vel || !b->bg ||
+        !b->ba || !b->kf_Rwb || !b->kf_twb || !b->kf_vel || !b->kf_bg || !b->kf_ba || !b->preint)
+        return OMV_ERR_ARG;
+    if (!edge_arrays_ok(b, true)) return OMV_ERR_ARG;
+    Rig rig{};
+    if (!fill_rig(b, rig)) return OMV_ERR_ARG;
+    for (int c = 0; c < b->n_cams; ++c) {   // the body-camera extrinsics and bf: the inertial optimisations only
         for (int q = 0; q < 9; ++q) rig.Rcb[c][q] = b->Rcb[9 * c + q], rig.Rbc[c][q] = b->Rbc[9 * c + q];
         for (int q = 0; q < 3; ++q) rig.tcb[c][q] = b->tcb[3 * c + q], rig.tbc[c][q] = b->tbc[3 * c + q];
     }
     rig.bf = (double)b->bf;
+    const int F = b->n_frames;
+    const PosePath path =
+        choose_path(h->mode, h->parts, F, (long long)b->n_mono + b->n_stereo, b->kp_cap, prior != nullptr);
+    if (path.status != OMV_OK) return path.status;
+    const bool grouped = path.grouped;
+    const int G = path.G;
     PoseArgs A{b->Rwb, b->twb, b->Rcw, b->tcw, b->vel, b->bg, b->ba, b->kf_Rwb, b->kf_twb, b->kf_vel, b->kf_bg,
                b->kf_ba, b->preint, b->mono_start, b->mono_cam, b->mono_kp, b->mono_obs, b->mono_inv_sigma2,
                b->mono_xw, b->mono_close, b->stereo_start, b->stereo_cam, b->stereo_kp, b->stereo_obs,
@@ -2404,25 +2402,6 @@ omv_status launch_pose(omv_pose *h, const omv_pose_batch *b, const omv_pose_prio
     if (prior) {
         A.pRwb = prior->Rwb, A.ptwb = prior->twb, A.pvel = prior->vel, A.pbg = prior->bg, A.pba = prior->ba;
         A.pH = prior->H;
-    }
-    // Path: the grouped kernel (G workgroups per frame, latency) for a few frames, the one-workgroup-per-frame kernel
-    // for batches.  G from the mean edge count: one visual edge per edge-wave thread.
-    const int F = b->n_frames;
-    const long long ne_tot = (long long)b->n_mono + b->n_stereo;
-    // A part holds at most kLatCap edges and a frame's edges are split over its G parts, so G is sized from the largest
-    // frame the batch can hold: no frame has more than ne_tot edges (the per-frame counts live on the device).  AUTO
-    // takes the grouped kernel only when that bound fits kLatMaxParts parts.
-    const long long g_need = (ne_tot + kLatCap - 3) / (kLatCap - 2);
-    const bool grouped_ok = b->kp_cap <= kLatFlagCap;
-    bool grouped = h->mode == OMV_POSE_GROUPED ||
-                   (h->mode == OMV_POSE_AUTO && F <= kLatAutoFrames && grouped_ok && g_need <= kLatMaxParts);
-    if (h->mode == OMV_POSE_GROUPED && !grouped_ok) return OMV_ERR_ARG;
-    int G = h->parts;
-    const int et = lat_edge_threads(prior != nullptr);
-    // one edge per edge-wave thread: parts hold ne / G edges up to one keypoint's two (lat_bound_wave)
-    if (G == 0) {
-        G = (int)std::min<long long>(kLatMaxParts, std::max<long long>(1, (ne_tot / F + et - 3) / (et - 2)));
-        G = (int)std::min<long long>(kLatMaxParts, std::max<long long>(G, g_need));
     }
     if (!grouped) pose_info_kernel<<<F, 64, 0, st>>>(b->preint, prior ? prior->preint_kf : b->preint, h->info);
     if (grouped) {
@@ -2477,22 +2456,10 @@ omv_status omv_pose_inertial_last_frame(omv_pose *h, const omv_pose_batch *b, co
 omv_status omv_pose_optimization(omv_pose *h, const omv_pose_batch *b, const double *rig_q, const double *rig_t,
                                  double *pose_q, double *pose_t, uint8_t *kp_outlier, int32_t *n_good, void *stream) {
     if (!h || !b || !rig_q || !rig_t || !pose_q || !pose_t || !kp_outlier || !n_good) return OMV_ERR_ARG;
-    if (b->n_frames <= 0 || b->n_frames > h->max_frames || b->n_cams <= 0 || b->n_cams > kMaxCams || b->n_mono < 0 ||
-        b->n_stereo < 0 || b->n_mono > h->max_edges || b->n_stereo > h->max_edges || b->kp_cap <= 0 || !b->cam ||
-        !b->mono_start || !b->stereo_start)
-        return OMV_ERR_ARG;
-    // every edge array the kernel reads must be present when its kind has edges (the Python binding leaves absent
-    // keys NULL): an error here instead of a fault on the device
-    if (b->n_mono > 0 && (!b->mono_kp || !b->mono_obs || !b->mono_inv_sigma2 || !b->mono_xw || !b->mono_cam))
-        return OMV_ERR_ARG;
-    if (b->n_stereo > 0 && (!b->stereo_kp || !b->stereo_obs || !b->stereo_inv_sigma2 || !b->stereo_xw))
-        return OMV_ERR_ARG;
+    if (!batch_ok(h, b) || !edge_arrays_ok(b, false)) return OMV_ERR_ARG;
     PoseOnlyRig P{};
-    P.rig.n_cams = b->n_cams;
+    if (!fill_rig(b, P.rig)) return OMV_ERR_ARG;
     for (int c = 0; c < b->n_cams; ++c) {
-        for (int q = 0; q < 8; ++q) P.rig.cam[c][q] = b->cam[8 * c + q];
-        P.rig.model[c] = b->cam_model ? b->cam_model[c] : OMV_CAM_KB8;
-        if (P.rig.model[c] != OMV_CAM_KB8 && P.rig.model[c] != OMV_CAM_PINHOLE) return OMV_ERR_ARG;
         // SE3Quat(q, t): normalised, w >= 0; toRotationMatrix for the Jacobian
         double q[4] = {rig_q[4 * c], rig_q[4 * c + 1], rig_q[4 * c + 2], rig_q[4 * c + 3]};
         if (q[3] < 0) q[0] = -q[0], q[1] = -q[1], q[2] = -q[2], q[3] = -q[3];

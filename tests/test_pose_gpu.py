@@ -22,7 +22,7 @@ MODES = [(PoseInertialOptimizer.BATCH, 0), (PoseInertialOptimizer.GROUPED, 0), (
          (PoseInertialOptimizer.GROUPED, 8)]
 
 
-def _run_gpu(b, rec_init=False, mode=(PoseInertialOptimizer.AUTO, 0)):
+def _run_gpu(b, rec_init=False, mode=(PoseInertialOptimizer.AUTO, 0), with_H=True):
     import torch
     dev = "cuda:0"
     arrays = {}
@@ -32,14 +32,14 @@ def _run_gpu(b, rec_init=False, mode=(PoseInertialOptimizer.AUTO, 0)):
         arrays[k] = torch.from_numpy(np.ascontiguousarray(b[k])).to(dev)
     F, cap = int(b["n_frames"]), int(b["kp_cap"])
     kpo = torch.full((F, cap), 255, dtype=torch.uint8, device=dev)
-    H = torch.zeros((F, 225), dtype=torch.float64, device=dev)
+    H = torch.zeros((F, 225), dtype=torch.float64, device=dev) if with_H else None
     opt = PoseInertialOptimizer(max_frames=F, max_edges=max(len(b["mono_cam"]), len(b["stereo_cam"]), 1))
     opt.set_mode(*mode)
     n_good = opt.PoseInertialOptimizationLastKeyFrame(b, arrays, kpo, H, bRecInit=rec_init)
     torch.cuda.synchronize()
     assert opt.last_error() == 0
     st = {k: arrays[k].cpu().numpy() for k in synth_pose.STATE_KEYS}
-    return st, kpo.cpu().numpy(), n_good.cpu().numpy(), H.cpu().numpy()
+    return st, kpo.cpu().numpy(), n_good.cpu().numpy(), H.cpu().numpy() if with_H else None
 
 
 def _compare(b, g, o):
@@ -119,3 +119,16 @@ def test_auto_mode_heavy_frame_among_light_ones(oracle):
     assert np.diff(b["mono_start"]).max() > 1024 * 2
     o = oracle.pose_last_kf(b)
     _compare(b, _run_gpu(b), o)
+
+
+def test_pose_without_hessian_is_the_same_run():
+    """H == nullptr: the Hessian step runs after the last update and only reads, so the state, mvbOutlier and the return
+    value are byte-equal to the run that asks for H (one workgroup per frame, and the grouped kernel with 3 parts)."""
+    b = synth_pose.make_pose_batch(n_frames=2, n_pts=40, seed=3, outlier_frac=0.5)
+    for mode in [(PoseInertialOptimizer.BATCH, 0), (PoseInertialOptimizer.GROUPED, 3)]:
+        st_h, k_h, n_h, _ = _run_gpu(b, mode=mode)
+        st_0, k_0, n_0, _ = _run_gpu(b, mode=mode, with_H=False)
+        for k in synth_pose.STATE_KEYS:
+            assert st_0[k].tobytes() == st_h[k].tobytes(), (mode, k)
+        assert k_0.tobytes() == k_h.tobytes(), mode
+        assert n_0.tobytes() == n_h.tobytes(), mode
