@@ -1202,6 +1202,12 @@ omv_status omv_selftest_inv16(int batch, const double *D, double *Dinv, int32_t 
  *   PREDICT_SCALE_CLAMPED the same with b[1] = the number of levels (as a float) -> int32 clamped to [0, levels - 1]
  *   ROT_BIN (a = angle1, b = angle2) -> int32, the matchers' rotation-histogram bin
  *   THREE_MAXIMA a = int32 histograms [n][30] -> int32 [n][3], ComputeThreeMaxima's indices (-1: absent)
+ *   GRID_CELL_OF a = keypoint (x, y) [n][2], b = (min_x, min_y, cell width inverse, cell height inverse) -> int32, the
+ *                grid cell column * 48 + row of Frame::PosInGrid (-1: outside the grid)
+ *   GRID_WINDOW  a = (x, y, r) [n][3], b as above -> int32 [n][4], the cells (min column, max column, min row, max
+ *                row) Frame::GetFeaturesInArea visits; four -1 when the window misses the grid
+ *   KP_IN_WINDOW a = (keypoint x, y, octave, window x, y, r, minLevel, maxLevel) [n][8], the three integers as floats
+ *                -> int32 1 / 0, GetFeaturesInArea's test of one keypoint of a visited cell
  * An unknown fn, n < 0, or a NULL among the pointers fn reads with n > 0: OMV_ERR_ARG before any launch; n == 0:
  * OMV_OK. */
 #define OMV_MATH_SINCOSF 0
@@ -1223,6 +1229,9 @@ omv_status omv_selftest_inv16(int batch, const double *D, double *Dinv, int32_t 
 #define OMV_MATH_ROT_BIN 16
 #define OMV_MATH_THREE_MAXIMA 17
 #define OMV_MATH_PREDICT_SCALE_CLAMPED 18
+#define OMV_MATH_GRID_CELL_OF 19
+#define OMV_MATH_GRID_WINDOW 20
+#define OMV_MATH_KP_IN_WINDOW 21
 omv_status omv_selftest_math(int fn, int64_t n, const void *a, const void *b, const void *c, void *out, void *stream);
 
 /* One reduced-system solve on a handle after omv_lba_set_problem, at the current state: errors, build, assemble and

@@ -36,7 +36,8 @@
 
 namespace {
 
-constexpr int kGridCols = 64, kGridRows = 48, kCells = kGridCols * kGridRows;
+using omv::kGridCols, omv::kGridRows;
+constexpr int kCells = omv::kGridCells;
 constexpr int kTH_HIGH = 100;
 constexpr int kTop = 16;   // candidates kept per (point, camera): rescans only when >14 are claimed
 constexpr int kMaxCams = 8;
@@ -54,6 +55,33 @@ struct FrameArgs {
     const int32_t *cell_idx;     // [frame][cam][kp_cap]
 };
 
+// A GetFeaturesInArea window flattened over one wavefront.  A window column's cells are contiguous in the cell-sorted
+// keypoint index, so lane j holds column w.x0 + j's run (at most 64 columns), an inclusive scan of the run lengths
+// puts the columns in the reference's iteration order, and the lanes walk window positions 0 .. total - 1 64 at a time:
+// one gather chain per 64 candidates.  Built and queried by the whole wavefront (uniform arguments but `lane` / `pos`).
+struct WaveWindow {
+    int start, len, excl;   // this lane's column: index position of its run, its length, window positions before it
+    int ncol, total;        // uniform
+    __device__ __forceinline__ WaveWindow(const int32_t *cs, const omv::GridRange &w, int lane) {
+        ncol = w.x1 - w.x0 + 1;
+        start = len = 0;
+        if (lane < ncol) {
+            const int ix = w.x0 + lane;
+            start = cs[ix * kGridRows + w.y0];
+            len = cs[ix * kGridRows + w.y1 + 1] - start;
+        }
+        const int incl = omv::wave_incl_scan_i32(len, lane);
+        excl = incl - len, total = __shfl(incl, 63, 64);
+    }
+    // the index position (into cell_idx) of window position pos, -1 past the window; every lane calls it
+    __device__ __forceinline__ int locate(int pos) const {
+        int j = 0;   // the last column that starts at or before pos (an empty column shares its successor's start)
+        for (int t = 1; t < ncol; ++t) j = __shfl(excl, t, 64) <= pos ? t : j;
+        const int p = __shfl(start, j, 64) + pos - __shfl(excl, j, 64);
+        return pos >= total ? -1 : p;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------
 // One 256-thread workgroup per (frame, camera): per-cell counts by LDS atomics, a block scan of the 3,072
 // counts, an unordered scatter by per-cell cursors, then each cell's (short) run sorted by keypoint index —
@@ -68,12 +96,7 @@ __global__ void __launch_bounds__(256) grid_kernel(FrameArgs f, int32_t *cell_st
     const omv_kp *kp = f.kps + (size_t)fc * f.kp_cap;
     for (int c = tid; c < kCells; c += 256) cnt[c] = 0;
     __syncthreads();
-    auto cell_of = [&](int i) {
-        const int px = (int)roundf((kp[i].x - f.min_x) * f.invW);
-        const int py = (int)roundf((kp[i].y - f.min_y) * f.invH);
-        if (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) return -1;
-        return px * kGridRows + py;   // mGrid[ix][iy]
-    };
+    auto cell_of = [&](int i) { return omv::grid_cell_of(kp[i].x, kp[i].y, f.min_x, f.min_y, f.invW, f.invH); };
     for (int i = tid; i < n; i += 256) {
         const int c = cell_of(i);
         if (c >= 0) atomicAdd(&cnt[c], 1);
@@ -84,11 +107,7 @@ __global__ void __launch_bounds__(256) grid_kernel(FrameArgs f, int32_t *cell_st
     int v[per], s = 0;
 #pragma unroll
     for (int k = 0; k < per; ++k) v[k] = cnt[tid * per + k], s += v[k];
-    int incl = s;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
+    const int incl = omv::wave_incl_scan_i32(s, lane);
     if (lane == 63) wsum[wv] = incl;
     __syncthreads();
     int run = incl - s;
@@ -139,14 +158,15 @@ struct Rec {
 };
 // SearchByProjection(F, MPs) records carry their own validity: bit 31 marks a filled entry (entries 0 .. n-1, n =
 // min(count, kTop)), bit 30 of entry 0 that the window held more than kTop unblocked candidates (no count array).
+// The keyframe searches' records (kMarked = false) are the bare entries, 0 past the list; their counts are an array.
 constexpr uint32_t kRecValid = 1u << 31, kRecOver = 1u << 30;
-template <class TopT>
+template <bool kMarked = true, class TopT>
 __device__ __forceinline__ void store_record(Rec *dst, const TopT &t) {
     uint4 *o4 = reinterpret_cast<uint4 *>(dst);   // 64-B record as four 16-B stores
     uint32_t w[kTop];
 #pragma unroll
-    for (int q = 0; q < kTop; ++q) w[q] = q < t.n ? t.rec(q) | kRecValid : 0u;
-    w[0] |= t.count > kTop ? kRecOver : 0u;
+    for (int q = 0; q < kTop; ++q) w[q] = q < t.n ? t.rec(q) | (kMarked ? kRecValid : 0u) : 0u;
+    if (kMarked) w[0] |= t.count > kTop ? kRecOver : 0u;
 #pragma unroll
     for (int v = 0; v < kTop / 4; ++v) o4[v] = make_uint4(w[4 * v], w[4 * v + 1], w[4 * v + 2], w[4 * v + 3]);
 }
@@ -232,22 +252,16 @@ template <class Blocked, class TopT>
 __device__ void scan_window(const FrameArgs &f, int frame, int cam, float x, float y, float r, int minL, int maxL,
                             const uint64_t dmp[4], Blocked blocked, TopT &t) {
     t.reset();
-    const int nMinCellX = max(0, (int)floorf((x - f.min_x - r) * f.invW));
-    if (nMinCellX >= kGridCols) return;
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - f.min_x + r) * f.invW));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = max(0, (int)floorf((y - f.min_y - r) * f.invH));
-    if (nMinCellY >= kGridRows) return;
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - f.min_y + r) * f.invH));
-    if (nMaxCellY < 0) return;
+    omv::GridRange w;
+    OMV_GRID_WINDOW_OR(x, y, r, f.min_x, f.min_y, f.invW, f.invH, w, return)
     const bool checkLevels = (minL > 0) || (maxL >= 0);
     const size_t fc = (size_t)frame * f.n_cams + cam;
     const int32_t *cs = f.cell_start + fc * (kCells + 1);
     const int32_t *ci = f.cell_idx + fc * f.kp_cap;
     const omv_kp *kp = f.kps + fc * f.kp_cap;
     const uint8_t *dd = f.desc + fc * f.kp_cap * 32;
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int c0 = ix * kGridRows + nMinCellY, c1 = ix * kGridRows + nMaxCellY;
+    for (int ix = w.x0; ix <= w.x1; ++ix) {
+        const int c0 = ix * kGridRows + w.y0, c1 = ix * kGridRows + w.y1;
         const int e = cs[c1 + 1];
         // cells iy = min..max of column ix are contiguous.  Latency-bound gathers, so one step's loads go
         // out together: the keypoint and its descriptor (speculatively) with the next index
@@ -259,6 +273,7 @@ __device__ void scan_window(const FrameArgs &f, int frame, int cam, float x, flo
             const omv_kp k = kp[i];
             uint64_t d[4];
             omv::load_desc(dd + (size_t)i * 32, d);
+            // omv::kp_in_window written out: through the call kf_resolve_kernel's registers move (VGPRs 39 -> 41)
             if (checkLevels) {
                 if (k.octave < minL) continue;
                 if (maxL >= 0 && k.octave > maxL) continue;
@@ -280,33 +295,22 @@ template <int G, class Blocked, class TopT>
 __device__ void scan_window_coop(const FrameArgs &f, int frame, int cam, float x, float y, float r, int minL, int maxL,
                                  const uint64_t dmp[4], Blocked blocked, TopT &t, int g) {
     t.reset();
-    const int nMinCellX = max(0, (int)floorf((x - f.min_x - r) * f.invW));
-    if (nMinCellX >= kGridCols) return;
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - f.min_x + r) * f.invW));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = max(0, (int)floorf((y - f.min_y - r) * f.invH));
-    if (nMinCellY >= kGridRows) return;
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - f.min_y + r) * f.invH));
-    if (nMaxCellY < 0) return;
-    const bool checkLevels = (minL > 0) || (maxL >= 0);
+    omv::GridRange w;
+    OMV_GRID_WINDOW_OR(x, y, r, f.min_x, f.min_y, f.invW, f.invH, w, return)
     const size_t fc = (size_t)frame * f.n_cams + cam;
     const int32_t *cs = f.cell_start + fc * (kCells + 1);
     const int32_t *ci = f.cell_idx + fc * f.kp_cap;
     const omv_kp *kp = f.kps + fc * f.kp_cap;
     const uint8_t *dd = f.desc + fc * f.kp_cap * 32;
     int pos = g, acc = 0;   // this lane's next window position; window positions before the current column
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int b = cs[ix * kGridRows + nMinCellY], e = cs[ix * kGridRows + nMaxCellY + 1];
+    for (int ix = w.x0; ix <= w.x1; ++ix) {
+        const int b = cs[ix * kGridRows + w.y0], e = cs[ix * kGridRows + w.y1 + 1];
         for (; pos < acc + (e - b); pos += G) {
             const int i = ci[b + pos - acc];
             const omv_kp k = kp[i];
             uint64_t d[4];
             omv::load_desc(dd + (size_t)i * 32, d);
-            if (checkLevels) {
-                if (k.octave < minL) continue;
-                if (maxL >= 0 && k.octave > maxL) continue;
-            }
-            if (!(fabsf(k.x - x) < r && fabsf(k.y - y) < r)) continue;
+            if (!omv::kp_in_window(k.x, k.y, k.octave, x, y, r, minL, maxL)) continue;
             if (blocked(cam * f.kp_cap + i)) continue;
             ++t.count;
             t.insert_at(i, omv::hamming256(dmp, d), k.octave, pos);
@@ -315,25 +319,30 @@ __device__ void scan_window_coop(const FrameArgs &f, int frame, int cam, float x
     }
 }
 
-// The group's kTop smallest keys (unique: window positions differ) into every lane's t, counts summed.
+// The smallest head of a G-lane group's sorted key lists (~0: every list is empty); the lane that holds it pops it
+// (keys are unique: window positions differ).
+template <int G, int N>
+__device__ __forceinline__ uint64_t pop_group_min(uint64_t (&key)[N]) {
+    const uint64_t h = key[0];
+    uint64_t mn = h;
+#pragma unroll
+    for (int s = 1; s < G; s <<= 1) {
+        const uint64_t o = __shfl_xor(mn, s, 64);
+        mn = o < mn ? o : mn;
+    }
+    const bool own = h == mn && h != ~0ull;
+#pragma unroll
+    for (int q = 0; q < N - 1; ++q) key[q] = own ? key[q + 1] : key[q];
+    key[N - 1] = own ? ~0ull : key[N - 1];
+    return mn;
+}
+
+// The group's kTop smallest keys into every lane's t, counts summed.
 template <int G>
 __device__ __forceinline__ void merge_top(Top &t) {
     uint64_t out[kTop];
 #pragma unroll
-    for (int r = 0; r < kTop; ++r) {
-        const uint64_t h = t.key[0];
-        uint64_t mn = h;
-#pragma unroll
-        for (int s = 1; s < G; s <<= 1) {
-            const uint64_t o = __shfl_xor(mn, s, 64);
-            mn = o < mn ? o : mn;
-        }
-        out[r] = mn;
-        const bool own = h == mn && h != ~0ull;
-#pragma unroll
-        for (int q = 0; q < kTop - 1; ++q) t.key[q] = own ? t.key[q + 1] : t.key[q];
-        t.key[kTop - 1] = own ? ~0ull : t.key[kTop - 1];
-    }
+    for (int r = 0; r < kTop; ++r) out[r] = pop_group_min<G>(t.key);
     int cnt = t.count;
 #pragma unroll
     for (int s = 1; s < G; s <<= 1) cnt += __shfl_xor(cnt, s, 64);
@@ -474,20 +483,14 @@ __device__ __forceinline__ void scan_window_lds(const FrameArgs &f, float x, flo
                                                 const uint64_t dmp[4], const int *scs, const float2 *sxy,
                                                 const uint32_t *smeta, const uint4 *sdesc, TopSeq &t) {
     t.reset();
-    const int nMinCellX = max(0, (int)floorf((x - f.min_x - r) * f.invW));
-    if (nMinCellX >= kGridCols) return;
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - f.min_x + r) * f.invW));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = max(0, (int)floorf((y - f.min_y - r) * f.invH));
-    if (nMinCellY >= kGridRows) return;
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - f.min_y + r) * f.invH));
-    if (nMaxCellY < 0) return;
+    omv::GridRange w;
+    OMV_GRID_WINDOW_OR(x, y, r, f.min_x, f.min_y, f.invW, f.invH, w, return)
     const bool checkLevels = (minL > 0) || (maxL >= 0);
     // a column's run in groups of kScanGroup entries: the group's position / meta reads go out together (one LDS
     // round trip per group instead of per entry; reads past the run stay inside the staged arrays and are masked)
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int e = scs[ix * kGridRows + nMaxCellY + 1];
-        for (int p0 = scs[ix * kGridRows + nMinCellY]; p0 < e; p0 += kScanGroup) {
+    for (int ix = w.x0; ix <= w.x1; ++ix) {
+        const int e = scs[ix * kGridRows + w.y1 + 1];
+        for (int p0 = scs[ix * kGridRows + w.y0]; p0 < e; p0 += kScanGroup) {
             float2 k[kScanGroup];
             uint32_t meta[kScanGroup];
 #pragma unroll
@@ -495,7 +498,7 @@ __device__ __forceinline__ void scan_window_lds(const FrameArgs &f, float x, flo
 #pragma unroll
             for (int u = 0; u < kScanGroup; ++u) {
                 const int oct = (int)((meta[u] >> 16) & 0x7f);
-                bool ok = p0 + u < e;
+                bool ok = p0 + u < e;   // then omv::kp_in_window written out: the call moves the kernel's VGPRs (88 -> 80)
                 if (checkLevels) ok = ok && oct >= minL && !(maxL >= 0 && oct > maxL);
                 ok = ok && fabsf(k[u].x - x) < r && fabsf(k[u].y - y) < r && !(meta[u] & kStageBlocked);
                 if (!ok) continue;
@@ -607,12 +610,8 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
     }
     __syncthreads();   // staging and bucket counts complete
     if (tid < 64) {    // exclusive scan of the 32 bucket counts
-        const int c = tid < kStageBuckets ? bucket[tid] : 0;
-        int incl = c;
-        for (int d = 1; d < 32; d <<= 1) {
-            const int t = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += t;
-        }
+        const int c = tid < kStageBuckets ? bucket[tid] : 0;   // lanes past the buckets add 0 behind them
+        const int incl = omv::wave_incl_scan_i32(c, lane);
         if (tid < kStageBuckets) bucket[tid] = incl - c;
         if (tid == kStageBuckets - 1) bucket[kStageBuckets] = incl;
     }
@@ -677,7 +676,8 @@ struct ResolveArgs {
 
 __device__ __forceinline__ bool bit_of(const uint32_t *bits, int s) { return (bits[s >> 5] >> (s & 31)) & 1u; }
 
-// Does keypoint slot `slot` (camera c) fall in the GetFeaturesInArea window of (x, y, r, lvl)?
+// Does keypoint slot `slot` (camera c) fall in the GetFeaturesInArea window of (x, y, r, lvl)?  omv::grid_cell_of,
+// omv::grid_window and omv::kp_in_window written out: through them resolve_kernel's SGPR spills move (181 -> 187).
 __device__ bool in_window(const FrameArgs &f, int frame, int c, int slot, float x, float y, float r, int lvl) {
     const omv_kp k = f.kps[((size_t)frame * f.n_cams) * f.kp_cap + slot];
     const int px = (int)roundf((k.x - f.min_x) * f.invW), py = (int)roundf((k.y - f.min_y) * f.invH);
@@ -773,12 +773,13 @@ __device__ __forceinline__ uint2 rescan_window_wave(const ResolveArgs &a, int fr
     const int minL = lvl - 1, maxL = lvl;
     Top2 t;
     t.reset();
+    // omv::grid_window and WaveWindow written out (the older three-shuffle lookup): either one moves resolve_kernel's
+    // VGPR or SGPR-spill figures
     const int nMinCellX = max(0, (int)floorf((x - f.min_x - r) * f.invW));
     const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - f.min_x + r) * f.invW));
     const int nMinCellY = max(0, (int)floorf((y - f.min_y - r) * f.invH));
     const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - f.min_y + r) * f.invH));
     if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0) {
-        const bool checkLevels = (minL > 0) || (maxL >= 0);
         const size_t fc = (size_t)frame * f.n_cams + c;
         const int32_t *cs = f.cell_start + fc * (kCells + 1);
         const int32_t *ci = f.cell_idx + fc * f.kp_cap;
@@ -793,12 +794,7 @@ __device__ __forceinline__ uint2 rescan_window_wave(const ResolveArgs &a, int fr
             cb = cs[ix * kGridRows + nMinCellY];
             len = cs[ix * kGridRows + nMaxCellY + 1] - cb;
         }
-        int incl = len;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int u = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += u;
-        }
+        const int incl = omv::wave_incl_scan_i32(len, lane);
         const int off = incl - len, total = __shfl(incl, 63, 64);
         for (int p0 = 0; p0 < total; p0 += 64) {
             const int pos = p0 + lane;
@@ -812,11 +808,7 @@ __device__ __forceinline__ uint2 rescan_window_wave(const ResolveArgs &a, int fr
             const omv_kp k = kp[i];
             uint64_t d[4];
             omv::load_desc(dd + (size_t)i * 32, d);
-            if (checkLevels) {
-                if (k.octave < minL) continue;
-                if (maxL >= 0 && k.octave > maxL) continue;
-            }
-            if (!(fabsf(k.x - x) < r && fabsf(k.y - y) < r)) continue;
+            if (!omv::kp_in_window(k.x, k.y, k.octave, x, y, r, minL, maxL)) continue;
             const int slot = c * f.kp_cap + i;
             if (slot == pa0 ? obs : bit_of(bits, slot)) continue;
             t.insert_at(i, omv::hamming256(dmp, d), k.octave, pos);
@@ -824,19 +816,7 @@ __device__ __forceinline__ uint2 rescan_window_wave(const ResolveArgs &a, int fr
     }
     uint64_t mn[2];
 #pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-        const uint64_t h = t.key[0];
-        uint64_t v = h;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const uint64_t o = __shfl_xor(v, s, 64);
-            v = o < v ? o : v;
-        }
-        mn[rr] = v;
-        const bool own = h == v && h != ~0ull;   // keys are unique (window positions)
-        t.key[0] = own ? t.key[1] : t.key[0];
-        t.key[1] = own ? ~0ull : t.key[1];
-    }
+    for (int rr = 0; rr < 2; ++rr) mn[rr] = pop_group_min<64>(t.key);
     // packed as record entries, 0: none (bit 31 marks an entry)
     return make_uint2(mn[0] != ~0ull ? key_rec(mn[0]) | 0x80000000u : 0u, mn[1] != ~0ull ? key_rec(mn[1]) | 0x80000000u : 0u);
 }
@@ -1765,12 +1745,7 @@ __global__ void __launch_bounds__(64) lf_resolve_kernel(LfResolveArgs a) {
             const int j0 = cm ? min(nb, __ffsll((long long)cm) - 1) : nb;
             const bool committed = lane >= start && lane < j0;
             // pushes of committed lanes in lane order
-            int np = committed ? nclaim : 0, incl = np;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int t = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += t;
-            }
+            const int np = committed ? nclaim : 0, incl = omv::wave_incl_scan_i32(np, lane);
             const int ptot = __shfl(incl, 63, 64);
             if (committed) {
                 for (int q = 0; q < nclaim; ++q) {
@@ -1963,11 +1938,7 @@ __global__ void __launch_bounds__(256) kf_cand_kernel(KfArgs a) {
         if (bi >= 0 && (float)bd <= a.max_dist) atomicAdd(a.n_matches + j, 1);
         return;
     }
-    uint4 *o4 = reinterpret_cast<uint4 *>(&a.recs[e]);
-#pragma unroll
-    for (int q = 0; q < kTop / 4; ++q)
-        o4[q] = make_uint4(4 * q < t.n ? t.rec(4 * q) : 0u, 4 * q + 1 < t.n ? t.rec(4 * q + 1) : 0u,
-                           4 * q + 2 < t.n ? t.rec(4 * q + 2) : 0u, 4 * q + 3 < t.n ? t.rec(4 * q + 3) : 0u);
+    store_record<false>(&a.recs[e], t);
     a.counts[e] = t.count;
     a.geo[e] = g;
 }
@@ -2196,40 +2167,16 @@ __device__ __forceinline__ void init_window_scan(const FrameArgs &f, const int32
     int ii[K];
 #pragma unroll
     for (int t = 0; t < K; ++t) ok[t] = kk[t] = kNoKey, oi[t] = ii[t] = -1;
-    const int nMinCellX = max(0, (int)floorf((x - f.min_x - r) * f.invW));
-    if (nMinCellX >= kGridCols) return;
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - f.min_x + r) * f.invW));
-    if (nMaxCellX < 0) return;
-    const int nMinCellY = max(0, (int)floorf((y - f.min_y - r) * f.invH));
-    if (nMinCellY >= kGridRows) return;
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - f.min_y + r) * f.invH));
-    if (nMaxCellY < 0) return;
-    // the window's columns are contiguous CSR runs; lane j < ncol holds column j's run, an inclusive scan
-    // flattens them in GetFeaturesInArea order, and the lanes walk the flattened list 64 at a time (one
-    // gather chain per 64 candidates instead of one per column)
-    const int ncol = nMaxCellX - nMinCellX + 1;
-    int cp0 = 0, clen = 0;
-    if (lane < ncol) {
-        const int ix = nMinCellX + lane;
-        cp0 = cs[ix * kGridRows + nMinCellY];
-        clen = cs[ix * kGridRows + nMaxCellY + 1] - cp0;
-    }
-    int incl = clen;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    const int excl = incl - clen, total = __shfl(incl, 63, 64);
-    for (int base = 0; base < total; base += 64) {
-        const int pos = base + lane;   // the shuffles run on the whole wavefront (uniform loop)
-        int j = 0;
-        for (int t = 1; t < ncol; ++t) j = __shfl(excl, t, 64) <= pos ? t : j;
-        const int p = __shfl(cp0, j, 64) + pos - __shfl(excl, j, 64);
-        if (pos >= total) continue;
+    omv::GridRange w;
+    OMV_GRID_WINDOW_OR(x, y, r, f.min_x, f.min_y, f.invW, f.invH, w, return)
+    const WaveWindow win(cs, w, lane);
+    for (int base = 0; base < win.total; base += 64) {
+        const int pos = base + lane, p = win.locate(pos);   // the shuffles run on the whole wavefront (uniform loop)
+        if (pos >= win.total) continue;   // p < 0, in the form that keeps init_spec_kernel's registers
         const int i2 = ci[p];
         const omv_kp k = kp2[i2];
-        if (k.octave != 0) continue;   // levels [0, 0]
+        // omv::kp_in_window at levels [0, 0] written out: the call moves init_kernel's VGPRs (44 -> 40)
+        if (k.octave != 0) continue;
         if (!(fabsf(k.x - x) < r && fabsf(k.y - y) < r)) continue;
         uint64_t d2[4];
         omv::load_desc(ds2 + (size_t)i2 * 32, d2);
@@ -2837,8 +2784,8 @@ omv_status omv_matcher_search_for_initialization(omv_matcher *h, int n_pairs, co
                                                  const omv_frame_geom *g, const omv_kp *kps, const uint8_t *desc,
                                                  const int *n_kp, float *prev_matched, int window, float nnratio,
                                                  int check_ori, int32_t *matches12, int32_t *n_matches, void *stream) {
-    if (!h || n_pairs < 0 || (n_pairs > 0 && (!pairs || !g || !kps || !desc || !n_kp || !prev_matched || !matches12 ||
-                                              !n_matches)) ||
+    if (!h || !g || n_pairs < 0 ||
+        (n_pairs > 0 && (!pairs || !kps || !desc || !n_kp || !prev_matched || !matches12 || !n_matches)) ||
         g->n_cams != h->n_cams || window < 0)
         return OMV_ERR_ARG;
     if (n_pairs == 0) return OMV_OK;

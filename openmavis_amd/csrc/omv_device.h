@@ -49,6 +49,17 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
     return v;
 }
 
+// Inclusive prefix sum over the 64 lanes of a wavefront (every lane active; `lane` is the caller's lane index): lane l
+// gets v[0] + .. + v[l].
+__device__ __forceinline__ int wave_incl_scan_i32(int v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(v, d, 64);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
 // 1 / x by v_rcp_f64 and two Newton steps (within an ulp of the IEEE quotient on normal numbers; a zero / non-finite
 // argument is the caller's to flag)
 __device__ __forceinline__ double rcp_nr(double x) {

@@ -1,6 +1,7 @@
 // The pure float arithmetic under every bit-exact claim: rounding, cv::fastAtan2, the glibc sincosf / atanf / atan2f /
 // tanf restatements, the correctly rounded sqrtf, the reference's float camera models, the matchers' rotation check
-// (rot_bin, three_maxima) and MapPoint::PredictScale.  Nothing in the bodies is
+// (rot_bin, three_maxima), MapPoint::PredictScale, and the keypoint grid with Frame::GetFeaturesInArea's window
+// (grid_cell_of, grid_window, kp_in_window).  Nothing in the bodies is
 // HIP-specific, so one text is compiled twice: by hipcc into every kernel (through omv_device.h / omv_camera.h), and by
 // the host compiler into the oracle library (oracle/math_host.cpp), where it is compared bit for bit with glibc
 // itself (tests/test_math_header_cpu.py) and with its own device build (omv_selftest_math,
@@ -359,6 +360,59 @@ OMV_MATH_FN int predict_scale_raw(float ratio, float log_scale_factor) {
 OMV_MATH_FN int predict_scale(float ratio, float log_scale_factor, int n_levels) {
     const int s = predict_scale_raw(ratio, log_scale_factor);
     return s < 0 ? 0 : (s >= n_levels ? n_levels - 1 : s);
+}
+
+// ---- the keypoint grid of Frame (FRAME_GRID_COLS x FRAME_GRID_ROWS) and Frame::GetFeaturesInArea's window on it: one
+// definition for the grid build and for every window walk, tested directly on both compilers.  The grid floats
+// (mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv) go by value.
+constexpr int kGridCols = 64, kGridRows = 48, kGridCells = kGridCols * kGridRows;
+
+// Frame::PosInGrid (Frame.cc:969-978) as the cell index mGrid[posX][posY], posX * rows + posY; -1 outside the grid.
+OMV_MATH_FN int grid_cell_of(float x, float y, float min_x, float min_y, float invW, float invH) {
+    const int px = (int)roundf((x - min_x) * invW);
+    const int py = (int)roundf((y - min_y) * invH);
+    if (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) return -1;
+    return px * kGridRows + py;
+}
+
+// The cells a GetFeaturesInArea(x, y, r) window visits (Frame.cc:890-930) into the GridRange w, both ends inclusive;
+// MISS (a statement: return, break) runs when the window misses the grid, at the reference's four early returns in
+// their order (the later fields of w are then unset).  A macro because the kernels pass fields of a kernel argument:
+// its operands are read where the reference reads them, after the earlier returns, while a call would read all four
+// grid floats first -- which renumbers the registers of every kernel that walks a window.  grid_window() below is the
+// same text as a function, and the one the tests call.
+#define OMV_GRID_WINDOW_OR(x, y, r, min_x, min_y, invW, invH, w, MISS)           \
+    {                                                                            \
+        const int x0_ = (int)floorf(((x) - (min_x) - (r)) * (invW));             \
+        (w).x0 = x0_ < 0 ? 0 : x0_;                                              \
+        if ((w).x0 >= omv::kGridCols) MISS;                                      \
+        const int x1_ = (int)ceilf(((x) - (min_x) + (r)) * (invW));              \
+        (w).x1 = x1_ > omv::kGridCols - 1 ? omv::kGridCols - 1 : x1_;            \
+        if ((w).x1 < 0) MISS;                                                    \
+        const int y0_ = (int)floorf(((y) - (min_y) - (r)) * (invH));             \
+        (w).y0 = y0_ < 0 ? 0 : y0_;                                              \
+        if ((w).y0 >= omv::kGridRows) MISS;                                      \
+        const int y1_ = (int)ceilf(((y) - (min_y) + (r)) * (invH));              \
+        (w).y1 = y1_ > omv::kGridRows - 1 ? omv::kGridRows - 1 : y1_;            \
+        if ((w).y1 < 0) MISS;                                                    \
+    }
+struct GridRange {
+    int x0, x1, y0, y1;
+};
+OMV_MATH_FN bool grid_window(float x, float y, float r, float min_x, float min_y, float invW, float invH,
+                             GridRange &g) {
+    OMV_GRID_WINDOW_OR(x, y, r, min_x, min_y, invW, invH, g, return false)
+    return true;
+}
+
+// GetFeaturesInArea's test of one keypoint of a visited cell (Frame.cc:932-963): the octave against [minL, maxL] when
+// bCheckLevels = (minLevel > 0) || (maxLevel >= 0), then the strict box |kx - x| < r && |ky - y| < r.
+OMV_MATH_FN bool kp_in_window(float kx, float ky, int octave, float x, float y, float r, int minL, int maxL) {
+    if ((minL > 0) || (maxL >= 0)) {
+        if (octave < minL) return false;
+        if (maxL >= 0 && octave > maxL) return false;
+    }
+    return fabsf(kx - x) < r && fabsf(ky - y) < r;
 }
 
 }  // namespace omv

@@ -10,7 +10,8 @@
 namespace omv {
 
 // element sizes (bytes per element of a / b / c / out; 0: not read).  b of the camera codes is one k[8], b of
-// PREDICT_SCALE one float and of PREDICT_SCALE_CLAMPED two, shared by every element.
+// PREDICT_SCALE one float, of PREDICT_SCALE_CLAMPED two and of the grid codes the four grid floats, shared by every
+// element.
 struct MathShape {
     int a, b, c, out;
     bool b_shared;
@@ -36,6 +37,9 @@ inline bool math_shape(int fn, MathShape *s) {
         case OMV_MATH_PREDICT_SCALE_CLAMPED: *s = {4, 8, 0, 4, true}; return true;
         case OMV_MATH_ROT_BIN: *s = {4, 4, 0, 4, false}; return true;
         case OMV_MATH_THREE_MAXIMA: *s = {4 * kRotHistLen, 0, 0, 12, false}; return true;
+        case OMV_MATH_GRID_CELL_OF: *s = {8, 16, 0, 4, true}; return true;
+        case OMV_MATH_GRID_WINDOW: *s = {12, 16, 0, 16, true}; return true;
+        case OMV_MATH_KP_IN_WINDOW: *s = {32, 0, 0, 4, false}; return true;
         default: return false;
     }
 }
@@ -71,6 +75,19 @@ OMV_MATH_FN void math_map_one(int fn, int64_t i, const void *a, const void *b, c
         case OMV_MATH_PREDICT_SCALE_CLAMPED: oi[i] = predict_scale(af[i], bf[0], (int)bf[1]); break;
         case OMV_MATH_ROT_BIN: oi[i] = rot_bin(af[i], bf[i]); break;
         case OMV_MATH_THREE_MAXIMA: three_maxima(ai + kRotHistLen * i, oi + 3 * i); break;
+        case OMV_MATH_GRID_CELL_OF: oi[i] = grid_cell_of(af[2 * i], af[2 * i + 1], bf[0], bf[1], bf[2], bf[3]); break;
+        case OMV_MATH_GRID_WINDOW: {
+            GridRange g;
+            const bool hit = grid_window(af[3 * i], af[3 * i + 1], af[3 * i + 2], bf[0], bf[1], bf[2], bf[3], g);
+            oi[4 * i] = hit ? g.x0 : -1, oi[4 * i + 1] = hit ? g.x1 : -1;
+            oi[4 * i + 2] = hit ? g.y0 : -1, oi[4 * i + 3] = hit ? g.y1 : -1;
+            break;
+        }
+        case OMV_MATH_KP_IN_WINDOW: {
+            const float *e = af + 8 * i;
+            oi[i] = kp_in_window(e[0], e[1], (int)e[2], e[3], e[4], e[5], (int)e[6], (int)e[7]);
+            break;
+        }
         default: break;
     }
 }

@@ -53,6 +53,9 @@ extern "C" omv_status omv_selftest_math(int fn, int64_t n, const void *a, const 
         OMV_MATH_CASE(OMV_MATH_PREDICT_SCALE_CLAMPED)
         OMV_MATH_CASE(OMV_MATH_ROT_BIN)
         OMV_MATH_CASE(OMV_MATH_THREE_MAXIMA)
+        OMV_MATH_CASE(OMV_MATH_GRID_CELL_OF)
+        OMV_MATH_CASE(OMV_MATH_GRID_WINDOW)
+        OMV_MATH_CASE(OMV_MATH_KP_IN_WINDOW)
 #undef OMV_MATH_CASE
         default: return OMV_ERR_ARG;
     }

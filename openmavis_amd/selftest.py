@@ -92,11 +92,13 @@ def inv16(D):
 
 # omv_selftest_math: the OMV_MATH_* codes of include/omv.h
 (SINCOSF, ATANF, ATAN2F, TANF, SQRTF, FAST_ATAN2_DEG, ROUND_EVEN, DIVF, MULADD_F32, MULADD_F64, RCP_NR, KB8_PROJECT,
- KB8_UNPROJECT, PINHOLE_PROJECT, PINHOLE_UNPROJECT, PREDICT_SCALE, ROT_BIN, THREE_MAXIMA, PREDICT_SCALE_CLAMPED) = range(19)
+ KB8_UNPROJECT, PINHOLE_PROJECT, PINHOLE_UNPROJECT, PREDICT_SCALE, ROT_BIN, THREE_MAXIMA, PREDICT_SCALE_CLAMPED,
+ GRID_CELL_OF, GRID_WINDOW, KP_IN_WINDOW) = range(22)
 ROT_HIST_LEN = 30   # omv::kRotHistLen
 MATH_NAMES = ("SINCOSF", "ATANF", "ATAN2F", "TANF", "SQRTF", "FAST_ATAN2_DEG", "ROUND_EVEN", "DIVF", "MULADD_F32",
               "MULADD_F64", "RCP_NR", "KB8_PROJECT", "KB8_UNPROJECT", "PINHOLE_PROJECT", "PINHOLE_UNPROJECT",
-              "PREDICT_SCALE", "ROT_BIN", "THREE_MAXIMA", "PREDICT_SCALE_CLAMPED")
+              "PREDICT_SCALE", "ROT_BIN", "THREE_MAXIMA", "PREDICT_SCALE_CLAMPED", "GRID_CELL_OF", "GRID_WINDOW",
+              "KP_IN_WINDOW")
 # per fn: input dtype, scalars per element of a, (dtype, scalars per element) of out
 MATH_IO = {SINCOSF: (np.float32, 1, np.float32, 2), ATANF: (np.float32, 1, np.float32, 1),
            ATAN2F: (np.float32, 1, np.float32, 1), TANF: (np.float32, 1, np.float32, 1),
@@ -107,15 +109,17 @@ MATH_IO = {SINCOSF: (np.float32, 1, np.float32, 2), ATANF: (np.float32, 1, np.fl
            KB8_UNPROJECT: (np.float32, 2, np.float32, 3), PINHOLE_PROJECT: (np.float32, 3, np.float32, 2),
            PINHOLE_UNPROJECT: (np.float32, 2, np.float32, 3), PREDICT_SCALE: (np.float32, 1, np.int32, 1),
            ROT_BIN: (np.float32, 1, np.int32, 1), THREE_MAXIMA: (np.int32, ROT_HIST_LEN, np.int32, 3),
-           PREDICT_SCALE_CLAMPED: (np.float32, 1, np.int32, 1)}
-# b shared by every element: fn -> its length (the camera codes: k[8])
+           PREDICT_SCALE_CLAMPED: (np.float32, 1, np.int32, 1), GRID_CELL_OF: (np.float32, 2, np.int32, 1),
+           GRID_WINDOW: (np.float32, 3, np.int32, 4), KP_IN_WINDOW: (np.float32, 8, np.int32, 1)}
+# b shared by every element: fn -> its length (the camera codes: k[8]; the grid codes: min_x, min_y, invW, invH)
 MATH_B_SHARED = {KB8_PROJECT: 8, KB8_UNPROJECT: 8, PINHOLE_PROJECT: 8, PINHOLE_UNPROJECT: 8, PREDICT_SCALE: 1,
-                 PREDICT_SCALE_CLAMPED: 2}
+                 PREDICT_SCALE_CLAMPED: 2, GRID_CELL_OF: 4, GRID_WINDOW: 4}
 
 
 def math_args(fn, a, b, c):
     """The arrays of one math() / oracle.math_map() call in the hook's layout: (n, a, b, c, an empty out).  b of the
-    camera codes is k[8], of PREDICT_SCALE one float, of PREDICT_SCALE_CLAMPED (log scale factor, levels); every other
+    camera codes is k[8], of PREDICT_SCALE one float, of PREDICT_SCALE_CLAMPED (log scale factor, levels), of the grid
+    codes (min_x, min_y, invW, invH); every other
     b / c has one scalar per element."""
     tin, wa, tout, wo = MATH_IO[fn]
     a = np.ascontiguousarray(a, tin)

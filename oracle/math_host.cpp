@@ -9,8 +9,9 @@
 //                   nothing: sinf / cosf / atanf / atan2f / tanf / sqrtf / nearbyintf, double cos / sin / log / ceil
 //                   inside the oracle's kb8_project_f (match_oracle.cpp), kb8_unproject_f (tri_oracle.cpp) and the
 //                   PredictScale expression, oracle_fast_atan2 (orb_oracle.cpp).  DIVF, the MULADD probes, RCP_NR,
-//                   ROT_BIN, THREE_MAXIMA and PREDICT_SCALE_CLAMPED have no libm counterpart (return 1): numpy, exact
-//                   arithmetic and the tests' literal restatements of the reference lines are their references.
+//                   ROT_BIN, THREE_MAXIMA, PREDICT_SCALE_CLAMPED and the three grid codes have no libm counterpart
+//                   (return 1): numpy, exact arithmetic and the tests' literal restatements of the reference lines
+//                   are their references.
 // The chain the tests assert: device build of the header == host build (GPU tests), host build == this glibc (CPU
 // tests), this glibc == recorded answers (tests/golden/libm_kat.npz).
 // =====================================================================================================
@@ -87,7 +88,7 @@ int oracle_math_map(int fn, int64_t n, const void *a, const void *b, const void 
 int oracle_libm_map(int fn, int64_t n, const void *a, const void *b, const void *c, void *out) {
     if (!args_ok(fn, n, a, b, c, out)) return 1;
     if (fn == OMV_MATH_DIVF || fn == OMV_MATH_MULADD_F32 || fn == OMV_MATH_MULADD_F64 || fn == OMV_MATH_RCP_NR ||
-        fn == OMV_MATH_ROT_BIN || fn == OMV_MATH_THREE_MAXIMA || fn == OMV_MATH_PREDICT_SCALE_CLAMPED)
+        fn == OMV_MATH_ROT_BIN || fn == OMV_MATH_THREE_MAXIMA || fn >= OMV_MATH_PREDICT_SCALE_CLAMPED)
         return 1;
     parallel_chunks(n, [=](int64_t lo, int64_t hi) {
         for (int64_t i = lo; i < hi; ++i) libm_one(fn, i, a, b, out);

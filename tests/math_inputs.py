@@ -409,10 +409,153 @@ def three_maxima_ref(hists):
     return out
 
 
+# ---- the keypoint grid and GetFeaturesInArea's window (omv::grid_cell_of / grid_window / kp_in_window) ----
+GRID_COLS, GRID_ROWS = 64, 48
+GRID_FRAMES = (("synthetic 720x540", 720, 540), ("pinhole 1920x1080", 1920, 1080))   # the suite's two frame geometries
+
+
+def grid_floats(width, height):
+    """(min_x, min_y, invW, invH) of a frame whose bounds are the image (Frame.cc:1878-1879, float)."""
+    return np.array([0, 0, F32(GRID_COLS) / F32(width), F32(GRID_ROWS) / F32(height)], F32)
+
+
+def _ulps(v):
+    """v and its two float neighbours."""
+    v = np.asarray(v, F32).ravel()
+    return np.concatenate([np.nextafter(v, F32(-np.inf)), v, np.nextafter(v, F32(np.inf))])
+
+
+@functools.lru_cache(None)
+def grid_windows(width, height):
+    """(x, y, r) [n][3] for one geometry: window edges x -+ r (y -+ r) exactly on cell boundaries and one ulp to either
+    side; windows off the grid on each side, just on and just off it; windows clipped by each clamp; r = 0; r larger
+    than the image; 300 random windows around the image."""
+    rng = np.random.default_rng(20240301 + width)
+    cw, ch = width / GRID_COLS, height / GRID_ROWS   # 11.25 x 11.25 and 30 x 22.5: exact floats
+    rows = []
+    for r in (0.0, 4.0, 7.5, cw, 2.5 * 1.2 ** 3):
+        for c in (0, 1, 7, 31, 62, 63, 64):      # column boundaries under the left and the right edge
+            for x in np.concatenate([_ulps(c * cw + r), _ulps(c * cw - r)]):
+                rows.append((x, 0.37 * height, r))
+        for c in (0, 1, 5, 23, 46, 47, 48):      # row boundaries under the top and the bottom edge
+            for y in np.concatenate([_ulps(c * ch + r), _ulps(c * ch - r)]):
+                rows.append((0.61 * width, y, r))
+    for r in (0.0, 3.0, 40.0):
+        # off the grid: x - r at / past the right bound, x + r a whole cell left of 0, the same for y; and just on it
+        for x in np.concatenate([_ulps(width + r), [width + r + 100], _ulps(-cw - r), [-cw - r - 100]]):
+            rows.append((x, 0.5 * height, r))
+        for y in np.concatenate([_ulps(height + r), [height + r + 100], _ulps(-ch - r), [-ch - r - 100]]):
+            rows.append((0.5 * width, y, r))
+        # x fine and y off, so that the third and the fourth return are reached after the first two pass
+        rows += [(3.0, height + r + 1, r), (width - 3.0, -ch - r - 1, r)]
+    for r in (15.0, 60.0):   # each clamp alone, then all four
+        rows += [(r / 2, 0.5 * height, r), (width - r / 2, 0.5 * height, r), (0.5 * width, r / 2, r),
+                 (0.5 * width, height - r / 2, r)]
+    for r in (0.0, 2.0 * width, 5000.0):
+        rows += [(0.0, 0.0, r), (0.5 * width, 0.5 * height, r), (float(width), float(height), r), (-r, -r, r)]
+    n = 300
+    rnd = np.stack([rng.uniform(-60, width + 60, n), rng.uniform(-60, height + 60, n),
+                    rng.choice([2.5, 4.0, 6.0, 10.0, 14.93, 50.0, 100.0], n)], 1)
+    return np.ascontiguousarray(np.concatenate([np.array(rows, np.float64), rnd]), F32)
+
+
+@functools.lru_cache(None)
+def grid_keypoints(width, height):
+    """(x, y) [n][2] for one geometry: the image border and one ulp outside / inside it; the cell centres' edges, where
+    roundf changes cell (half away from zero), +- one ulp; the last cell's far edge, where the keypoint leaves the
+    grid; 300 random keypoints; a few outside the image; four keypoints just inside the box of every window of
+    grid_windows()."""
+    rng = np.random.default_rng(20240302 + width)
+    cw, ch = width / GRID_COLS, height / GRID_ROWS
+    xs = np.concatenate([_ulps([0.0, width, -0.5 * cw, (GRID_COLS - 0.5) * cw]), _ulps((np.array([0, 1, 31, 62, 63]) + 0.5) * cw)])
+    ys = np.concatenate([_ulps([0.0, height, -0.5 * ch, (GRID_ROWS - 0.5) * ch]), _ulps((np.array([0, 1, 23, 46, 47]) + 0.5) * ch)])
+    rows = [(x, 0.37 * height) for x in xs] + [(0.61 * width, y) for y in ys]
+    rows += [(x, y) for x in _ulps([0.0, width]) for y in _ulps([0.0, height])]
+    rows += [(-30.0, 10.0), (width + 30.0, 10.0), (10.0, -30.0), (10.0, height + 30.0)]
+    rnd = np.stack([rng.uniform(0, width, 300), rng.uniform(0, height, 300)], 1)
+    # just inside the box of every window of the set, at its left / right and top / bottom edge: the keypoints a
+    # window admits that are nearest to the cells it might not visit
+    win = grid_windows(width, height)
+    win = win[win[:, 2] > 0]
+    x, y, r = win[:, 0], win[:, 1], win[:, 2]
+    edge = np.concatenate([np.stack([np.nextafter(x - r, F32(np.inf)), y], 1), np.stack([np.nextafter(x + r, F32(-np.inf)), y], 1),
+                           np.stack([x, np.nextafter(y - r, F32(np.inf))], 1), np.stack([x, np.nextafter(y + r, F32(-np.inf))], 1)])
+    return np.ascontiguousarray(np.concatenate([np.array(rows, np.float64), rnd, edge]), F32)
+
+
+@functools.lru_cache(None)
+def kp_window_cases(width, height):
+    """[n][8] (kx, ky, octave, x, y, r, minL, maxL) for one geometry: 400 random keypoints near random windows with
+    every level rule -- minL 0 and above, maxL -1 (with minL 0: bCheckLevels false), equal to and above the octave,
+    below it -- and keypoints at |kx - x| == r and |ky - y| == r exactly and one ulp to either side (the test is
+    strict)."""
+    rng = np.random.default_rng(20240303 + width)
+    rows = []
+    levels = lambda o: [(0, -1), (1, -1), (o + 1, -1), (0, o), (o, o), (o - 1, o), (0, o + 2), (o + 1, o + 2), (0, o - 1), (-1, -1)]
+    for _ in range(40):
+        x, y, r = rng.uniform(0, width), rng.uniform(0, height), float(rng.choice([2.5, 4.0, 14.93, 50.0]))
+        kx, ky, o = x + rng.uniform(-1.2, 1.2) * r, y + rng.uniform(-1.2, 1.2) * r, int(rng.integers(0, 8))
+        rows += [(kx, ky, o, x, y, r, lo, hi) for lo, hi in levels(o)]
+    for r in (0.0, 2.5, 4.0, 7.5):   # x, y, r chosen so that x + r and x - r are exact: the keypoint sits on the box
+        x, y = F32(0.25 * width + 0.5), F32(0.75 * height + 0.25)
+        for kx in np.concatenate([_ulps(x + F32(r)), _ulps(x - F32(r))]):
+            rows += [(kx, y, 2, x, y, r, 1, 2), (kx, y, 2, x, y, r, 0, -1)]
+        for ky in np.concatenate([_ulps(y + F32(r)), _ulps(y - F32(r))]):
+            rows += [(x, ky, 2, x, y, r, 1, 2), (x, ky, 2, x, y, r, 0, -1)]
+    return np.ascontiguousarray(np.array(rows, np.float64), F32)
+
+
+def grid_cell_of_ref(kp, g):
+    """Frame::PosInGrid (Frame.cc:969-978) in float32, one IEEE operation per step; round() is half away from zero."""
+    v = [(kp[:, 0] - g[0]) * g[2], (kp[:, 1] - g[1]) * g[3]]
+    assert v[0].dtype == F32
+    px, py = (np.copysign(np.floor(np.abs(u).astype(np.float64) + 0.5), u).astype(np.int64) for u in v)
+    out = (px < 0) | (px >= GRID_COLS) | (py < 0) | (py >= GRID_ROWS)
+    return np.where(out, -1, px * GRID_ROWS + py).astype(np.int32)
+
+
+def grid_window_ref(win, g):
+    """Frame.cc:890-930 in float32: ([n][4] min / max column, min / max row, four -1 for a window that misses the grid;
+    [n] which of the four early returns was taken, 0 none; [n][4] whether each clamp changed its value)."""
+    x, y, r = win[:, 0], win[:, 1], win[:, 2]
+    raw = [np.floor((x - g[0] - r) * g[2]), np.ceil((x - g[0] + r) * g[2]), np.floor((y - g[1] - r) * g[3]),
+           np.ceil((y - g[1] + r) * g[3])]
+    assert all(v.dtype == F32 for v in raw)
+    raw = [v.astype(np.int64) for v in raw]
+    cl = [np.maximum(0, raw[0]), np.minimum(GRID_COLS - 1, raw[1]), np.maximum(0, raw[2]), np.minimum(GRID_ROWS - 1, raw[3])]
+    miss = [cl[0] >= GRID_COLS, cl[1] < 0, cl[2] >= GRID_ROWS, cl[3] < 0]
+    ret = np.zeros(len(win), np.int32)
+    for k in (3, 2, 1, 0):
+        ret = np.where(miss[k], k + 1, ret)
+    rng4 = np.where((ret > 0)[:, None], -1, np.stack(cl, 1)).astype(np.int32)
+    return rng4, ret, np.stack([c != v for c, v in zip(cl, raw)], 1)
+
+
+def kp_in_window_ref(e):
+    """Frame.cc:932-963 for one keypoint of a visited cell, in float32."""
+    kx, ky, o, x, y, r, lo, hi = (e[:, k] for k in range(8))
+    check = (lo > 0) | (hi >= 0)
+    lvl_ok = ~check | ((o >= lo) & ((hi < 0) | (o <= hi)))
+    return (lvl_ok & (np.abs(kx - x) < r) & (np.abs(ky - y) < r)).astype(np.int32)
+
+
+def grid_cell_of():
+    return [(name, grid_keypoints(w, h), grid_floats(w, h), None) for name, w, h in GRID_FRAMES]
+
+
+def grid_window():
+    return [(name, grid_windows(w, h), grid_floats(w, h), None) for name, w, h in GRID_FRAMES]
+
+
+def kp_in_window():
+    return [(name, kp_window_cases(w, h), None, None) for name, w, h in GRID_FRAMES]
+
+
 # fn -> the calls of its input set, for the functions with plain [n] arguments
 SETS = {st.SINCOSF: trig, st.TANF: trig, st.ATANF: atanf, st.ATAN2F: atan2, st.FAST_ATAN2_DEG: fast_atan2,
         st.SQRTF: sqrtf, st.DIVF: divf, st.ROUND_EVEN: round_even, st.RCP_NR: rcp_nr, st.PREDICT_SCALE: predict_scale,
-        st.ROT_BIN: rot_bin, st.THREE_MAXIMA: three_maxima}
+        st.ROT_BIN: rot_bin, st.THREE_MAXIMA: three_maxima, st.GRID_CELL_OF: grid_cell_of, st.GRID_WINDOW: grid_window,
+        st.KP_IN_WINDOW: kp_in_window}
 
 
 def camera_sets(fn):

@@ -108,6 +108,16 @@ def test_destroy_of_null(lib):
         assert getattr(lib, destroy)(None) == want, name
 
 
+def test_search_for_initialization_requires_the_geometry(lib):
+    """A null frame geometry is OMV_ERR_ARG before it is read, with no pairs too (as in every other entry point)."""
+    h = ctypes.c_void_p()
+    assert HANDLES["matcher"][0](lib, ctypes.byref(h)) == _lib.OMV_OK
+    for n_pairs in (0, 1):
+        assert lib.omv_matcher_search_for_initialization(h, n_pairs, None, None, None, None, None, None, 10, 0.9, 1,
+                                                         None, None, None) == _lib.OMV_ERR_ARG
+    assert lib.omv_matcher_destroy(h) == _lib.OMV_OK
+
+
 # ---- omv_lba_set_problem -------------------------------------------------------------------------------------------
 def _lba(prob):
     return LocalInertialBA(max_kf=prob["n_kf"], max_cams=prob["n_cams"], max_pts=len(prob["pts"]),

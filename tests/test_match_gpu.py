@@ -155,6 +155,73 @@ def test_search_by_projection_small_batch_lanes(frames, oracle, torch_cuda, case
     _sbp_case(frames, oracle, torch_cuda, *case, M=4000)
 
 
+def _needs_full_rescan(kps, desc, n_kp, mp, th, far, th_far, occ, final, scale, cams=(0,)):
+    """How many (point, camera) visits of one frame find the 16 best candidates of their window all taken: the visits
+    for which resolve_kernel can only answer by rescanning the whole window (rescan_window_wave), since a record holds
+    16 candidates.  From the oracle's final assignment `final` [C * cap] alone, which is exact when every point has
+    observations: a keypoint taken by such a point is never taken again, so it was held at point i's visit iff its
+    final holder j < i (the reference visits the points in index order).  Windows, cell order and the keypoint test are
+    tests/math_inputs.py's numpy restatements of Frame.cc:890-967; candidates are ordered by (Hamming distance, window
+    order) and initially occupied keypoints are no candidates, as in the records.  Only a point's first camera is
+    counted (a later one is not visited when the ratio test of an earlier one fails), and only cameras `cams`."""
+    import math_inputs as mi
+    assert mp["has_obs"].all()
+    Cn, cap = kps.shape
+    g = mi.grid_floats(W, H)
+    M = len(mp["desc"])
+    lvl, iv = mp["level"], mp["in_view"].astype(bool)
+    skipped = ~iv.any(1) | (mp["is_bad"] != 0) | (far & (mp["track_depth"] > th_far))
+    active = iv & (lvl >= 0) & (lvl < 8)
+    first = np.where(iv.any(1), iv.argmax(1), -1)
+    need = 0
+    for c in cams:
+        n = n_kp[c]
+        k = kps[c, :n]
+        xy = np.stack([k["x"], k["y"]], 1).astype(np.float32)
+        cell = mi.grid_cell_of_ref(xy, g)
+        rank = np.empty(n, np.int64)
+        rank[np.lexsort((np.arange(n), cell))] = np.arange(n)   # GetFeaturesInArea order: column, row, index
+        bits = np.unpackbits(desc[c, :n], axis=1)
+        holder = final[c * cap:c * cap + n]
+        for i in np.flatnonzero(active[:, c] & ~skipped & (first == c)):
+            r = np.float32(2.5 if mp["view_cos"][i, c] > 0.998 else 4.0)
+            if c == 0 and th != 1.0:
+                r = r * np.float32(th)
+            r = r * np.float32(scale[lvl[i, c]])
+            win = np.array([[mp["proj_x"][i, c], mp["proj_y"][i, c], r]], np.float32)
+            (x0, x1, y0, y1), = mi.grid_window_ref(win, g)[0]
+            if x0 < 0:
+                continue
+            e = np.empty((n, 8), np.float32)
+            e[:, 0], e[:, 1], e[:, 2] = xy[:, 0], xy[:, 1], k["octave"]
+            e[:, 3:] = (win[0, 0], win[0, 1], r, lvl[i, c] - 1, lvl[i, c])
+            px, py = cell // mi.GRID_ROWS, cell % mi.GRID_ROWS
+            cand = np.flatnonzero((cell >= 0) & (px >= x0) & (px <= x1) & (py >= y0) & (py <= y1) &
+                                  (mi.kp_in_window_ref(e) == 1) & (occ[c * cap:c * cap + n] == 0))
+            if len(cand) <= 16:
+                continue
+            dist = (bits[cand] != np.unpackbits(mp["desc"][i])[None]).sum(1)
+            top = cand[np.lexsort((rank[cand], dist))[:16]]
+            need += bool(((holder[top] >= 0) & (holder[top] < i)).all())
+    return need
+
+
+def test_search_by_projection_reaches_the_full_rescan(frames, oracle, torch_cuda):
+    """The parameter sets of test_search_by_projection_matches_oracle in which every point has observations (th = 1 and
+    th = 15, where _needs_full_rescan is exact) have no visit that needs resolve_kernel's full window rescan, evaluated
+    with the oracle.  This one has: th = 60 makes a camera-0 window most of the
+    image, nnratio = 1 lets every best candidate be taken, every point has observations and 2 % of the keypoints start
+    occupied.  With the oracle, 1, 1 and 2 visits of the three frames find their 16 recorded candidates all held
+    while the window holds more.  The assignments equal the oracle's, as in every other case."""
+    th, far = 60.0, False
+    per, occ, exp, (kps, desc, n_kp) = _sbp_case(frames, oracle, torch_cuda, th, far, 1.0, 0.02, 1.0, False)
+    scale = [frames.geom.scale_factors[i] for i in range(8)]
+    need = [_needs_full_rescan(kps[f], desc[f], n_kp[f], per[f], th, far, 20.0, occ[f], exp[f], scale)
+            for f in range(frames.n_frames)]
+    print("visits that need the full rescan, per frame:", need)
+    assert sum(need) >= 1, need
+
+
 def _sbp_case(frames, oracle, torch_cuda, th, far, nnratio, occ_frac, obs, rand_stereo, M=5000):
     torch = torch_cuda
     per, mpb = _mps_for(frames, oracle, M, 7 + int(th), torch)
@@ -190,6 +257,7 @@ def _sbp_case(frames, oracle, torch_cuda, th, far, nnratio, occ_frac, obs, rand_
     kps, desc, n_kp, _ = host(frames, oracle)
     l2r, r2l = frames.l2r.cpu().numpy(), frames.r2l.cpu().numpy()
     g = oracle.frame_geom(C, W, H, [frames.geom.scale_factors[i] for i in range(8)])
+    exps = []
     for f in range(frames.n_frames):
         exp = init[f].copy()
         n = oracle.search_by_projection(g, kps[f], desc[f], n_kp[f], per[f], th, far, 20.0, nnratio, l2r[f], r2l[f],
@@ -198,9 +266,11 @@ def _sbp_case(frames, oracle, torch_cuda, th, far, nnratio, occ_frac, obs, rand_
         bad = np.nonzero(exp != got[f])[0]
         assert bad.size == 0, f"frame {f}: {bad.size} assignments differ, first slots {bad[:8]}"
         assert n > 300
+        exps.append(exp)
     assert m.last_error() == 0
     frames.occ_init = None
     frames.kp_to_mp.fill_(-1)
+    return per, occ, exps, (kps, desc, n_kp)
 
 
 def test_knn2_matches_oracle_with_ties(oracle, torch_cuda):

@@ -16,7 +16,8 @@ from openmavis_amd import _lib, selftest as st
 pytestmark = pytest.mark.gpu
 
 IEEE_ONLY = [st.SINCOSF, st.ATANF, st.ATAN2F, st.TANF, st.SQRTF, st.FAST_ATAN2_DEG, st.ROUND_EVEN, st.DIVF,
-             st.KB8_UNPROJECT, st.PINHOLE_PROJECT, st.PINHOLE_UNPROJECT, st.ROT_BIN, st.THREE_MAXIMA]
+             st.KB8_UNPROJECT, st.PINHOLE_PROJECT, st.PINHOLE_UNPROJECT, st.ROT_BIN, st.THREE_MAXIMA, st.GRID_CELL_OF,
+             st.GRID_WINDOW, st.KP_IN_WINDOW]
 CAMERA = [st.KB8_PROJECT, st.KB8_UNPROJECT, st.PINHOLE_PROJECT, st.PINHOLE_UNPROJECT]
 
 
@@ -39,7 +40,9 @@ def test_device_equals_host_build(torch_cuda, oracle, fn):
     orb_extract.hip's angles are in [0, 2 pi), imu.hip's arguments dt * theta, tri.hip's go through cosf_glibc).
     DIVF, SQRTF and ROUND_EVEN are also held to numpy's IEEE float32 divide, sqrt and rint.  ROT_BIN and THREE_MAXIMA
     are the matchers' rotation check (omv::rot_bin on all pairs of ~750 angles, omv::three_maxima on ~2,000
-    histograms); tests/test_math_header_cpu.py holds their host build to the reference's lines."""
+    histograms); GRID_CELL_OF, GRID_WINDOW and KP_IN_WINDOW are the keypoint grid and GetFeaturesInArea's window on
+    the suite's two frame geometries (a few thousand elements); tests/test_math_header_cpu.py holds their host build
+    to the reference's lines."""
     total = 0
     for name, a, b, c in _calls(fn):
         got, want = st.math(fn, a, b, c), oracle.math_map(fn, a, b, c)

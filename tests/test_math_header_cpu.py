@@ -189,6 +189,85 @@ def test_three_maxima_against_the_reference_loop(oracle):
     assert dropped2.sum() >= 30 and dropped3.sum() >= 30 and (got[:, 2] >= 0).sum() >= 30
 
 
+def test_grid_input_sets_cover_the_window_branches():
+    """The grid sets reach, on both frame geometries: each of GetFeaturesInArea's four early returns; each of the four
+    clamps on a window that hits the grid; window edges exactly on a cell boundary (and both float neighbours, by
+    construction); r = 0 and r larger than the image; keypoints on the image border, one ulp outside it, and outside
+    the grid on each side; for the keypoint test bCheckLevels false and true, maxL -1, equal to and above the octave,
+    and |kx - x| == r, |ky - y| == r exactly."""
+    for (name, win, g, _), (_, kp, _, _), (_, e, _, _), (_, w, h) in zip(mi.grid_window(), mi.grid_cell_of(),
+                                                                       mi.kp_in_window(), mi.GRID_FRAMES):
+        assert 500 <= len(win) <= 3000 and 300 <= len(kp) <= 5000 and 400 <= len(e) <= 3000, name
+        rng4, ret, clamped = mi.grid_window_ref(win, g)
+        for k in (1, 2, 3, 4):
+            assert (ret == k).sum() >= 3, (name, k)
+        hit = ret == 0
+        for k in range(4):
+            assert (hit & clamped[:, k]).sum() >= 3, (name, k)
+            assert (hit & ~clamped[:, k]).sum() >= 3, (name, k)
+        x, y, r = win[:, 0], win[:, 1], win[:, 2]
+        for v in ((x - r) * g[2], (x + r) * g[2], (y - r) * g[3], (y + r) * g[3]):
+            assert (hit & (v == np.rint(v)) & (r > 0)).sum() >= 5, name   # an edge exactly on a cell boundary
+        assert (r == 0).sum() >= 10 and (r > max(w, h)).sum() >= 4, name
+        cell = mi.grid_cell_of_ref(kp, g)
+        kx, ky = kp[:, 0], kp[:, 1]
+        for on, v, lim in ((kx, kx, w), (ky, ky, h)):
+            assert (v == 0).any() and (v == lim).any() and (v == np.nextafter(np.float32(0), np.float32(-1))).any()
+            assert (v == np.nextafter(np.float32(lim), np.float32(np.inf))).any(), name
+        assert ((cell < 0) & (kx < 0)).any() and ((cell < 0) & (kx > 0) & (ky > 0) & (ky < h)).any(), name
+        assert ((cell < 0) & (ky < 0)).any() and ((cell < 0) & (ky > 0) & (kx > 0) & (kx < w)).any(), name
+        assert set(np.unique(cell // mi.GRID_ROWS)) >= {-1, 0, 63} and set(np.unique(cell[cell >= 0] % mi.GRID_ROWS)) >= {0, 47}
+        o, lo, hi = e[:, 2], e[:, 6], e[:, 7]
+        check = (lo > 0) | (hi >= 0)
+        assert (~check).sum() >= 40 and ((lo > 0) & (hi < 0)).sum() >= 40 and ((lo == 0) & (hi >= 0)).sum() >= 40, name
+        assert (check & (hi == o)).sum() >= 40 and (check & (hi > o)).sum() >= 40 and (check & (hi >= 0) & (hi < o)).sum() >= 20
+        assert (check & (o < lo)).sum() >= 40, name
+        edge = e[:, 5] > 0
+        assert (edge & (np.abs(e[:, 0] - e[:, 3]) == e[:, 5])).sum() >= 6, name
+        assert (edge & (np.abs(e[:, 1] - e[:, 4]) == e[:, 5])).sum() >= 6, name
+        want = mi.kp_in_window_ref(e)
+        assert (want == 1).sum() >= 50 and (want == 0).sum() >= 50, name
+
+
+def test_grid_functions_against_the_reference_lines(oracle):
+    """omv::grid_cell_of, grid_window and kp_in_window (host build) against Frame.cc:969-978, :890-930 and :932-963
+    restated in numpy float32, exactly (integers), on both frame geometries."""
+    for name, kp, g, _ in mi.grid_cell_of():
+        got, want = oracle.math_map(st.GRID_CELL_OF, kp, g), mi.grid_cell_of_ref(kp, g)
+        bad = mi.mismatches(got, want)
+        assert len(bad) == 0, (name, len(bad), kp[bad[:3]], got[bad[:3]], want[bad[:3]])
+    for name, win, g, _ in mi.grid_window():
+        got, want = oracle.math_map(st.GRID_WINDOW, win, g), mi.grid_window_ref(win, g)[0]
+        bad = mi.mismatches(got, want)
+        assert len(bad) == 0, (name, len(bad), win[bad[:3]], got[bad[:3]], want[bad[:3]])
+    for name, e, _, _ in mi.kp_in_window():
+        got, want = oracle.math_map(st.KP_IN_WINDOW, e), mi.kp_in_window_ref(e)
+        bad = mi.mismatches(got, want)
+        assert len(bad) == 0, (name, len(bad), e[bad[:3]], got[bad[:3]], want[bad[:3]])
+
+
+def test_a_keypoint_in_the_box_lies_in_a_visited_cell(oracle):
+    """The agreement between the grid build and the window walk: for every keypoint and every window of the sets
+    (~3,100 x ~800 pairs per geometry), a keypoint that lies in the grid and passes the box test |kx - x| < r &&
+    |ky - y| < r is binned (grid_cell_of) into a cell that the window (grid_window) visits.  Otherwise
+    GetFeaturesInArea would never see a keypoint its own test admits.  Both functions are the host build.
+
+    Measured: no pair of either geometry fails, so no input is recorded here as the reference's own miss."""
+    for (name, win, g, _), (_, kp, _, _) in zip(mi.grid_window(), mi.grid_cell_of()):
+        cell = oracle.math_map(st.GRID_CELL_OF, kp, g)
+        rng4 = oracle.math_map(st.GRID_WINDOW, win, g)
+        assert np.array_equal(cell, mi.grid_cell_of_ref(kp, g)) and np.array_equal(rng4, mi.grid_window_ref(win, g)[0])
+        px, py = (cell // mi.GRID_ROWS)[:, None], (cell % mi.GRID_ROWS)[:, None]
+        box = (np.abs(kp[:, 0][:, None] - win[:, 0][None]) < win[:, 2][None]) & \
+              (np.abs(kp[:, 1][:, None] - win[:, 1][None]) < win[:, 2][None]) & (cell >= 0)[:, None]
+        x0, x1, y0, y1 = (rng4[:, k][None] for k in range(4))
+        visited = (px >= x0) & (px <= x1) & (py >= y0) & (py <= y1) & (x0 >= 0)
+        bad = np.argwhere(box & ~visited)
+        print(f"{name}: {int(box.sum())} of {box.size} pairs in the box")
+        assert box.sum() >= len(win), name   # every window with r > 0 admits the edge keypoints made for it
+        assert len(bad) == 0, (name, len(bad), [(kp[i], win[j], cell[i], rng4[j]) for i, j in bad[:3]])
+
+
 def test_predict_scale_clamp(oracle):
     """omv::predict_scale is predict_scale_raw (the PREDICT_SCALE code, held to libm and to 50 digits above) clamped to
     [0, n_levels - 1]: on the PredictScale set and on ratios around both ends of the clamp, raw levels below 0 and at
