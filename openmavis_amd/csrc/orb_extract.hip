@@ -450,27 +450,32 @@ __global__ void __launch_bounds__(256) pyr_chain_kernel(Geom g, const uint8_t *i
 // cornerScore<16>(t) then returns S - 1 (the threshold floor max(t, .) never binds for a corner).
 typedef short pk16 __attribute__((ext_vector_type(2)));   // packed int16 pair (v_pk_* ops)
 
-// The strength on packed f16 pairs (k, k+8): 1024 + n is the f16 bit pattern 0x6400 | n (n < 1024), so the
-// differences d = v - ring are exact, and every min / max of integers in [-255, 255] is exact.  gfx950's
+// The strength on packed f16 pairs (k, k+8): the byte n, zero-extended to 16 bits, is the f16 denormal n * 2^-24, so
+// the differences d = v - ring are exact denormals k * 2^-24 with |k| <= 255, and every min / max of them is exact.
+// This relies on the kernel's default f16 denormal mode (float_denorm_mode_16_64 = 3: denormals kept, which is what
+// hipcc sets unless told to flush them); with flushing every d would be 0.  gfx950's
 // v_pk_minimum3_f16 / v_pk_maximum3_f16 take three operands: the 9-arc is min3 of three 3-runs.
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ h2 h2_swap(h2 x) { return h2{x.y, x.x}; }
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ h2 h2_biased(const uint8_t *lo, const uint8_t *hi) {   // (1024 + *lo, 1024 + *hi)
+__device__ __forceinline__ h2 h2_bytes(const uint8_t *lo, const uint8_t *hi) {   // (*lo, *hi) * 2^-24
     const u16x2 v{(unsigned short)*lo, (unsigned short)*hi};   // ds_read_u8_d16 / _d16_hi
-    return __builtin_bit_cast(h2, __builtin_bit_cast(uint32_t, v) | 0x64006400u);
+    return __builtin_bit_cast(h2, v);
 }
 
-template <int RS>
-__device__ __forceinline__ int fast_strength_h(const uint8_t *p, int stride_rt) {
+// p7 is the top-left pixel of the centre's 7x7 neighbourhood, so that every ring offset is >= 0 and fits the LDS
+// instructions' unsigned offset field (from the centre, half of them are negative and cost an address add each).
+template <int RS>   // returns max(S, 0)
+__device__ __forceinline__ int fast_strength_h(const uint8_t *p7, int stride_rt) {
     const int stride = RS > 0 ? RS : stride_rt;
-    const int o[16] = {3 * stride, 3 * stride + 1, 2 * stride + 2, stride + 3, 3, -stride + 3, -2 * stride + 2,
-                       -3 * stride + 1, -3 * stride, -3 * stride - 1, -2 * stride - 2, -stride - 3, -3, stride - 3,
-                       2 * stride - 2, 3 * stride - 1};
-    const h2 vv = h2_biased(p, p);
+    const int c = 3 * stride + 3;
+    const int o[16] = {c + 3 * stride, c + 3 * stride + 1, c + 2 * stride + 2, c + stride + 3, c + 3, c - stride + 3,
+                       c - 2 * stride + 2, c - 3 * stride + 1, c - 3 * stride, c - 3 * stride - 1, c - 2 * stride - 2,
+                       c - stride - 3, c - 3, c + stride - 3, c + 2 * stride - 2, c + 3 * stride - 1};
+    const h2 vv = h2_bytes(p7 + c, p7 + c);
     h2 d[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) d[k] = vv - h2_biased(p + o[k], p + o[k + 8]);
+    for (int k = 0; k < 8; ++k) d[k] = vv - h2_bytes(p7 + o[k], p7 + o[k + 8]);
     auto Q = [&](const h2 *a, int k) { return k < 8 ? a[k] : h2_swap(a[k - 8]); };
     h2 t3n[8], t3x[8];
 #pragma unroll
@@ -486,8 +491,12 @@ __device__ __forceinline__ int fast_strength_h(const uint8_t *p, int stride_rt) 
         a = __builtin_elementwise_maximum(a, m9);
         b = __builtin_elementwise_minimum(b, M9);
     }
-    const int A = (int)__builtin_elementwise_maximum(a.x, a.y), B = (int)__builtin_elementwise_minimum(b.x, b.y);
-    return max(A, -B);
+    // k * 2^-24 has the bit pattern k (k >= 0) or 0x8000 | -k (k < 0; -0 never arises from x - y): as int16 the
+    // pattern of a positive value is the value and that of a negative one is negative, so max(A, -B, 0) is the signed
+    // maximum of a's patterns, b's with the sign flipped, and 0
+    const pk16 m = __builtin_elementwise_max(__builtin_bit_cast(pk16, a),
+                                             __builtin_bit_cast(pk16, __builtin_bit_cast(uint32_t, b) ^ 0x80008000u));
+    return max(max((int)m.x, (int)m.y), 0);
 }
 
 // Inclusive wave64 prefix sum by DPP (row_shr 1/2/4/8 inside each 16-lane row, then row_bcast 15 / 31);
@@ -509,8 +518,9 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int v) {
 //      brighter (d < -t) or darker (d > t) together -- exact, not a heuristic; survivors are compacted
 //      in row-major order (ballot prefix) into an LDS list;
 //   2. the full FAST strength for the survivors only (the strength map S stays 0 elsewhere, which is
-//      what the NMS of any threshold >= t sees for non-corners);
-//   3. NMS (3x3, strict >) at iniTh and minTh in one pass over the survivors;
+//      what the NMS of any threshold >= t sees for non-corners); the corners among them (S > t) are
+//      compacted, in the same order, over the front of the list;
+//   3. NMS (3x3, strict >) over the corners;
 //   4. emission at iniTh, or minTh if the cell had no iniTh keypoint (ORBextractor.cc:764-782).
 #ifdef OMV_FAST_PROFILE
 __device__ unsigned long long g_fast_stats[8];
@@ -576,7 +586,11 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
         r = 3 + rr, q = 3 + i - omv::mul_u24(rr, dw);   // 24-bit multiplies: full rate
     };
     const uint64_t lt = (1ull << lane) - 1ull;
-    // compass prefilter at threshold t: the row-major candidate list cand[0..n) (returns n)
+#ifdef OMV_FAST_PROFILE
+    int ncand_last = 0;   // candidates of the last prefilter pass
+#endif
+    // compass prefilter at threshold t: the row-major candidate list cand[0..ncand), entries (r << 7) | q (cells are
+    // < 128 px), their strengths into S, then the corners among them as cand[0..n) (returns n)
     auto prefilter = [&](int t) {
         int ncand = 0;
         if (dwords && ndet > 0) {
@@ -637,17 +651,17 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
                 const int cnt = __popc(bits);
                 const int incl = wave_incl_scan_dpp(cnt);
                 int pos = ncand + incl - cnt;
-                const int ibase = omv::mul_u24(r - 3, dw) + (4 * jq - o) - 3;
+                const int ebase = (r << 7) + (4 * jq - o);   // entry of column q0
                 // row-major: lanes hold consecutive pairs, bit k = column q0 + k (a few set bits per lane)
-                for (uint32_t b = bits; b; b &= b - 1u) cand[pos++] = (uint16_t)(ibase + __builtin_ctz(b));
+                for (uint32_t b = bits; b; b &= b - 1u) cand[pos++] = (uint16_t)(ebase + __builtin_ctz(b));
                 ncand += __builtin_amdgcn_readlane(incl, 63);
             }
         } else {
             for (int i0 = 0; i0 < ndet; i0 += 64) {
                 const int i = i0 + lane;
                 bool pass = false;
+                int r = 0, q = 0;
                 if (i < ndet) {
-                    int r, q;
                     rowcol(i, r, q);
                     const uint8_t *p = pix + r * rs + q;
                     const int v = p[0];
@@ -658,35 +672,53 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
                            (b8 && b12) || (b12 && b0);
                 }
                 const uint64_t m = __ballot(pass);
-                if (pass) cand[ncand + __popcll(m & lt)] = (uint16_t)i;
+                if (pass) cand[ncand + __popcll(m & lt)] = (uint16_t)((r << 7) | q);
                 ncand += __popcll(m);
             }
         }
         __syncthreads();
-        // FAST strength of the candidates (threshold-free; non-candidates keep S = 0)
-        for (int k = lane; k < ncand; k += 64) {
-            const int i = cand[k];
-            int r, q;
-            rowcol(i, r, q);
-            const int sv = fast_strength_h<RS>(pix + r * rs + q, rs);
-            S[omv::mul_u24(r - 2, sw) + (q - 2)] = (uint8_t)min(max(sv, 0), 255);
+        // FAST strength of the candidates (threshold-free; non-candidates keep S = 0).  The corners (S > t) are
+        // compacted by the ballot prefix, in candidate order, over the front of cand[] itself: a round reads
+        // cand[k0 + lane] before it writes positions <= k0 + lane, from the same wave in program order, and later
+        // rounds read indices >= k0 + 64.  No LDS is added.  A candidate that is no corner can never be kept by the
+        // NMS at t; only its stored S is read, as a neighbour.
+#ifdef OMV_FAST_PROFILE
+        ncand_last = ncand;
+#endif
+        // pixel (r - 3, q - 3) is pix7[r * rs + q]; the readfirstlane keeps the compiler from folding the constant
+        // back into the ring offsets (r, q >= 3: the address itself is never below pix)
+        const uint8_t *pix7 = smem + __builtin_amdgcn_readfirstlane(o - (3 * rs + 3));
+        int ncorn = 0;
+        for (int k0 = 0; k0 < ncand; k0 += 64) {
+            const int k = k0 + lane;
+            bool corner = false;
+            int e = 0;
+            if (k < ncand) {
+                e = cand[k];
+                const int r = e >> 7, q = e & 127;
+                const int sv = fast_strength_h<RS>(pix7 + r * rs + q, rs);
+                S[omv::mul_u24(r - 2, sw) + (q - 2)] = (uint8_t)sv;   // 0 <= sv <= 255
+                corner = sv > t;
+            }
+            const uint64_t m = __ballot(corner);
+            if (corner) cand[ncorn + __popcll(m & lt)] = (uint16_t)e;
+            ncorn += __popcll(m);
         }
         __syncthreads();
-        return ncand;
+        return ncorn;
     };
-    // NMS at threshold th over the candidates: keypoint k survives iff S > th and S - 1 > every neighbour's
+    // NMS at threshold th over the corners of prefilter(th): corner k survives iff S - 1 > every neighbour's
     // cornerScore (S - 1 if S > th, else 0) -- i.e. S > max(th, 1, every neighbour's S).  Returns the count;
     // with `out`, emits row-major.
-    auto nms = [&](int ncand, int th, uint32_t *out) {
+    auto nms = [&](int ncorn, int th, uint32_t *out) {
         int base = 0;
-        for (int k0 = 0; k0 < ncand; k0 += 64) {
+        for (int k0 = 0; k0 < ncorn; k0 += 64) {
             const int k = k0 + lane;
             bool keep = false;
             uint32_t packed = 0;
-            if (k < ncand) {
-                const int i = cand[k];
-                int r, q;
-                rowcol(i, r, q);
+            if (k < ncorn) {
+                const int e = cand[k];
+                const int r = e >> 7, q = e & 127;
                 const uint8_t *sp8 = S + omv::mul_u24(r - 2, sw) + (q - 2);
                 const int v = sp8[0];
                 // v > th and v - 1 > (nv > th ? nv - 1 : 0) for all 8 neighbours <=> v > max(nv..., th, 1)
@@ -712,15 +744,15 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
     // minBorder = 16); a cell without an iniTh keypoint wrote nothing and is redone at minTh
     uint32_t *out = cell_kp + (size_t)blk * g.cell_cap;
     int th = g.ini_th;
-    int ncand = prefilter(th);
+    int ncorn = prefilter(th);
 #ifdef OMV_FAST_PROFILE
-    const int ncand0 = ncand;
+    const int ncand0 = ncand_last;
 #endif
-    int total = nms(ncand, th, out);
+    int total = nms(ncorn, th, out);
     if (total == 0) {
         th = g.min_th;
-        ncand = prefilter(th);
-        total = nms(ncand, th, out);
+        ncorn = prefilter(th);
+        total = nms(ncorn, th, out);
     }
     // cap = max NMS survivors of the window, so this cannot trigger (writes past it were dropped)
     if (lane == 0) cell_cnt[blk] = total > g.cell_cap ? -1 : total;
@@ -735,14 +767,16 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
             atomicAdd(&g_fast_stats[1], (unsigned long long)ndet);
             atomicAdd(&g_fast_stats[2], (unsigned long long)ncand0);
             atomicAdd(&g_fast_stats[3], th == g.min_th && g.min_th != g.ini_th ? 1ull : 0ull);
-            atomicAdd(&g_fast_stats[4], (unsigned long long)ncand);
+            atomicAdd(&g_fast_stats[4], (unsigned long long)ncand_last);
             atomicAdd(&g_fast_stats[5], (unsigned long long)total);
+            atomicAdd(&g_fast_stats[6], (unsigned long long)ncorn);
             __threadfence();
             const unsigned long long done = atomicAdd(&g_fast_stats[7], 1ull) + 1;
             if (done == (unsigned long long)n_blocks)
-                printf("fast: cells %llu pixels %llu cand(iniTh) %llu retries %llu cand(last pass) %llu keypoints %llu\n",
+                printf("fast: cells %llu pixels %llu cand(iniTh) %llu retries %llu cand(last pass) %llu corners(last pass) "
+                       "%llu keypoints %llu\n",
                        g_fast_stats[0], g_fast_stats[1], g_fast_stats[2], g_fast_stats[3], g_fast_stats[4],
-                       g_fast_stats[5]);
+                       g_fast_stats[6], g_fast_stats[5]);
         }
     }
 #endif
@@ -1393,10 +1427,9 @@ __global__ void __launch_bounds__(256, 2) describe_kernel(Geom g, DescArgs a, in
         m10 -= __mul24(15, rs);
         m01 = __mul24(vr - 15, rs);
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        m01 += __shfl_xor(m01, d, 64);
-        m10 += __shfl_xor(m10, d, 64);
-    }
+    // the two wave sums as DPP row reductions (every lane is active: the exits above are wave-uniform)
+    m01 = __builtin_amdgcn_readlane(wave_incl_scan_dpp(m01), 63);
+    m10 = __builtin_amdgcn_readlane(wave_incl_scan_dpp(m10), 63);
     // optional Harris response (OpenCV ORB's HarrisResponses, blockSize 7, k 0.04 -- the north star's "Harris score";
     // the reference's response is FAST's): lane k < 49 = block pixel (cy - 3 + k / 7, cx - 3 + k % 7) of the raw patch
     float harris = 0.f;
