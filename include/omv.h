@@ -1054,6 +1054,72 @@ omv_status omv_sim3_solver_debug(omv_sim3_solver *h, int job, int32_t *n_hyp, in
                                  void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * MLPnPsolver (src/MLPnPsolver.cpp, include/MLPnPsolver.h): the PnP RANSAC of Tracking::Relocalization
+ * (src/Tracking.cc:3543-3730), between SearchByBoW and PoseOptimization.  One handle holds n_jobs independent solvers
+ * (one per candidate keyframe of a frame; many frames may share a handle); the phases are the reference's: constructor
+ * + SetRansacParameters (omv_pnp_set), iterate (omv_pnp_iterate).
+ * Arithmetic: computePose in double as the reference's, CheckInliers in its mixed double / float.  Not bit-exact: the
+ * JacobiSVDs are cyclic Jacobi eigen-decompositions, sums run in correspondence order per matrix entry, mlpnpJacs is the
+ * same derivative through the chain rule, the eigenvectors of the planarity matrix have a fixed sign.  Refine keeps
+ * computePose's result for its CheckInliers, and its outcome is kept with the carried state (a pure function of
+ * mvbBestInliers).
+ * ---------------------------------------------------------------------------------------------- */
+#define OMV_PNP_NO_MORE 1   /* flags bit 0: bNoMore                    */
+#define OMV_PNP_FOUND 2     /* flags bit 1: iterate's return value     */
+typedef struct omv_pnp omv_pnp;
+
+/* max_jobs solvers, max_corr_total correspondences over all of them, max_hyp hypotheses per omv_pnp_iterate. */
+omv_status omv_pnp_create(int max_jobs, int max_corr_total, int max_hyp, omv_pnp **out);
+omv_status omv_pnp_destroy(omv_pnp *h);
+
+/* The constructor's numeric part (:28-45) and SetRansacParameters(prob, min_inliers, max_its, min_set, epsilon, th2)
+ * (:177-218) for every job; resets the carried state (mnIterations = 0, mnBestInliers = 0).  Every pointer is HOST
+ * memory.  Job j owns the correspondences corr_start[j] .. corr_start[j+1]-1 (corr_start[0] = 0), in the order the
+ * constructor pushes them:
+ *   P2D    [n][2] F.mvKeysUn[i].pt        sigma2 [n] F.mvLevelSigma2[kp.octave]        Xw [n][3] pMP->GetWorldPos()
+ *   index  [n] mvKeyPointIndices (i in vpMapPointMatches), each < mN[j] = vpMapPointMatches.size()
+ *   cam    [n_jobs][8] fx fy cx cy k0..k3, model [n_jobs] OMV_CAM_KB8 / OMV_CAM_PINHOLE
+ * The header's defaults are (0.99, 8, 300, 6, 0.4, 5.991); Tracking passes (0.99, 10, 300, 6, 0.5, 5.991).
+ * ransac_max_its_out / ransac_min_inliers_out [n_jobs] (or NULL) receive mRansacMaxIts / mRansacMinInliers.  A job with
+ * fewer correspondences than mRansacMinInliers (iterate's entry test) does no work and reports bNoMore.
+ * OMV_ERR_ARG: min_set != 6, an unknown camera model, a negative size, an index outside [0, mN); OMV_ERR_CAPACITY: more
+ * jobs / correspondences than the handle's.  Synchronises `stream`. */
+omv_status omv_pnp_set(omv_pnp *h, int n_jobs, const int32_t *corr_start, const float *P2D, const float *sigma2,
+                       const float *Xw, const int32_t *index, const int32_t *mN, const float *cam, const int32_t *model,
+                       double prob, int min_inliers, int max_its, int min_set, float epsilon, float th2,
+                       int32_t *ransac_max_its_out, int32_t *ransac_min_inliers_out, void *stream);
+
+/* iterate(nIterations, bNoMore, vbInliers, nInliers, Tout) (:56-175) for every job, asynchronous on `stream`; every
+ * pointer is DEVICE memory.  The reference's loop condition is an OR (:75): a call runs
+ * max(n_iterations, mRansacMaxIts - mnIterations) hypotheses unless it returns earlier -- the whole RANSAC on the first
+ * call, n_iterations more on every later one.  draws [n_jobs][n_draws][6]: for hypothesis k of the call the six values
+ * DUtils::Random::RandomInt(0, size-1) returns, draw i in [0, N-1-i] (out-of-range values are clamped); a job runs at
+ * most n_draws hypotheses, so n_draws >= max(n_iterations, mRansacMaxIts) gives the reference's call.  Draws after a
+ * return are unused.
+ *   T_out [n_jobs][16] row-major: mRefinedTcw when Refine succeeded, mBestTcw at exhaustion, else identity
+ *   n_inliers_out [n_jobs]; inliers_out: vbInliers, job j's mN[j] bytes at sum(mN[0..j-1]);
+ *   flags_out [n_jobs]: OMV_PNP_NO_MORE | OMV_PNP_FOUND.  n_draws <= max_hyp (OMV_ERR_CAPACITY). */
+omv_status omv_pnp_iterate(omv_pnp *h, int n_iterations, int n_draws, const int32_t *draws, float *T_out,
+                           int32_t *n_inliers_out, uint8_t *inliers_out, int32_t *flags_out, void *stream);
+
+/* Test hook: what job `job` did in the last omv_pnp_iterate call, host outputs (any but n_hyp / n_refine may be NULL).
+ * n_hyp = H hypotheses up to the one the call returned at:
+ *   hyp_int  [H][10]  the six sampled correspondences, planar flag, Gauss-Newton iterations, exit reason (0 five
+ *                     iterations, 1 max|Jac dx| < 1e-5, 2 the 5.0 / 1.0 break, 3 no finite step), mnInliersi
+ *   hyp_pose [H][24]  doubles: the linear stage R0 [9], t0 [3], the final R [9], t [3]
+ *   mask_words [H][ceil(N / 64)] mvbInliersi (bit i of word i / 64)
+ * n_refine = K Refine calls, in order:
+ *   ref_int  [K][8]   the hypothesis that became best, its inlier count, planar, iterations, exit reason,
+ *                     mnRefinedInliers, success, 0
+ *   ref_pose [K][24], ref_mask_words [K][ceil(N / 64)] as above for the refined pose
+ * state_out [6]: mnIterations, mnBestInliers, a Refine outcome is kept, its count, its success, what the call returned
+ * (0 identity, 1 the refined outcome, 2 the best).  prepared [N][12]: per correspondence the bearing, its two nullspace
+ * vectors and Xw, in double.  Synchronous. */
+omv_status omv_pnp_debug(omv_pnp *h, int job, int32_t *n_hyp, int32_t *hyp_int, double *hyp_pose, uint64_t *mask_words,
+                         int32_t *n_refine, int32_t *ref_int, double *ref_pose, uint64_t *ref_mask_words,
+                         int32_t *state_out, double *prepared, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer::OptimizeSim3 (src/Optimizer.cc:2460-2726): the Sim3 refinement of LoopClosing's loop / merge candidates
  * (src/LoopClosing.cc:658, :899, :935), after Sim3Solver and between the SearchByProjection calls.  One call optimises
  * n_jobs independent candidate pairs, one wavefront each.  Double arithmetic as g2o's, except that the two projection

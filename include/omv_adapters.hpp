@@ -1419,6 +1419,98 @@ class Sim3Solver {
     DeviceArray<uint8_t> d_inl_;
 };
 
+// ---- MLPnPsolver -------------------------------------------------------------------------------------------
+// What MLPnPsolver(F, vpMapPointMatches) reads (src/MLPnPsolver.cpp:6-53), flattened by the caller: every entry i of
+// vpMapPointMatches with its flags, keypoint and world position; the constructor's test (pMP && !pMP->isBad() &&
+// i < F.mvKeysUn.size()) is applied here.
+struct MLPnPInput {
+    std::vector<uint8_t> has_mp, is_bad;   // [mN] vpMapPointMatches[i] != NULL, pMP->isBad()
+    std::vector<float> P2D;                // [mN][2] F.mvKeysUn[i].pt (entries past n_keys unused)
+    std::vector<float> sigma2;             // [mN] F.mvLevelSigma2[kp.octave]
+    std::vector<float> Xw;                 // [mN][3] pMP->GetWorldPos() (unused where there is no map point)
+    int n_keys = 0;                        // F.mvKeysUn.size()
+    float cam[8] = {};                     // fx fy cx cy k0..k3 of F.mpCamera
+    int model = OMV_CAM_KB8;
+};
+
+// One solver (one job of the batched handle) with the reference's call shape.  The draws of a call are made up front
+// with std::rand() in DUtils::Random::RandomInt's formula, six per hypothesis the call may run
+// (max(nIterations, mRansacMaxIts) of them: iterate's loop condition is an OR); the reference stops drawing when it
+// returns, so after a return the rand() stream is further along here.
+class MLPnPsolver {
+  public:
+    explicit MLPnPsolver(const MLPnPInput &in, int max_iterations = 300, hipStream_t stream = nullptr)
+        : mN_((int)in.has_mp.size()), st_(stream), max_hyp_(std::max(1, max_iterations)), model_(in.model) {
+        if (in.is_bad.size() != (size_t)mN_ || in.P2D.size() != (size_t)2 * mN_ || in.sigma2.size() != (size_t)mN_ ||
+            in.Xw.size() != (size_t)3 * mN_)
+            throw Error("MLPnPsolver: array lengths differ from has_mp's");
+        for (int k = 0; k < 8; k++) cam_[k] = in.cam[k];
+        for (int i = 0; i < mN_ && i < in.n_keys; i++) {   // :21-50
+            if (!in.has_mp[i] || in.is_bad[i]) continue;
+            P2D_.push_back(in.P2D[2 * i]), P2D_.push_back(in.P2D[2 * i + 1]);
+            sigma2_.push_back(in.sigma2[i]);
+            for (int k = 0; k < 3; k++) Xw_.push_back(in.Xw[3 * i + k]);
+            index_.push_back(i);
+        }
+        check(omv_pnp_create(1, (int)index_.size(), max_hyp_, &h_), "omv_pnp_create");
+        d_T_.resize(16), d_n_.resize(1), d_flags_.resize(1), d_inl_.resize(std::max(1, mN_));
+        SetRansacParameters();   // the constructor's last line (:52)
+    }
+    MLPnPsolver(const MLPnPsolver &) = delete;
+    MLPnPsolver &operator=(const MLPnPsolver &) = delete;
+    ~MLPnPsolver() {
+        if (h_) (void)omv_pnp_destroy(h_);
+    }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 6,
+                             float epsilon = 0.4f, float th2 = 5.991f) {
+        if (maxIterations > max_hyp_) throw Error("MLPnPsolver: maxIterations above the constructor's max_iterations");
+        const int32_t corr_start[2] = {0, (int32_t)index_.size()};
+        const int32_t mn = mN_, model = model_;
+        check(omv_pnp_set(h_, 1, corr_start, P2D_.data(), sigma2_.data(), Xw_.data(), index_.data(), &mn, cam_, &model,
+                          probability, minInliers, maxIterations, minSet, epsilon, th2, &max_its_, &min_inliers_, st_),
+              "omv_pnp_set");
+    }
+
+    // bool iterate(nIterations, bNoMore, vbInliers, nInliers, Tout): Tout [16] row-major
+    bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers,
+                 std::array<float, 16> &Tout) {
+        const int N = (int)index_.size();
+        const int n_draws = std::min(max_hyp_, std::max(nIterations, (int)max_its_));
+        std::vector<int32_t> draws((size_t)6 * std::max(n_draws, 1));
+        for (int k = 0; k < n_draws; k++)
+            for (int i = 0; i < 6; i++) draws[6 * k + i] = Sim3Solver::RandomInt(0, std::max(N - i, 1) - 1);
+        d_draws_.upload(draws.data(), draws.size(), st_);
+        check(omv_pnp_iterate(h_, nIterations, n_draws, d_draws_.p, d_T_.p, d_n_.p, d_inl_.p, d_flags_.p, st_),
+              "omv_pnp_iterate");
+        int32_t n = 0, flags = 0;
+        std::vector<uint8_t> inl(std::max(1, mN_));
+        d_T_.download(Tout.data(), 16, st_), d_n_.download(&n, 1, st_), d_flags_.download(&flags, 1, st_);
+        d_inl_.download(inl.data(), inl.size(), st_);
+        hip_check(hipStreamSynchronize(st_), "hipStreamSynchronize");
+        bNoMore = (flags & OMV_PNP_NO_MORE) != 0, nInliers = n;
+        vbInliers.assign(mN_, false);
+        for (int i = 0; i < mN_; i++) vbInliers[i] = inl[i] != 0;
+        return (flags & OMV_PNP_FOUND) != 0;
+    }
+    int ransac_max_its() const { return max_its_; }
+    int ransac_min_inliers() const { return min_inliers_; }
+    const std::vector<int32_t> &key_point_indices() const { return index_; }   // mvKeyPointIndices
+
+  private:
+    int mN_;
+    hipStream_t st_;
+    int max_hyp_, model_;
+    float cam_[8];
+    std::vector<float> P2D_, sigma2_, Xw_;
+    std::vector<int32_t> index_;
+    int32_t max_its_ = 1, min_inliers_ = 0;
+    omv_pnp *h_ = nullptr;
+    DeviceArray<int32_t> d_draws_, d_n_, d_flags_;
+    DeviceArray<float> d_T_;
+    DeviceArray<uint8_t> d_inl_;
+};
+
 // ---- Optimizer::OptimizeSim3 -------------------------------------------------------------------------------
 // g2o::Sim3 as the optimiser keeps it: quaternion (x y z w), translation, scale.
 struct Sim3 {

@@ -339,6 +339,11 @@ SIGNATURES = {
     "omv_sim3_solver_iterate": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "omv_sim3_solver_best": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "omv_sim3_solver_debug": (_I, [_VP, _I] + [_VP] * 10),
+    "omv_pnp_create": (_I, [_I, _I, _I, ctypes.POINTER(_VP)]),
+    "omv_pnp_destroy": (_I, [_VP]),
+    "omv_pnp_set": (_I, [_VP, _I] + [_VP] * 8 + [ctypes.c_double, _I, _I, _I, _F, _F, _VP, _VP, _VP]),
+    "omv_pnp_iterate": (_I, [_VP, _I, _I] + [_VP] * 6),
+    "omv_pnp_debug": (_I, [_VP, _I] + [_VP] * 11),
     "omv_optimize_sim3_create": (_I, [_I, _I, ctypes.POINTER(_VP)]),
     "omv_optimize_sim3_destroy": (_I, [_VP]),
     "omv_optimize_sim3": (_I, [_VP, _I] + [_VP] * 22),

@@ -43,16 +43,16 @@ def select_correspondences(indices1, indices2, valid=None):
     return int(c1), int(c2), idx, i1[idx, c1].astype(np.int32), i2[idx, c2].astype(np.int32)
 
 
-def draw(rng_or_rand, n_iterations, n):
-    """Raw draws [n_iterations][3] for a job with n correspondences by DUtils::Random::RandomInt's formula
+def draw(rng_or_rand, n_iterations, n, k=3):
+    """Raw draws [n_iterations][k] for a job with n correspondences by DUtils::Random::RandomInt's formula
     (Thirdparty/DBoW2/DUtils/Random.cpp:47-50): int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min with
-    d = n - i for the i-th pick.  rng_or_rand: a callable returning rand() values in [0, RAND_MAX], or a
-    numpy.random.Generator (then rand() is its integers(0, RAND_MAX + 1))."""
+    d = n - i for the i-th pick (k = 3 for Sim3Solver, 6 for MLPnPsolver).  rng_or_rand: a callable returning rand()
+    values in [0, RAND_MAX], or a numpy.random.Generator (then rand() is its integers(0, RAND_MAX + 1))."""
     if callable(rng_or_rand):
-        r = np.array([[rng_or_rand() for _ in range(3)] for _ in range(n_iterations)], np.float64).reshape(-1, 3)
+        r = np.array([[rng_or_rand() for _ in range(k)] for _ in range(n_iterations)], np.float64).reshape(-1, k)
     else:
-        r = rng_or_rand.integers(0, RAND_MAX + 1, (n_iterations, 3)).astype(np.float64)
-    d = np.maximum(n - np.arange(3), 1).astype(np.float64)
+        r = rng_or_rand.integers(0, RAND_MAX + 1, (n_iterations, k)).astype(np.float64)
+    d = np.maximum(n - np.arange(k), 1).astype(np.float64)
     return ((r / (RAND_MAX + 1.0)) * d).astype(np.int32)
 
 
