@@ -1233,6 +1233,65 @@ omv_status omv_kfdb_debug(omv_kfdb *h, int query, int32_t *max_common_words, int
                           int32_t *scored_slot, double *score, float *si, uint32_t *acc_bits, int32_t *acc_best,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Optimizer::InertialOptimization (src/Optimizer.cc:3469-3925): the IMU initialisation of LocalMapping::InitializeIMU
+ * (src/LocalMapping.cc:1255-1517), ScaleRefinement (:1548) and LoopClosing (src/LoopClosing.cc:2037), batched over
+ * n_jobs independent maps, one workgroup each.  The three overloads are modes:
+ *   FULL (:3469-3653)  velocities, bg, ba, gravity direction free, the scale iff mono; Levenberg, optimize(200), lambda
+ *                      init 1e3 only if priorG != 0 (otherwise tau * max diagonal); EdgePriorAcc / EdgePriorGyro
+ *   BIAS (:3655-3813)  velocities, bg, ba free; Rwg = I and scale = 1 (Rwg / scale are not read and come back
+ *                      untouched); Levenberg, optimize(200), lambda init 1e3; the same priors
+ *   GS   (:3815-3925)  gravity direction and scale free; Gauss-Newton, optimize(10); Huber (delta 1); no priors
+ * ---------------------------------------------------------------------------------------------- */
+#define OMV_INERTIAL_FULL 0
+#define OMV_INERTIAL_BIAS 1
+#define OMV_INERTIAL_GS 2
+#define OMV_INERTIAL_MAX_KF 320   /* keyframes of one job (the elimination's working set lives in LDS) */
+typedef struct omv_inertial_opt omv_inertial_opt;
+
+/* A handle for up to max_jobs jobs, max_kf_total keyframes and max_edges_total edges over all of them per call. */
+omv_status omv_inertial_opt_create(int max_jobs, int max_kf_total, int max_edges_total, omv_inertial_opt **out);
+omv_status omv_inertial_opt_destroy(omv_inertial_opt *h);
+
+/* Every pointer is HOST memory; the call synchronises `stream`.  Job j owns the keyframes kf_start[j] .. kf_start[j+1]-1
+ * and the edges edge_start[j] .. edge_start[j+1]-1 (both start at 0).  Per keyframe (the vertices of :3503-3520, i.e.
+ * mnId <= maxKFid): Rwb [9] row-major and twb [3], the body pose as VertexPose(KeyFrame*) forms it; vel_in [3];
+ * old_gyro_bias [3], GetGyroBias() before the call.  Per edge (the tests of :3571-3594: mPrevKF set, both ids
+ * <= maxKFid, the keyframe not bad): edge_kf1 / edge_kf2, the previous and the current keyframe as indices into the
+ * job's keyframes, and preint [OMV_PREINT_FLOATS], the current keyframe's record.  Per job: bg0 / ba0 [3], the bias of
+ * vpKFs.front() (every bias vertex is built from it; in GS mode the fixed bias of every edge), mode (OMV_INERTIAL_*),
+ * mono, priorG, priorA, and Rwg [9] / scale in and out.
+ * Outputs: Rwg, scale, bg [3], ba [3] per job; per keyframe vel [3] (double), vel_f32 [3] (what SetVelocity stores) and
+ * reintegrate: 1 iff (old_gyro_bias - (float)bg).norm() > 0.01 in float, the records Reintegrate() is called on (GS: 0,
+ * and bg, ba, vel are the inputs); iterations / trials per job: solver iterations and linear solves.
+ * The edges of a job must form simple paths (mPrevKF is a single link): a keyframe that is kf1 of two edges or kf2 of
+ * two, an index outside the job, a cycle are OMV_ERR_ARG; a keyframe without an edge is a legal vertex.  OMV_ERR_ARG also
+ * for a negative size or a descending start array, an unknown mode, more than OMV_INERTIAL_MAX_KF keyframes in a job,
+ * more jobs / keyframes / edges than the handle holds, a NULL pointer with a non-zero size. */
+omv_status omv_inertial_optimization(omv_inertial_opt *h, int n_jobs, const int32_t *kf_start, const int32_t *edge_start,
+                                     const double *Rwb, const double *twb, const double *vel_in, const float *old_gyro_bias,
+                                     const int32_t *edge_kf1, const int32_t *edge_kf2, const float *preint,
+                                     const double *bg0, const double *ba0, const int32_t *mode, const int32_t *mono,
+                                     const float *priorG, const float *priorA, double *Rwg, double *scale, double *bg,
+                                     double *ba, double *vel, float *vel_f32, uint8_t *reintegrate, int32_t *iterations,
+                                     int32_t *trials, void *stream);
+
+/* Test hook: job `job` of the last call, host outputs in the job's own keyframe / edge order (any may be NULL).  e0
+ * [E][9] the residuals at the input state.  The first buildSystem: Hvv [K][9] the velocity diagonal blocks, Hvoff [E][9]
+ * the V1-rows x V2-columns block of every edge, border [K][3][9] (columns bg ba gdir(2) scale), bv [K][3], corner [81],
+ * bc [9], chi2 (activeRobustChi2), lambda_init; rows and columns of fixed unknowns are zero.  xv [K][3], xc [9]: the
+ * first trial's solution.  iterations, trials, max_trials (the most trials of one iteration); err [2]: GS mode's float
+ * robust chi2 before and after; ticks [3]: the workgroup's time in buildSystem, in the linear solves and in the trials'
+ * error evaluations, in ticks of the device's constant 100 MHz clock.  Synchronous. */
+omv_status omv_inertial_opt_debug(omv_inertial_opt *h, int job, double *e0, double *Hvv, double *Hvoff, double *border,
+                                  double *bv, double *corner, double *bc, double *chi2, double *lambda_init, double *xv,
+                                  double *xc, int32_t *iterations, int32_t *trials, int32_t *max_trials, float *err,
+                                  int64_t *ticks, void *stream);
+/* Test hook, host only (no device needed): the path planner on one job.  order [K] position -> keyframe, pos_of [K],
+ * edge_in / edge_out [K] per position (-1: none), n_paths.  OMV_ERR_ARG where omv_inertial_optimization rejects. */
+omv_status omv_inertial_opt_plan(int K, int E, const int32_t *kf1, const int32_t *kf2, int32_t *order, int32_t *pos_of,
+                                 int32_t *edge_in, int32_t *edge_out, int32_t *n_paths);
+
 /* ---- Test hooks (no reference counterpart): the device linear-algebra routines on plain device arrays ----
  * Each launches the product's own instantiation of the routine, one workgroup per problem (`batch` problems, on
  * `stream`, not synchronised).  Every pointer is device memory. */

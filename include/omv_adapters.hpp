@@ -1700,6 +1700,72 @@ private:
     DeviceArray<int32_t> out_;
 };
 
+// ---- Optimizer::InertialOptimization ----------------------------------------------------------------------------
+// What the three overloads read from the map (src/Optimizer.cc:3503-3610), flattened by the caller: the keyframes with
+// mnId <= maxKFid in vpKFs order, and one edge per keyframe that passes the tests of :3574-3594 (mPrevKF set and not
+// newer than maxKFid, the keyframe not bad).  The bias vertices are built from vpKFs.front(): bg0 / ba0.
+struct InertialMap {
+    std::vector<double> Rwb, twb;          // [K][9], [K][3] the body pose (ImuCamPose of VertexPose(pKF))
+    std::vector<double> vel;               // [K][3] pKF->GetVelocity(), widened; in / out
+    std::vector<float> gyro_bias;          // [K][3] pKF->GetGyroBias() before the call
+    std::vector<int32_t> kf1, kf2;         // [E] mPrevKF and the keyframe, as indices into the arrays above
+    std::vector<float> preint;             // [E][OMV_PREINT_FLOATS] the keyframe's mpImuPreintegrated
+    double bg0[3] = {0, 0, 0}, ba0[3] = {0, 0, 0};
+    // outputs
+    std::vector<float> vel_f32;            // [K][3] what SetVelocity stores
+    std::vector<uint8_t> reintegrate;      // [K] the keyframes whose record Reintegrate() is called on
+    int iterations = 0, trials = 0;
+};
+
+namespace detail {
+inline void inertial_call(InertialMap &m, int mode, double *Rwg, double *scale, double *bg, double *ba, bool bMono,
+                          float priorG, float priorA, omv_inertial_opt *h, hipStream_t stream) {
+    const int K = (int)(m.Rwb.size() / 9), E = (int)m.kf1.size();
+    if (m.Rwb.size() != (size_t)9 * K || m.twb.size() != (size_t)3 * K || m.vel.size() != (size_t)3 * K ||
+        m.gyro_bias.size() != (size_t)3 * K || m.kf2.size() != (size_t)E || m.preint.size() != (size_t)E * OMV_PREINT_FLOATS)
+        throw Error("InertialOptimization: array lengths differ");
+    omv_inertial_opt *own = nullptr;
+    if (!h) {
+        check(omv_inertial_opt_create(1, std::max(K, 1), std::max(E, 1), &own), "omv_inertial_opt_create");
+        h = own;
+    }
+    const int32_t kf_start[2] = {0, K}, edge_start[2] = {0, E}, md = mode, mono = bMono ? 1 : 0;
+    int32_t it = 0, tr = 0;
+    std::vector<double> vel_out((size_t)3 * std::max(K, 1));
+    m.vel_f32.assign((size_t)3 * std::max(K, 1), 0.f), m.reintegrate.assign((size_t)std::max(K, 1), 0);
+    const omv_status rc = omv_inertial_optimization(h, 1, kf_start, edge_start, m.Rwb.data(), m.twb.data(), m.vel.data(),
+                                                    m.gyro_bias.data(), m.kf1.data(), m.kf2.data(), m.preint.data(), m.bg0,
+                                                    m.ba0, &md, &mono, &priorG, &priorA, Rwg, scale, bg, ba, vel_out.data(),
+                                                    m.vel_f32.data(), m.reintegrate.data(), &it, &tr, stream);
+    if (own) (void)omv_inertial_opt_destroy(own);
+    check(rc, "omv_inertial_optimization");
+    m.vel.assign(vel_out.begin(), vel_out.begin() + (size_t)3 * K);
+    m.vel_f32.resize((size_t)3 * K), m.reintegrate.resize((size_t)K);
+    m.iterations = it, m.trials = tr;
+}
+}  // namespace detail
+
+// void Optimizer::InertialOptimization(Map*, Matrix3d &Rwg, double &scale, Vector3d &bg, Vector3d &ba, bool bMono,
+// MatrixXd &covInertial, bool bFixedVel, bool bGauss, float priorG, float priorA): covInertial and bGauss are unused by
+// the reference and bFixedVel is false at its only call site; none is a parameter here.  Rwg [9] row-major.
+inline void InertialOptimization(InertialMap &map, double *Rwg, double &scale, double *bg, double *ba, bool bMono,
+                                 float priorG = 1e2f, float priorA = 1e6f, omv_inertial_opt *h = nullptr,
+                                 hipStream_t stream = nullptr) {
+    detail::inertial_call(map, OMV_INERTIAL_FULL, Rwg, &scale, bg, ba, bMono, priorG, priorA, h, stream);
+}
+// void Optimizer::InertialOptimization(Map*, Vector3d &bg, Vector3d &ba, float priorG, float priorA)
+inline void InertialOptimization(InertialMap &map, double *bg, double *ba, float priorG = 1e2f, float priorA = 1e6f,
+                                 omv_inertial_opt *h = nullptr, hipStream_t stream = nullptr) {
+    double Rwg[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, scale = 1.0;
+    detail::inertial_call(map, OMV_INERTIAL_BIAS, Rwg, &scale, bg, ba, false, priorG, priorA, h, stream);
+}
+// void Optimizer::InertialOptimization(Map*, Matrix3d &Rwg, double &scale)
+inline void InertialOptimization(InertialMap &map, double *Rwg, double &scale, omv_inertial_opt *h = nullptr,
+                                 hipStream_t stream = nullptr) {
+    double bg[3], ba[3];
+    detail::inertial_call(map, OMV_INERTIAL_GS, Rwg, &scale, bg, ba, false, 0.f, 0.f, h, stream);
+}
+
 }  // namespace omv_adapt
 
 #endif  // OMV_ADAPTERS_HPP

@@ -348,6 +348,11 @@ SIGNATURES = {
     "omv_optimize_sim3_destroy": (_I, [_VP]),
     "omv_optimize_sim3": (_I, [_VP, _I] + [_VP] * 22),
     "omv_optimize_sim3_debug": (_I, [_VP, _I] + [_VP] * 11),
+    "omv_inertial_opt_create": (_I, [_I, _I, _I, ctypes.POINTER(_VP)]),
+    "omv_inertial_opt_destroy": (_I, [_VP]),
+    "omv_inertial_optimization": (_I, [_VP, _I] + [_VP] * 25),
+    "omv_inertial_opt_debug": (_I, [_VP, _I] + [_VP] * 17),
+    "omv_inertial_opt_plan": (_I, [_I, _I] + [_VP] * 7),
     "omv_kfdb_create": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(_VP)]),
     "omv_kfdb_destroy": (_I, [_VP]),
     "omv_kfdb_add": (_I, [_VP, _I] + [_VP] * 5 + [_I, _VP]),

@@ -17,7 +17,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("OMV_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["orb_extract.hip", "match.hip", "lba.hip", "pose.hip", "tri.hip", "frame.hip", "imu.hip", "bow.hip", "bowmatch.hip",
-               "mappoint.hip", "fuse.hip", "sim3.hip", "pnp.hip", "optsim3.hip", "kfdb.hip", "selftest_math.hip", "omv_host.hip"]
+               "mappoint.hip", "fuse.hip", "sim3.hip", "pnp.hip", "optsim3.hip", "kfdb.hip", "inertial.hip", "selftest_math.hip", "omv_host.hip"]
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
              f"--offload-arch={ARCH}", "-Wno-unused-result"]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
@@ -86,6 +86,8 @@ KFDB_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "kfdb_consumer.cpp")
 KFDB_CONSUMER_BIN = os.path.join(PKG, "bin", "kfdb_consumer")
 MLPNP_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "mlpnp_consumer.cpp")
 MLPNP_CONSUMER_BIN = os.path.join(PKG, "bin", "mlpnp_consumer")
+INERTIAL_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "inertial_opt_consumer.cpp")
+INERTIAL_CONSUMER_BIN = os.path.join(PKG, "bin", "inertial_opt_consumer")
 
 
 def build_consumer(verbose=True, src=CONSUMER_SRC, out=CONSUMER_BIN):
@@ -116,6 +118,7 @@ def build_all(force=False, verbose=True):
     build_consumer(verbose, OPTSIM3_CONSUMER_SRC, OPTSIM3_CONSUMER_BIN)
     build_consumer(verbose, KFDB_CONSUMER_SRC, KFDB_CONSUMER_BIN)
     build_consumer(verbose, MLPNP_CONSUMER_SRC, MLPNP_CONSUMER_BIN)
+    build_consumer(verbose, INERTIAL_CONSUMER_SRC, INERTIAL_CONSUMER_BIN)
     return lib
 
 

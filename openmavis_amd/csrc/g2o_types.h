@@ -1090,4 +1090,109 @@ __device__ __forceinline__ bool ldlt_pick_solve(const double *H, const double *b
     return true;
 }
 
+// ---- EdgeInertialGS (G2oTypes.cc:601-746) ---------------------------------------------------------
+// The state of the vertices one edge reads, apart from the two fixed poses: the velocities of its keyframes, the one
+// bias of the graph (as the float IMU::Bias the edge builds from the double estimates), gravity g = Rwg gI and the scale.
+struct GsState {
+    float b1[6];     // bax bay baz bwx bwy bwz
+    double g[3];     // Rwg * (0, 0, -GRAVITY_VALUE)
+    double Rwg[9];
+    double s;
+};
+__device__ inline void gs_gravity(const double *Rwg, double *g) {
+    const double gI[3] = {0, 0, -(double)9.81f};
+    mv3(Rwg, gI, g);
+}
+
+// computeError (:624-659): e = (er, ev, ep).  eR (dR^T Rbw1 Rwb2), dvw = Rbw1 (v2 - v1) and dpw = Rbw1 (p2 - p1 - v1 dt)
+// are what linearizeOplus uses again; any may be null.
+__device__ inline void gs_error(const float *p, const double *Rwb1, const double *twb1, const double *v1,
+                                const double *Rwb2, const double *twb2, const double *v2, const GsState &S, double *e,
+                                double *eR_out, double *dvw, double *dpw) {
+    double dR[9], dV[3], dP[3];
+    delta_rot(p, S.b1, dR);
+    delta_vp(p, PreView::dV, PreView::JVg, PreView::JVa, S.b1, dV);
+    delta_vp(p, PreView::dP, PreView::JPg, PreView::JPa, S.b1, dP);
+    const double dt = (double)p[PreView::dT];
+    double A[9], eR[9];
+    {   // dR^T * Rwb1^T * Rwb2, left to right
+        double dRt[9], R1t[9];
+        tr3(dR, dRt), tr3(Rwb1, R1t);
+        mm3(dRt, R1t, A);
+        mm3(A, Rwb2, eR);
+    }
+    log_so3(eR, e);
+    if (eR_out)
+        for (int q = 0; q < 9; ++q) eR_out[q] = eR[q];
+    double t[3], w[3];
+    for (int q = 0; q < 3; ++q) t[q] = S.s * (v2[q] - v1[q]) - S.g[q] * dt;
+    mtv3(Rwb1, t, w);
+    for (int q = 0; q < 3; ++q) e[3 + q] = w[q] - dV[q];
+    for (int q = 0; q < 3; ++q) t[q] = S.s * (twb2[q] - twb1[q] - v1[q] * dt) - S.g[q] * dt * dt / 2;
+    mtv3(Rwb1, t, w);
+    for (int q = 0; q < 3; ++q) e[6 + q] = w[q] - dP[q];
+    if (dvw) {
+        for (int q = 0; q < 3; ++q) t[q] = v2[q] - v1[q];
+        mtv3(Rwb1, t, dvw);
+    }
+    if (dpw) {
+        for (int q = 0; q < 3; ++q) t[q] = twb2[q] - twb1[q] - v1[q] * dt;
+        mtv3(Rwb1, t, dpw);
+    }
+}
+
+// linearizeOplus (:661-746), the blocks of the six vertices that can be free, written to J with row stride `ld`:
+// columns V1 (0-2) V2 (3-5) bg (6-8) ba (9-11) gdir (12-13) scale (14); the blocks of a fixed vertex (fv: velocities,
+// fb: biases, fg: gravity direction, fs: scale) are written as zeros.  The scale column has no factor s (:741-745).
+__device__ inline void gs_jacobian(const float *p, const double *Rwb1, const GsState &S, const double *er, const double *eR,
+                                   const double *dvw, const double *dpw, bool fv, bool fb, bool fg, bool fs, double *J,
+                                   int ld) {
+    const double dt = (double)p[PreView::dT];
+    const double s = S.s;
+    for (int r = 0; r < 9; ++r)
+        for (int c = 0; c < 15; ++c) J[r * ld + c] = 0.0;
+    if (fv) {
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                const double rb = Rwb1[3 * c + r];   // Rbw1(r, c)
+                J[(3 + r) * ld + c] = -s * rb;
+                J[(6 + r) * ld + c] = -s * rb * dt;
+                J[(3 + r) * ld + 3 + c] = s * rb;
+            }
+    }
+    if (fb) {
+        const float dbgf[3] = {S.b1[3] - p[PreView::b + 3], S.b1[4] - p[PreView::b + 4], S.b1[5] - p[PreView::b + 5]};
+        const double dbg[3] = {(double)dbgf[0], (double)dbgf[1], (double)dbgf[2]};
+        double JRg[9], invJr[9], eRt[9], RJ[9], w3[3], A[9], Bm[9], Jg[9];
+        for (int q = 0; q < 9; ++q) JRg[q] = (double)p[PreView::JRg + q];
+        inv_right_jac(er, invJr);
+        tr3(eR, eRt);
+        mv3(JRg, dbg, w3);
+        right_jac(w3, RJ);
+        mm3(invJr, eRt, A);
+        mm3(A, RJ, Bm);
+        mm3(Bm, JRg, Jg);
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                J[r * ld + 6 + c] = -Jg[3 * r + c];
+                J[(3 + r) * ld + 6 + c] = -(double)p[PreView::JVg + 3 * r + c];
+                J[(6 + r) * ld + 6 + c] = -(double)p[PreView::JPg + 3 * r + c];
+                J[(3 + r) * ld + 9 + c] = -(double)p[PreView::JVa + 3 * r + c];
+                J[(6 + r) * ld + 9 + c] = -(double)p[PreView::JPa + 3 * r + c];
+            }
+    }
+    if (fg) {   // dGdTheta = Rwg Gm, Gm(0, 1) = -G, Gm(1, 0) = G: its columns are G Rwg(:, 1) and -G Rwg(:, 0)
+        const double G = (double)9.81f;
+        double c0[3], c1[3], a0[3], a1[3];
+        for (int q = 0; q < 3; ++q) c0[q] = S.Rwg[3 * q + 1] * G, c1[q] = S.Rwg[3 * q] * -G;
+        mtv3(Rwb1, c0, a0), mtv3(Rwb1, c1, a1);
+        for (int r = 0; r < 3; ++r) {
+            J[(3 + r) * ld + 12] = -a0[r] * dt, J[(3 + r) * ld + 13] = -a1[r] * dt;
+            J[(6 + r) * ld + 12] = -0.5 * a0[r] * dt * dt, J[(6 + r) * ld + 13] = -0.5 * a1[r] * dt * dt;
+        }
+    }
+    if (fs)
+        for (int r = 0; r < 3; ++r) J[(3 + r) * ld + 14] = dvw[r], J[(6 + r) * ld + 14] = dpw[r];
+}
+
 }  // namespace omv_g2o

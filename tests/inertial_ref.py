@@ -1,0 +1,480 @@
+"""Float64 numpy restatement of the three Optimizer::InertialOptimization overloads (src/Optimizer.cc:3469-3925) with
+dense matrices: the reference the device kernel (openmavis_amd/csrc/inertial.hip) is tested against.
+
+  edge      EdgeInertialGS (src/G2oTypes.cc:601-746): residual (er, ev, ep) from the float32 bias-corrected deltas
+            (GetDeltaRotation / Velocity / Position, renormalised rotation), the six free Jacobian blocks, the 9 x 9
+            information of the ctor (inverse by Gauss-Jordan with partial pivoting in the device's operation order,
+            symmetrised, eigenvalues below 1e-12 zeroed)
+  vertices  VertexVelocity / GyroBias / AccBias (additions), VertexGDir (Rwg <- Rwg ExpSO3(u0, u1, 0)), VertexScale
+            (s <- s exp(u))
+  solver    g2o's Levenberg loop (optimization_algorithm_levenberg.cpp:61-184: push / pop, computeScale, _nBad, the
+            lambda rules, computeLambdaInit) and Gauss-Newton, SparseOptimizer::optimize's "anything but OK ends it"
+  epilogue  float velocities, the Reintegrate() flag
+
+Switches:  deltas = "literal" | "smooth"   (smooth: float64 bias corrections without the float renormalisation; only
+                                             to differentiate through the edge)
+           solve  = "dense" | "structured" (dense Cholesky in g2o's vertex order -- velocities by keyframe, bg, ba,
+                                             gravity, scale -- or velocities eliminated first, then the Schur complement)
+Column order of an edge's Jacobian J [9][15]: V1 (3) V2 (3) bg (3) ba (3) gdir (2) scale (1)."""
+import numpy as np
+
+import oracle   # oracle/oracle.py: the product's float layer on the host (math_map)
+
+FULL, BIAS, GS = 0, 1, 2
+G = float(np.float32(9.81))
+DBL_MAX = np.finfo(np.float64).max
+f32 = np.float32
+
+# offsets inside one preintegration record (csrc/g2o_types.h PreView)
+DR, DV, DP, JRG, JVG, JVA, JPG, JPA, B, DT, C = 0, 9, 12, 15, 24, 33, 42, 51, 60, 66, 67
+
+
+# ---- float32 deltas, in the device's operation order ----------------------------------------------------------------
+def _f33mulv(A, x):
+    return (A[:, :, 0] * x[:, None, 0] + A[:, :, 1] * x[:, None, 1]) + A[:, :, 2] * x[:, None, 2]
+
+
+def _so3f_exp(w):
+    """Sophus SO3f::exp as csrc/g2o_types.h so3f_exp states it; w [E][3] float32 -> [E][3][3] float32."""
+    w = np.asarray(w, f32)
+    th2 = (w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2]
+    small = th2 < f32(1e-5) * f32(1e-5)
+    t4 = th2 * th2
+    imag_s = (f32(0.5) - f32(1.0 / 48.0) * th2) + f32(1.0 / 3840.0) * t4
+    real_s = (f32(1.0) - f32(1.0 / 8.0) * th2) + f32(1.0 / 384.0) * t4
+    with np.errstate(all="ignore"):
+        theta = np.sqrt(th2.astype(np.float64)).astype(f32)
+        half = f32(0.5) * theta
+        sc = np.asarray(oracle.math_map(0, np.ascontiguousarray(half, f32)), f32).reshape(-1, 2)
+        imag = np.where(small, imag_s, sc[:, 0] / theta).astype(f32)
+    real = np.where(small, real_s, sc[:, 1]).astype(f32)
+    qw, qx, qy, qz = real, imag * w[:, 0], imag * w[:, 1], imag * w[:, 2]
+    two = f32(2.0)
+    tx, ty, tz = two * qx, two * qy, two * qz
+    twx, twy, twz = tx * qw, ty * qw, tz * qw
+    txx, txy, txz = tx * qx, ty * qx, tz * qx
+    tyy, tyz, tzz = ty * qy, tz * qy, tz * qz
+    one = f32(1.0)
+    R = np.stack([one - (tyy + tzz), txy - twz, txz + twy, txy + twz, one - (txx + tzz), tyz - twx,
+                  txz - twy, tyz + twx, one - (txx + tyy)], axis=1).astype(f32)
+    return R.reshape(-1, 3, 3)
+
+
+def _polar3_f32(R):
+    """polar3<float> (Newton iteration to the polar factor, at most 20 steps, per matrix its own stop)."""
+    r = np.array(R, f32).reshape(-1, 9)
+    active = np.ones(len(r), bool)
+    with np.errstate(all="ignore"):
+        for _ in range(20):
+            if not active.any():
+                break
+            c = np.stack([r[:, 4] * r[:, 8] - r[:, 5] * r[:, 7], r[:, 5] * r[:, 6] - r[:, 3] * r[:, 8],
+                          r[:, 3] * r[:, 7] - r[:, 4] * r[:, 6], r[:, 2] * r[:, 7] - r[:, 1] * r[:, 8],
+                          r[:, 0] * r[:, 8] - r[:, 2] * r[:, 6], r[:, 1] * r[:, 6] - r[:, 0] * r[:, 7],
+                          r[:, 1] * r[:, 5] - r[:, 2] * r[:, 4], r[:, 2] * r[:, 3] - r[:, 0] * r[:, 5],
+                          r[:, 0] * r[:, 4] - r[:, 1] * r[:, 3]], axis=1).astype(f32)
+            det = (r[:, 0] * c[:, 0] + r[:, 1] * c[:, 1]) + r[:, 2] * c[:, 2]
+            inv = f32(1.0) / det
+            nv = ((r + c * inv[:, None]) * f32(0.5)).astype(f32)
+            dd = np.where(nv > r, nv - r, r - nv)
+            diff = np.zeros(len(r), f32)
+            for k in range(9):
+                diff = np.where(dd[:, k] > diff, dd[:, k], diff)
+            r = np.where(active[:, None], nv, r)
+            active = active & ~(diff <= f32(2.5e-7))
+    return r.reshape(-1, 3, 3)
+
+
+def _hat(w):
+    W = np.zeros(w.shape[:-1] + (3, 3))
+    W[..., 0, 1], W[..., 0, 2], W[..., 1, 0] = -w[..., 2], w[..., 1], w[..., 2]
+    W[..., 1, 2], W[..., 2, 0], W[..., 2, 1] = -w[..., 0], -w[..., 1], w[..., 0]
+    return W
+
+
+def _exp_so3_smooth(w):
+    d = np.linalg.norm(w, axis=-1)[..., None, None]
+    W = _hat(w)
+    with np.errstate(all="ignore"):
+        a = np.where(d < 1e-8, 1.0, np.sin(d) / d)
+        b = np.where(d < 1e-8, 0.5, (1 - np.cos(d)) / (d * d))
+    return np.eye(3) + a * W + b * (W @ W)
+
+
+def deltas(pre, bg, ba, kind="literal"):
+    """(dR [E][3][3], dV, dP [E][3], dbg [E][3]) of every record at the bias (bg, ba), as float64."""
+    pre = np.asarray(pre, f32).reshape(-1, 292)
+    E = len(pre)
+    if kind == "smooth":
+        p = pre.astype(np.float64)
+        dbg = np.asarray(bg, np.float64) - p[:, B + 3:B + 6]
+        dba = np.asarray(ba, np.float64) - p[:, B:B + 3]
+        m = lambda o: p[:, o:o + 9].reshape(E, 3, 3)
+        dR = m(DR) @ _exp_so3_smooth(np.einsum("eij,ej->ei", m(JRG), dbg))
+        dV = p[:, DV:DV + 3] + np.einsum("eij,ej->ei", m(JVG), dbg) + np.einsum("eij,ej->ei", m(JVA), dba)
+        dP = p[:, DP:DP + 3] + np.einsum("eij,ej->ei", m(JPG), dbg) + np.einsum("eij,ej->ei", m(JPA), dba)
+        return dR, dV, dP, dbg
+    b1g, b1a = np.asarray(bg, np.float64).astype(f32), np.asarray(ba, np.float64).astype(f32)
+    with np.errstate(all="ignore"):
+        dbg = (b1g[None, :] - pre[:, B + 3:B + 6]).astype(f32)
+        dba = (b1a[None, :] - pre[:, B:B + 3]).astype(f32)
+        m = lambda o: pre[:, o:o + 9].reshape(E, 3, 3)
+        Ex = _so3f_exp(_f33mulv(m(JRG), dbg))
+        A = m(DR)
+        R = (A[:, :, 0, None] * Ex[:, None, 0, :] + A[:, :, 1, None] * Ex[:, None, 1, :]) + A[:, :, 2, None] * Ex[:, None, 2, :]
+        dR = _polar3_f32(R.astype(f32))
+        dV = (pre[:, DV:DV + 3] + _f33mulv(m(JVG), dbg)) + _f33mulv(m(JVA), dba)
+        dP = (pre[:, DP:DP + 3] + _f33mulv(m(JPG), dbg)) + _f33mulv(m(JPA), dba)
+    return dR.astype(np.float64), dV.astype(np.float64), dP.astype(np.float64), dbg.astype(np.float64)
+
+
+# ---- SO(3) helpers of G2oTypes.cc ------------------------------------------------------------------------------------
+def log_so3(R):
+    R = np.asarray(R, np.float64)
+    w = np.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], -1) / 2
+    ct = (R[..., 0, 0] + R[..., 1, 1] + R[..., 2, 2] - 1.0) * 0.5
+    with np.errstate(all="ignore"):
+        ok = ~((ct > 1) | (ct < -1))
+        th = np.arccos(np.where(ok, ct, 0.0))
+        s = np.sin(th)
+        ok = ok & ~(np.abs(s) < 1e-5)
+        out = np.where(ok[..., None], th[..., None] * w / np.where(ok, s, 1.0)[..., None], w)
+    return out
+
+
+def inv_right_jac(v):
+    d2 = np.sum(v * v, -1)
+    d = np.sqrt(d2)
+    W = _hat(v)
+    with np.errstate(all="ignore"):
+        k = 1.0 / d2 - (1.0 + np.cos(d)) / (2.0 * d * np.sin(d))
+        J = np.eye(3) + W / 2 + (W @ W) * k[..., None, None]
+    return np.where((d < 1e-5)[..., None, None], np.eye(3), J)
+
+
+def right_jac(v):
+    d2 = np.sum(v * v, -1)
+    d = np.sqrt(d2)
+    W = _hat(v)
+    with np.errstate(all="ignore"):
+        J = np.eye(3) - W * ((1.0 - np.cos(d)) / d2)[..., None, None] + (W @ W) * ((d - np.sin(d)) / (d2 * d))[..., None, None]
+    return np.where((d < 1e-5)[..., None, None], np.eye(3), J)
+
+
+def exp_so3(w):
+    """ExpSO3 (G2oTypes.cc:802-815) with its NormalizeRotation (SVD polar factor)."""
+    w = np.asarray(w, np.float64)
+    d2 = float(w @ w)
+    d = np.sqrt(d2)
+    W = _hat(w)
+    if d < 1e-5:
+        R = np.eye(3) + W + 0.5 * (W @ W)
+    else:
+        R = np.eye(3) + W * np.sin(d) / d + (W @ W) * (1.0 - np.cos(d)) / d2
+    if not np.isfinite(R).all():
+        return R
+    u, _, vt = np.linalg.svd(R)
+    return u @ vt
+
+
+# ---- the information of EdgeInertialGS's ctor --------------------------------------------------------------------------
+def information(pre):
+    """[E][9][9]: C[0:9,0:9]^-1 (Gauss-Jordan, partial pivoting, the device's operation order), symmetrised, projected onto
+    the eigen-space of eigenvalues >= 1e-12."""
+    pre = np.asarray(pre, f32).reshape(-1, 292)
+    E = len(pre)
+    A = pre[:, C:C + 225].reshape(E, 15, 15)[:, :9, :9].astype(np.float64)
+    I = np.tile(np.eye(9), (E, 1, 1))
+    ar = np.arange(E)
+    with np.errstate(all="ignore"):
+        for c in range(9):
+            col = np.abs(A[:, c:, c])
+            p = c + np.argmax(np.where(np.isnan(col), -1.0, col), axis=1)
+            for M in (A, I):
+                t = M[ar, p].copy()
+                M[ar, p] = M[ar, c]
+                M[ar, c] = t
+            d = A[:, c, c].copy()
+            A[:, c] /= d[:, None]
+            I[:, c] /= d[:, None]
+            f = A[:, :, c].copy()
+            f[:, c] = 0.0
+            rowA, rowI = A[:, c].copy(), I[:, c].copy()
+            nz = (f != 0)[:, :, None]
+            A = np.where(nz, A - f[:, :, None] * rowA[:, None, :], A)
+            I = np.where(nz, I - f[:, :, None] * rowI[:, None, :], I)
+    out = np.empty((E, 9, 9))
+    for e in range(E):
+        S = (I[e] + I[e].T) / 2
+        if not np.isfinite(S).all():
+            out[e] = np.nan
+            continue
+        w, V = np.linalg.eigh(S)
+        w = np.where(w < 1e-12, 0.0, w)
+        out[e] = (V * w) @ V.T
+    return out
+
+
+# ---- the edge -----------------------------------------------------------------------------------------------------------
+class Problem:
+    def __init__(self, job, deltas_kind="literal"):
+        j = job
+        self.K = len(np.asarray(j["Rwb"]).reshape(-1, 9))
+        self.Rwb = np.asarray(j["Rwb"], np.float64).reshape(self.K, 3, 3)
+        self.twb = np.asarray(j["twb"], np.float64).reshape(self.K, 3)
+        self.kf1 = np.asarray(j["kf1"], np.int64).reshape(-1)
+        self.kf2 = np.asarray(j["kf2"], np.int64).reshape(-1)
+        self.E = len(self.kf1)
+        self.pre = np.asarray(j["preint"], f32).reshape(self.E, 292)
+        self.dt = self.pre[:, DT].astype(np.float64)
+        self.mode, self.mono = int(j["mode"]), bool(j["mono"])
+        self.priorG, self.priorA = float(f32(j.get("priorG", 0))), float(f32(j.get("priorA", 0)))
+        self.kind = deltas_kind
+        self.info = information(self.pre) if self.E else np.zeros((0, 9, 9))
+        self.huber = self.mode == GS
+        m = lambda o: self.pre[:, o:o + 9].reshape(self.E, 3, 3).astype(np.float64)
+        self.JRg, self.JVg, self.JVa, self.JPg, self.JPa = m(JRG), m(JVG), m(JVA), m(JPG), m(JPA)
+        # the free unknowns, in the order vel [3K] bg ba gdir (2) scale
+        free = np.zeros(3 * self.K + 9, bool)
+        touched = np.zeros(self.K, bool)
+        touched[self.kf1], touched[self.kf2] = True, True
+        if self.mode != GS:
+            free[:3 * self.K] = np.repeat(touched, 3)
+            free[3 * self.K:3 * self.K + 6] = True
+        if self.mode != BIAS and self.E:
+            free[3 * self.K + 6:3 * self.K + 8] = True
+            free[3 * self.K + 8] = self.mono if self.mode == FULL else True
+        self.free = free
+
+    def state0(self, job):
+        if self.mode == BIAS:
+            Rwg, s = np.eye(3), 1.0
+        else:
+            Rwg, s = np.asarray(job["Rwg"], np.float64).reshape(3, 3).copy(), float(job["scale"])
+        return dict(vel=np.asarray(job["vel"], np.float64).reshape(self.K, 3).copy(),
+                    bg=np.asarray(job["bg0"], np.float64).reshape(3).copy(),
+                    ba=np.asarray(job["ba0"], np.float64).reshape(3).copy(), Rwg=Rwg, s=s)
+
+    def error(self, st, want_jac=False):
+        """e [E][9] (and J [E][9][15]) at the state."""
+        E = self.E
+        if E == 0:
+            return (np.zeros((0, 9)), np.zeros((0, 9, 15))) if want_jac else np.zeros((0, 9))
+        dR, dV, dP, dbg = deltas(self.pre, st["bg"], st["ba"], self.kind)
+        R1, R2 = self.Rwb[self.kf1], self.Rwb[self.kf2]
+        Rbw1 = np.swapaxes(R1, 1, 2)
+        v1, v2 = st["vel"][self.kf1], st["vel"][self.kf2]
+        p1, p2 = self.twb[self.kf1], self.twb[self.kf2]
+        g = st["Rwg"] @ np.array([0.0, 0.0, -G])
+        s, dt = st["s"], self.dt[:, None]
+        eR = np.swapaxes(dR, 1, 2) @ Rbw1 @ R2
+        er = log_so3(eR)
+        mv = lambda M, x: np.einsum("eij,ej->ei", M, x)
+        ev = mv(Rbw1, s * (v2 - v1) - g * dt) - dV
+        ep = mv(Rbw1, s * (p2 - p1 - v1 * dt) - g * dt * dt / 2) - dP
+        e = np.concatenate([er, ev, ep], 1)
+        if not want_jac:
+            return e
+        J = np.zeros((E, 9, 15))
+        invJr = inv_right_jac(er)
+        J[:, 3:6, 0:3] = -s * Rbw1
+        J[:, 6:9, 0:3] = -s * Rbw1 * dt[:, :, None]
+        J[:, 3:6, 3:6] = s * Rbw1
+        J[:, 0:3, 6:9] = -invJr @ np.swapaxes(eR, 1, 2) @ right_jac(mv(self.JRg, dbg)) @ self.JRg
+        J[:, 3:6, 6:9], J[:, 6:9, 6:9] = -self.JVg, -self.JPg
+        J[:, 3:6, 9:12], J[:, 6:9, 9:12] = -self.JVa, -self.JPa
+        Gm = np.zeros((3, 2))
+        Gm[0, 1], Gm[1, 0] = -G, G
+        dG = Rbw1 @ (st["Rwg"] @ Gm)
+        J[:, 3:6, 12:14] = -dG * dt[:, :, None]
+        J[:, 6:9, 12:14] = -0.5 * dG * dt[:, :, None] * dt[:, :, None]
+        J[:, 3:6, 14] = mv(Rbw1, v2 - v1)          # no factor s: the reference's Jacobian (G2oTypes.cc:741-745)
+        J[:, 6:9, 14] = mv(Rbw1, p2 - p1 - v1 * dt)
+        return e, J
+
+    def chi2(self, st, e=None):
+        """activeRobustChi2 and the per-edge (chi2, rho1)."""
+        e = self.error(st) if e is None else e
+        c = np.einsum("ei,eij,ej->e", e, self.info, e) if self.E else np.zeros(0)
+        rho0, rho1 = c.copy(), np.ones_like(c)
+        if self.huber and self.E:
+            with np.errstate(all="ignore"):
+                big = ~(c <= 1.0)
+                sq = np.sqrt(c)
+                rho0 = np.where(big, 2 * sq * 1.0 - 1.0, c)
+                rho1 = np.where(big, 1.0 / sq, 1.0)
+        tot = float(np.sum(rho0))
+        if self.mode != GS:   # EdgePriorAcc / EdgePriorGyro: error = 0 - bias, information prior * I
+            tot += self.priorA * float(st["ba"] @ st["ba"]) + self.priorG * float(st["bg"] @ st["bg"])
+        return tot, c, rho1
+
+    def index(self):
+        K = self.K
+        tail = np.arange(3 * K, 3 * K + 9)
+        i1 = 3 * self.kf1[:, None] + np.arange(3)
+        i2 = 3 * self.kf2[:, None] + np.arange(3)
+        return np.concatenate([i1, i2, np.tile(tail, (self.E, 1))], 1)
+
+    def build(self, st):
+        """(H, b, chi2, e) over all 3K + 9 unknowns; rows / columns of fixed unknowns are zero."""
+        N = 3 * self.K + 9
+        H, b = np.zeros((N, N)), np.zeros(N)
+        e, J = self.error(st, True)
+        tot, c, rho1 = self.chi2(st, e)
+        if self.E:
+            idx = self.index()
+            J = J * self.free[idx][:, None, :]
+            Om = self.info * rho1[:, None, None]
+            JtO = np.einsum("eki,ekl->eil", J, Om)
+            He = JtO @ J
+            be = -np.einsum("eil,el->ei", JtO, e)
+            np.add.at(H, (idx[:, :, None], idx[:, None, :]), He)
+            np.add.at(b, idx, be)
+        if self.mode != GS:
+            K3 = 3 * self.K
+            H[K3:K3 + 3, K3:K3 + 3] += self.priorG * np.eye(3)
+            H[K3 + 3:K3 + 6, K3 + 3:K3 + 6] += self.priorA * np.eye(3)
+            b[K3:K3 + 3] += self.priorG * (0.0 - st["bg"])
+            b[K3 + 3:K3 + 6] += self.priorA * (0.0 - st["ba"])
+        return H, b, tot, e
+
+    def oplus(self, st, x):
+        K3 = 3 * self.K
+        n = dict(vel=st["vel"] + x[:K3].reshape(self.K, 3), bg=st["bg"] + x[K3:K3 + 3], ba=st["ba"] + x[K3 + 3:K3 + 6],
+                 Rwg=st["Rwg"], s=st["s"])
+        if self.free[K3 + 6]:
+            n["Rwg"] = st["Rwg"] @ exp_so3(np.array([x[K3 + 6], x[K3 + 7], 0.0]))
+        if self.free[K3 + 8]:
+            n["s"] = st["s"] * np.exp(x[K3 + 8])
+        return n
+
+    def solve(self, H, b, lam, how="dense"):
+        """(ok, x): (H + lam I) x = b over the free unknowns; ok False for a non-positive or non-finite pivot."""
+        N = len(b)
+        x = np.zeros(N)
+        act = np.nonzero(self.free)[0]
+        if len(act) == 0:
+            return True, x
+        with np.errstate(all="ignore"):
+            A = H[np.ix_(act, act)] + lam * np.eye(len(act))
+        r = b[act]
+        if not (np.isfinite(A).all() and np.isfinite(r).all()):
+            return False, x
+        try:
+            if how == "dense":
+                L = np.linalg.cholesky(A)
+                y = np.linalg.solve(L, r)
+                x[act] = np.linalg.solve(L.T, y)
+            else:
+                nv = int(np.sum(act < 3 * self.K))
+                if nv == 0 or nv == len(act):
+                    L = np.linalg.cholesky(A)
+                    x[act] = np.linalg.solve(L.T, np.linalg.solve(L, r))
+                else:
+                    Avv, Avc, Acc = A[:nv, :nv], A[:nv, nv:], A[nv:, nv:]
+                    Lv = np.linalg.cholesky(Avv)
+                    sol = lambda M: np.linalg.solve(Lv.T, np.linalg.solve(Lv, M))
+                    Y, yb = sol(Avc), sol(r[:nv])
+                    S = Acc - Avc.T @ Y
+                    Ls = np.linalg.cholesky(S)
+                    xc = np.linalg.solve(Ls.T, np.linalg.solve(Ls, r[nv:] - Avc.T @ yb))
+                    x[act] = np.concatenate([yb - Y @ xc, xc])
+        except np.linalg.LinAlgError:
+            return False, np.zeros(N)
+        return True, x
+
+
+def optimize(job, deltas="literal", solve="dense"):
+    """One job through its overload.  Returns a dict: the outputs (Rwg, scale, bg, ba, vel, vel_f32, reintegrate), the
+    first system (H, b, chi2, lambda_init, x, e0), per iteration (chi2, lambda, trials), iterations, trials, exit."""
+    P = Problem(job, deltas)
+    st = P.state0(job)
+    out = dict(first=None, log=[], iterations=0, trials=0, exit="max_iterations")
+    has_work = P.E > 0 or P.mode != GS
+    if P.mode == GS:
+        max_it = 10
+        x_prev = np.zeros(3 * P.K + 9)
+        for it in range(max_it if has_work else 0):
+            H, b, cur, e = P.build(st)
+            ok, x = P.solve(H, b, 0.0, solve)
+            if not ok:
+                x = x_prev   # the solver's vector keeps what it held
+            if it == 0:
+                out["first"] = dict(H=H, b=b, chi2=cur, lambda_init=0.0, x=x.copy(), e0=e)
+            st = P.oplus(st, x)
+            x_prev = x
+            out["iterations"] += 1
+            out["trials"] += 1
+            out["log"].append(dict(chi2=cur, lam=0.0, trials=1))
+            if not ok:
+                out["exit"] = "fail"
+                break
+    else:
+        lam, ni, n_bad = 0.0, 2.0, 0
+        for it in range(200):
+            H, b, cur, e = P.build(st)
+            ini = cur
+            if it == 0:
+                user = P.mode == BIAS or P.priorG != 0.0
+                lam = 1e3 if user else 1e-5 * float(np.max(np.abs(np.diag(H)[P.free]))) if P.free.any() else 0.0
+                ni, n_bad = 2.0, 0
+            out["iterations"] += 1
+            qmax, rho = 0, 0.0
+            entry_lam = lam
+            while True:
+                ok, x = P.solve(H, b, lam, solve)
+                if it == 0 and qmax == 0:
+                    out["first"] = dict(H=H, b=b, chi2=cur, lambda_init=lam, x=x.copy(), e0=e)
+                trial = P.oplus(st, x)
+                with np.errstate(all="ignore"):
+                    temp = P.chi2(trial)[0] if ok else DBL_MAX
+                    if not ok:
+                        temp = DBL_MAX
+                    scale = float(np.sum(x * (lam * x + b))) + 1e-3
+                    rho = (cur - temp) / scale
+                if rho > 0 and np.isfinite(temp):
+                    alpha = min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0)
+                    lam *= max(1.0 / 3.0, alpha)
+                    ni = 2.0
+                    cur = temp
+                    st = trial
+                else:
+                    lam *= ni
+                    ni *= 2
+                qmax += 1
+                out["trials"] += 1
+                if not (rho < 0 and qmax < 10):
+                    break
+            out["log"].append(dict(chi2=cur, lam=entry_lam, trials=qmax))
+            if qmax == 10 or rho == 0:
+                out["exit"] = "terminate"
+                break
+            n_bad = n_bad + 1 if (ini - cur) * 1e3 < ini else 0
+            if n_bad >= 3:
+                out["exit"] = "n_bad"
+                break
+    if out["first"] is None:
+        N = 3 * P.K + 9
+        out["first"] = dict(H=np.zeros((N, N)), b=np.zeros(N), chi2=0.0, lambda_init=0.0, x=np.zeros(N),
+                            e0=np.zeros((P.E, 9)))
+    # epilogue
+    if P.mode == BIAS:
+        out["Rwg"], out["scale"] = np.asarray(job["Rwg"], np.float64).reshape(3, 3).copy(), float(job["scale"])
+    else:
+        out["Rwg"], out["scale"] = st["Rwg"], st["s"]
+    out["bg"], out["ba"], out["vel"] = st["bg"], st["ba"], st["vel"]
+    out["vel_f32"] = st["vel"].astype(f32)
+    out["reintegrate"], out["bias_norm"] = reintegrate_flags(job, st["bg"]) if P.mode != GS else (np.zeros(P.K, np.uint8), np.zeros(P.K, f32))
+    out["free"] = P.free
+    return out
+
+
+def reintegrate_flags(job, bg):
+    """(flag [K] uint8, norm [K] float32): (GetGyroBias() - bg.cast<float>()).norm() > 0.01, in float (Eigen's stable-free
+    norm: sqrt of the sum of squares, summed left to right)."""
+    old = np.asarray(job["old_bg"], f32).reshape(-1, 3)
+    d = (old - np.asarray(bg, np.float64).astype(f32)[None, :]).astype(f32)
+    with np.errstate(all="ignore"):
+        n2 = ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).astype(f32)
+        n = np.sqrt(n2.astype(np.float64)).astype(f32)
+    return (n.astype(np.float64) > 0.01).astype(np.uint8), n
