@@ -1376,6 +1376,85 @@ omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda,
 omv_status omv_debug_live_allocations(int64_t *n);
 omv_status omv_debug_fail_allocation(int nth);
 
+/* ------------------------------------------------------------------------------------------------
+ * Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1280-1830), and the graph Optimizer::BundleAdjustment (:40-366)
+ * and the merge overload of LocalBundleAdjustment (:3927-4363) share: VertexSE3Expmap keyframes, VertexSBAPointXYZ
+ * points, EdgeSE3ProjectXYZ / ...ToBody / ...SLToBody / ...SRToBody and g2o::EdgeStereoSE3ProjectXYZ edges,
+ * BlockSolver_6_3 with Levenberg.  The visual kind of the omv_lba solver: the same Schur complement, block LDL^T, LM
+ * control and host plan; state, Jacobians, update, lambda_0 and outlier test are this graph's.  Single rank.
+ * The caller flattens its window (host-side selection and write-back stay with the caller) and keeps the state on the
+ * device between calls: optimize(5), set_levels + Huber 0, optimize(10) is the merge overload's two rounds.
+ * ---------------------------------------------------------------------------------------------- */
+struct omv_vba_problem {
+    int n_cams;
+    const float *cam;          /* [n_cams][8] fx fy cx cy k1..k4 (Pinhole: fx fy cx cy) */
+    const int32_t *cam_model;  /* [n_cams] OMV_CAM_KB8 / OMV_CAM_PINHOLE; NULL: every camera KannalaBrandt8 */
+    const double *q_c0, *t_c0; /* [n_cams][4] (x y z w), [n_cams][3]: camera c <- camera 0 (mTrl, mTsll, mTsrl); camera 0
+                                  is the vertex's own camera (identity) */
+    int n_kf, n_opt;           /* keyframes; the first n_opt optimisable, the rest fixed (the InitKF among them) */
+    double *q_cw, *t_cw;       /* [n_kf][4] (x y z w), [n_kf][3]: camera 0's Tcw (in/out) */
+    int n_pts;
+    double *pts;               /* [n_pts][3] (in/out) */
+    int n_mono;                /* 2-row edges: camera 0 -> EdgeSE3ProjectXYZ, camera c > 0 -> the ToBody edge of T_c0[c] */
+    const int32_t *mono_pt, *mono_kf, *mono_cam;
+    const double *mono_obs;    /* [n_mono][2] */
+    const float *mono_inv_sigma2;
+    int n_stereo;              /* g2o::EdgeStereoSE3ProjectXYZ on camera 0 */
+    const int32_t *stereo_pt, *stereo_kf;
+    const double *stereo_obs;  /* [n_stereo][3] (u, v, u_R >= 0) */
+    const float *stereo_inv_sigma2;
+    double fx, fy, cx, cy, bf; /* the stereo edges' pinhole (pKF->fx ... mbf, floats widened) */
+};
+typedef struct omv_vba_problem omv_vba_problem;
+
+struct omv_vba_opts {
+    int iterations;            /* optimize(n) */
+    double lambda_init;        /* setUserLambdaInit (100 on an inertial map); <= 0: computeLambdaInit = 1e-5 max |diag H| */
+    int max_trials;            /* maxTrialsAfterFailure (10) */
+    double huber_mono, huber_stereo;   /* Huber deltas: (float)sqrt(5.991) / (float)sqrt(7.815); 0 = no robust kernel */
+};
+typedef struct omv_vba_opts omv_vba_opts;
+
+struct omv_vba_result {
+    double err, err_end;       /* activeRobustChi2 before optimize() / of the last computed errors */
+    int iterations, trials;
+    double lambda;             /* final lambda */
+    double lambda_init;        /* the lambda_0 used (computeLambdaInit's when opts.lambda_init <= 0) */
+    double *mono_chi2;         /* optional [n_mono]: e->chi2() at the final state (excluded edges too) */
+    uint8_t *mono_outlier;     /* optional [n_mono]: chi2 > 5.991 || !isDepthPositive (depth in the edge's camera) */
+    double *stereo_chi2;       /* optional [n_stereo] */
+    uint8_t *stereo_outlier;   /* optional [n_stereo]: chi2 > 7.815 || !isDepthPositive */
+};
+typedef struct omv_vba_result omv_vba_result;
+
+typedef struct omv_vba omv_vba;
+
+/* Capacities: keyframes, cameras, points, edges (2-row + stereo).  A problem beyond them is OMV_ERR_CAPACITY. */
+omv_status omv_vba_create(int max_kf, int max_cams, int max_pts, int max_edges, omv_vba **out);
+omv_status omv_vba_destroy(omv_vba *h);
+/* Upload and plan a problem; every edge at level 0.  OMV_ERR_ARG (a NULL or out-of-range field) and OMV_ERR_CAPACITY
+ * leave the previous problem as it was, OMV_ERR_HIP leaves none.  Without a problem every call below is OMV_ERR_ARG
+ * before any launch. */
+omv_status omv_vba_set_problem(omv_vba *h, const omv_vba_problem *p);
+/* Edge levels in the caller's order (0 = active, 1 = excluded: it adds nothing to errors, chi2 sums or the system; a
+ * point whose edges are all excluded does not move).  NULL arrays: every edge of that kind active. */
+omv_status omv_vba_set_levels(omv_vba *h, const uint8_t *mono_level, const uint8_t *stereo_level);
+/* optimize(o->iterations) from the state on the device (it stays there for the next call); q_cw, t_cw and pts of `p`
+ * receive the new state.  Synchronous. */
+omv_status omv_vba_optimize(omv_vba *h, const omv_vba_opts *o, omv_vba_problem *p, omv_vba_result *r);
+/* Errors and Jacobians at the device state for parity (any may be NULL): mono_err [n_mono][2], mono_jxi [n_mono][6]
+ * (2x3), mono_jxj [n_mono][12] (2x6, (omega, upsilon)); stereo_err [n_stereo][3], jxi [.][9], jxj [.][18]. */
+omv_status omv_vba_evaluate(omv_vba *h, const omv_vba_opts *o, double *mono_err, double *mono_jxi, double *mono_jxj,
+                            double *stereo_err, double *stereo_jxi, double *stereo_jxj);
+/* The state uploaded by the last set_problem again (the levels stay). */
+omv_status omv_vba_reset(omv_vba *h);
+/* omv_lba_debug_solve for this kind (Huber deltas from `o`); S, rhs, x, plan as there. */
+omv_status omv_vba_debug_solve(omv_vba *h, const omv_vba_opts *o, double lambda, double *S, double *rhs, double *x,
+                               int32_t *fail, int32_t *plan, int plan_cap);
+/* omv_lba_enable_timing / omv_lba_stage_ms for this kind. */
+omv_status omv_vba_enable_timing(omv_vba *h, int on);
+omv_status omv_vba_stage_ms(omv_vba *h, double *ms4, int *trials);
+
 #ifdef __cplusplus
 }
 #endif

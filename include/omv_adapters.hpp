@@ -1766,6 +1766,90 @@ inline void InertialOptimization(InertialMap &map, double *Rwg, double &scale, o
     detail::inertial_call(map, OMV_INERTIAL_GS, Rwg, &scale, bg, ba, false, 0.f, 0.f, h, stream);
 }
 
+// ---- Optimizer::LocalBundleAdjustment (the LocalMapping overload, src/Optimizer.cc:1280-1830) --------------------
+// The window the reference selects (:1288-1348) flattened by the caller, who also writes the result back (:1787-1823):
+// the keyframes that are optimised first (lLocalKeyFrames without the map's InitKF), then the fixed ones (the InitKF if
+// it is local, then lFixedCameras); camera 0's Tcw per keyframe as SE3Quat (q (x y z w), t); lLocalMapPoints; one 2-row
+// edge per observation without a right coordinate (camera 0 EdgeSE3ProjectXYZ, cameras 1 / 2 / 3 the ToBody / SLToBody /
+// SRToBody edges) and one stereo edge per camera-0 observation with one, each in the reference's creation order.
+struct LocalBAView {
+    int n_cams = 0;
+    std::vector<float> cam;                // [n_cams][8]
+    std::vector<int32_t> cam_model;        // [n_cams] OMV_CAM_KB8 / OMV_CAM_PINHOLE; empty: all KannalaBrandt8
+    std::vector<double> q_c0, t_c0;        // [n_cams][4], [n_cams][3]: identity, mTrl, mTsll, mTsrl
+    int n_opt = 0;                         // the keyframes optimised (the first n_opt of the arrays)
+    int n_local = 0;                       // lLocalKeyFrames.size() (n_opt, + 1 when the InitKF is local)
+    std::vector<double> q_cw, t_cw;        // [K][4], [K][3]; in / out
+    std::vector<double> pts;               // [P][3]; in / out
+    std::vector<int32_t> mono_pt, mono_kf, mono_cam;
+    std::vector<double> mono_obs;          // [E][2]
+    std::vector<float> mono_inv_sigma2;
+    std::vector<int32_t> stereo_pt, stereo_kf;
+    std::vector<double> stereo_obs;        // [S][3]
+    std::vector<float> stereo_inv_sigma2;
+    double fx = 0, fy = 0, cx = 0, cy = 0, bf = 0;   // pKFi->fx ... mbf of the stereo edges
+    // outputs
+    std::vector<std::pair<int, int>> vToErase;   // (keyframe, map point) indices, in the reference's order: Mono, Body,
+                                                 // Stereo, SL, SR
+    double err = 0, err_end = 0;
+    int iterations = 0, trials = 0;
+};
+
+// void Optimizer::LocalBundleAdjustment(KeyFrame *pKF, bool *pbStopFlag, Map *pMap, int &num_fixedKF, int &num_OptKF,
+// int &num_MPs, int &num_edges): `view` stands for pKF's window and bInertialMap for pMap->IsInertial() (lambda_0 = 100,
+// else computeLambdaInit).  pbStopFlag is read once before the optimisation, as the reference does before optimize();
+// the stop inside optimize() (setForceStopFlag) is not modelled, as in LocalInertialBA's adapter.  Returns before any
+// device call when the window has no fixed keyframe (:1350-1355).
+inline void LocalBundleAdjustment(LocalBAView &view, bool *pbStopFlag, bool bInertialMap, int &num_fixedKF, int &num_OptKF,
+                                  int &num_MPs, int &num_edges, omv_vba *h = nullptr) {
+    LocalBAView &v = view;
+    const int K = (int)(v.q_cw.size() / 4), P = (int)(v.pts.size() / 3), E = (int)v.mono_pt.size(), S = (int)v.stereo_pt.size();
+    if (v.t_cw.size() != (size_t)3 * K || v.mono_kf.size() != (size_t)E || v.mono_cam.size() != (size_t)E ||
+        v.mono_obs.size() != (size_t)2 * E || v.mono_inv_sigma2.size() != (size_t)E || v.stereo_kf.size() != (size_t)S ||
+        v.stereo_obs.size() != (size_t)3 * S || v.stereo_inv_sigma2.size() != (size_t)S ||
+        v.cam.size() != (size_t)8 * v.n_cams || v.q_c0.size() != (size_t)4 * v.n_cams || v.t_c0.size() != (size_t)3 * v.n_cams)
+        throw Error("LocalBundleAdjustment: array lengths differ");
+    v.vToErase.clear();
+    num_fixedKF = K - v.n_opt;
+    if (num_fixedKF == 0) return;
+    num_OptKF = v.n_local > 0 ? v.n_local : v.n_opt;
+    num_MPs = P;
+    num_edges = E + S;
+    if (pbStopFlag && *pbStopFlag) return;
+    omv_vba *own = nullptr;
+    if (!h) {
+        check(omv_vba_create(K, v.n_cams, std::max(P, 1), std::max(E + S, 1), &own), "omv_vba_create");
+        h = own;
+    }
+    omv_vba_problem p{};
+    p.n_cams = v.n_cams, p.cam = v.cam.data(), p.cam_model = v.cam_model.empty() ? nullptr : v.cam_model.data();
+    p.q_c0 = v.q_c0.data(), p.t_c0 = v.t_c0.data(), p.n_kf = K, p.n_opt = v.n_opt;
+    p.q_cw = v.q_cw.data(), p.t_cw = v.t_cw.data(), p.n_pts = P, p.pts = v.pts.data();
+    p.n_mono = E, p.mono_pt = v.mono_pt.data(), p.mono_kf = v.mono_kf.data(), p.mono_cam = v.mono_cam.data();
+    p.mono_obs = v.mono_obs.data(), p.mono_inv_sigma2 = v.mono_inv_sigma2.data();
+    p.n_stereo = S, p.stereo_pt = v.stereo_pt.data(), p.stereo_kf = v.stereo_kf.data(), p.stereo_obs = v.stereo_obs.data();
+    p.stereo_inv_sigma2 = v.stereo_inv_sigma2.data();
+    p.fx = v.fx, p.fy = v.fy, p.cx = v.cx, p.cy = v.cy, p.bf = v.bf;
+    // thHuberMono / thHuberStereo are floats (:1469-1470)
+    const omv_vba_opts o{10, bInertialMap ? 100.0 : 0.0, 10, (double)(float)std::sqrt(5.991), (double)(float)std::sqrt(7.815)};
+    std::vector<uint8_t> mo((size_t)std::max(E, 1)), so((size_t)std::max(S, 1));
+    omv_vba_result r{};
+    r.mono_outlier = mo.data(), r.stereo_outlier = so.data();
+    omv_status rc = omv_vba_set_problem(h, &p);
+    if (rc == OMV_OK) rc = omv_vba_optimize(h, &o, &p, &r);
+    if (own) (void)omv_vba_destroy(own);
+    check(rc, "omv_vba_set_problem / omv_vba_optimize");
+    v.err = r.err, v.err_end = r.err_end, v.iterations = r.iterations, v.trials = r.trials;
+    auto erase_cam = [&](int c) {
+        for (int e = 0; e < E; ++e)
+            if (v.mono_cam[e] == c && mo[e]) v.vToErase.emplace_back(v.mono_kf[e], v.mono_pt[e]);
+    };
+    erase_cam(0), erase_cam(1);
+    for (int e = 0; e < S; ++e)
+        if (so[e]) v.vToErase.emplace_back(v.stereo_kf[e], v.stereo_pt[e]);
+    erase_cam(2), erase_cam(3);
+}
+
 }  // namespace omv_adapt
 
 #endif  // OMV_ADAPTERS_HPP

@@ -232,6 +232,30 @@ class LbaResult(ctypes.Structure):
                 ("stereo_chi2", ctypes.c_void_p), ("stereo_outlier", ctypes.c_void_p)]
 
 
+class VbaProblem(ctypes.Structure):
+    """omv_vba_problem (include/omv.h)."""
+    _fields_ = [("n_cams", ctypes.c_int), ("cam", ctypes.c_void_p), ("cam_model", ctypes.c_void_p),
+                ("q_c0", ctypes.c_void_p), ("t_c0", ctypes.c_void_p), ("n_kf", ctypes.c_int), ("n_opt", ctypes.c_int),
+                ("q_cw", ctypes.c_void_p), ("t_cw", ctypes.c_void_p), ("n_pts", ctypes.c_int), ("pts", ctypes.c_void_p),
+                ("n_mono", ctypes.c_int), ("mono_pt", ctypes.c_void_p), ("mono_kf", ctypes.c_void_p),
+                ("mono_cam", ctypes.c_void_p), ("mono_obs", ctypes.c_void_p), ("mono_inv_sigma2", ctypes.c_void_p),
+                ("n_stereo", ctypes.c_int), ("stereo_pt", ctypes.c_void_p), ("stereo_kf", ctypes.c_void_p),
+                ("stereo_obs", ctypes.c_void_p), ("stereo_inv_sigma2", ctypes.c_void_p), ("fx", ctypes.c_double),
+                ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double), ("bf", ctypes.c_double)]
+
+
+class VbaOpts(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("lambda_init", ctypes.c_double), ("max_trials", ctypes.c_int),
+                ("huber_mono", ctypes.c_double), ("huber_stereo", ctypes.c_double)]
+
+
+class VbaResult(ctypes.Structure):
+    _fields_ = [("err", ctypes.c_double), ("err_end", ctypes.c_double), ("iterations", ctypes.c_int),
+                ("trials", ctypes.c_int), ("lambda_", ctypes.c_double), ("lambda_init", ctypes.c_double),
+                ("mono_chi2", ctypes.c_void_p), ("mono_outlier", ctypes.c_void_p),
+                ("stereo_chi2", ctypes.c_void_p), ("stereo_outlier", ctypes.c_void_p)]
+
+
 # numpy dtype with the omv_kp layout (24 bytes)
 try:
     import numpy as _np
@@ -364,6 +388,17 @@ SIGNATURES = {
     "omv_kfdb_detect_n_best": (_I, [_VP, _I] + [_VP] * 7 + [_I, _I] + [_VP] * 5),
     "omv_kfdb_detect_reloc": (_I, [_VP, _I] + [_VP] * 5 + [_I] + [_VP] * 3),
     "omv_kfdb_debug": (_I, [_VP, _I] + [_VP] * 12),
+    "omv_vba_create": (_I, [_I, _I, _I, _I, ctypes.POINTER(_VP)]),
+    "omv_vba_destroy": (_I, [_VP]),
+    "omv_vba_set_problem": (_I, [_VP, ctypes.POINTER(VbaProblem)]),
+    "omv_vba_set_levels": (_I, [_VP, _VP, _VP]),
+    "omv_vba_optimize": (_I, [_VP, ctypes.POINTER(VbaOpts), ctypes.POINTER(VbaProblem), ctypes.POINTER(VbaResult)]),
+    "omv_vba_evaluate": (_I, [_VP, ctypes.POINTER(VbaOpts)] + [_VP] * 6),
+    "omv_vba_reset": (_I, [_VP]),
+    "omv_vba_debug_solve": (_I, [_VP, ctypes.POINTER(VbaOpts), ctypes.c_double, _VP, _VP, _VP, ctypes.POINTER(_I),
+                                 _VP, _I]),
+    "omv_vba_enable_timing": (_I, [_VP, _I]),
+    "omv_vba_stage_ms": (_I, [_VP, _VP, ctypes.POINTER(_I)]),
     "omv_debug_live_allocations": (_I, [ctypes.POINTER(ctypes.c_int64)]),
     "omv_debug_fail_allocation": (_I, [_I]),
 }

@@ -88,6 +88,8 @@ MLPNP_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "mlpnp_consumer.cpp")
 MLPNP_CONSUMER_BIN = os.path.join(PKG, "bin", "mlpnp_consumer")
 INERTIAL_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "inertial_opt_consumer.cpp")
 INERTIAL_CONSUMER_BIN = os.path.join(PKG, "bin", "inertial_opt_consumer")
+VBA_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "vba_consumer.cpp")
+VBA_CONSUMER_BIN = os.path.join(PKG, "bin", "vba_consumer")
 
 
 def build_consumer(verbose=True, src=CONSUMER_SRC, out=CONSUMER_BIN):
@@ -119,6 +121,7 @@ def build_all(force=False, verbose=True):
     build_consumer(verbose, KFDB_CONSUMER_SRC, KFDB_CONSUMER_BIN)
     build_consumer(verbose, MLPNP_CONSUMER_SRC, MLPNP_CONSUMER_BIN)
     build_consumer(verbose, INERTIAL_CONSUMER_SRC, INERTIAL_CONSUMER_BIN)
+    build_consumer(verbose, VBA_CONSUMER_SRC, VBA_CONSUMER_BIN)
     return lib
 
 

@@ -25,6 +25,8 @@
 //   The accept / reject decision (rho, lambda schedule, push/pop) runs on the device (finish_trial_kernel,
 //   LmCtl) with one read-back per optimize(); a host-driven loop with the same decisions is kept for
 //   sharded solves and parity checks.  Push/pop is a double-buffered state.
+// The same solver has a visual kind (omv_vba: Optimizer::LocalBundleAdjustment's graph, SE3Quat keyframes, the
+// EdgeSE3ProjectXYZ family): see Kind<V> below; only the kernels the pose parameterisation reaches are templates on it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -117,6 +119,152 @@ __device__ __forceinline__ double mono_err_edge(const Rig &rig, const double *R,
     if (ur >= 0.f) huber(c2, delta_st, dsqr_st, r0, r1);
     else huber(c2, delta, dsqr, r0, r1);
     return r0;
+}
+
+// ---- the visual kind (omv_vba: Optimizer::LocalBundleAdjustment / BundleAdjustment) ---------------------------------
+// The same solver on another parameterisation: the keyframe state is the SE3Quat Tcw of camera 0, q (x y z w) in the
+// first four doubles of the keyframe's Rwb slot and t in its twb slot, updated by VertexSE3Expmap::oplusImpl; the rig's
+// Rcb / tcb hold the constant camera c <- camera 0 transforms (mTrl / mTsll / mTsrl, identity for camera 0), and the
+// per-camera Rcw / tcw are derived from (q, t) after every update as `mTrl * T` and toRotationMatrix do.  Kernels that
+// depend on the parameterisation are templates on the kind; Kind<false> is empty, so the inertial instantiations are
+// the code they were.
+template <bool V>
+struct Kind {};
+template <>
+struct Kind<true> {
+    double qc0[kMaxCams][4];     // rotation of camera c <- camera 0 (its matrix is rig.Rcb[c], its translation rig.tcb[c])
+    double fx, fy, cx, cy, bf;   // g2o::EdgeStereoSE3ProjectXYZ's own pinhole
+    const double *huber;         // [2] device: Huber delta of the 2-row edges / the stereo edges; 0 = no kernel
+    const uint8_t *level;        // [E] device order: 1 = the edge is excluded (setLevel(1) / initializeOptimization(0))
+};
+
+// Huber with delta > 0, the plain chi2 with delta == 0 (setRobustKernel(0))
+__device__ __forceinline__ void huber0(double e2, double delta, double &r0, double &r1) {
+    if (delta > 0) huber(e2, delta, delta * delta, r0, r1);
+    else r0 = e2, r1 = 1.0;
+}
+
+// Camera c's pose of a keyframe from camera 0's (q, t): SE3Quat::operator* (se3quat.h:104-110) and toRotationMatrix.
+__device__ __forceinline__ void vis_cam_pose(const Rig &rig, const Kind<true> &vis, int c, const double *q, const double *t,
+                                             double Rc[9], double tc[3]) {
+    if (c == 0) {   // the vertex's own camera: T itself
+        q_to_mat(q, Rc);
+        for (int i = 0; i < 3; ++i) tc[i] = t[i];
+        return;
+    }
+    double qc[4], rt[3];
+    q_rot(vis.qc0[c], t, rt);
+    for (int i = 0; i < 3; ++i) tc[i] = rig.tcb[c][i] + rt[i];
+    q_mul(vis.qc0[c], q, qc);
+    q_normalize_pos(qc);
+    q_to_mat(qc, Rc);
+}
+
+// computeError of EdgeSE3ProjectXYZ / ...ToBody (OptimizableTypes.h:142-148, :174-180: obs - pCamera->project) and of
+// g2o::EdgeStereoSE3ProjectXYZ (types_six_dof_expmap.cpp:190-197: invz and bf * invz are floats) where ur >= 0, at the
+// edge camera's pose (R, t); residual and chi2 into the error buffers.  Returns the robust chi2; an excluded edge's
+// chi2 is still written, and it adds nothing to activeRobustChi2.
+__device__ __forceinline__ double vis_err_edge(const Rig &rig, const Kind<true> &vis, const double *R, const double *t,
+                                               const Edges &E, int e, const double *X, double *err, double *err3,
+                                               double *chi2) {
+    double Xc[3];
+    mv3(R, X, Xc);
+    Xc[0] += t[0], Xc[1] += t[1], Xc[2] += t[2];
+    const double w = (double)E.w[e];
+    const float ur = E.ur[e];
+    double e0, e1, c2;
+    if (ur >= 0.f) {
+        const float invz = (float)(1.0 / Xc[2]);
+        const double u = Xc[0] * (double)invz * vis.fx + vis.cx, v = Xc[1] * (double)invz * vis.fy + vis.cy;
+        const double e2 = (double)ur - (u - (double)((float)vis.bf * invz));
+        e0 = E.obs[2 * e] - u, e1 = E.obs[2 * e + 1] - v;
+        err3[e] = e2;
+        c2 = e0 * w * e0 + e1 * w * e1 + e2 * w * e2;
+    } else {
+        double u, v;
+        cam_project(rig, E.cam[e], Xc, u, v);
+        e0 = E.obs[2 * e] - u, e1 = E.obs[2 * e + 1] - v;
+        c2 = e0 * w * e0 + e1 * w * e1;
+    }
+    err[2 * e] = e0, err[2 * e + 1] = e1;
+    chi2[e] = c2;
+    double r0, r1;
+    huber0(c2, vis.huber[ur >= 0.f ? 1 : 0], r0, r1);
+    return vis.level[e] ? 0.0 : r0;
+}
+
+// linearizeOplus of the five edges at the current errors, in the reference's own form: JX = _jacobianOplusXi (nr x 3),
+// JP = _jacobianOplusXj (nr x 6, (omega, upsilon) order), w and om as edge_jacobians.
+//   EdgeSE3ProjectXYZ (OptimizableTypes.cpp:202-221) and the three ToBody edges (:252-371): -projectJac(X_c) R_cw and
+//   -projectJac(X_c) R_c0 SE3deriv(X_l), X_l in camera 0 (R_c0 the identity there);
+//   g2o::EdgeStereoSE3ProjectXYZ (types_six_dof_expmap.cpp:228-274), entry by entry.
+// An excluded edge has zero Jacobians and weights: it adds nothing to the system.
+__device__ __forceinline__ int vis_edge_jacobians(const Rig &rig, const Kind<true> &vis, const State &s, const Edges &E,
+                                                  int e, const double *err, const double *err3, const double *chi2,
+                                                  double JX[9], double JP[18], double &w, double om[3]) {
+    const bool st = E.ur[e] >= 0.f;
+    if (vis.level[e]) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) JX[q] = 0.0;
+#pragma unroll
+        for (int q = 0; q < 18; ++q) JP[q] = 0.0;
+        w = 0.0, om[0] = om[1] = om[2] = 0.0;
+        return st ? 3 : 2;
+    }
+    const int k = E.kf[e], c = E.cam[e], C = rig.n_cams;
+    const double *R = s.Rcw + ((size_t)k * C + c) * 9, *t = s.tcw + ((size_t)k * C + c) * 3;
+    const double *X = s.pts + (size_t)E.pt[e] * 3;
+    double Xc[3];
+    mv3(R, X, Xc);
+    for (int q = 0; q < 3; ++q) Xc[q] += t[q];
+    if (st) {
+        const double x = Xc[0], y = Xc[1], z = Xc[2], z_2 = z * z, fx = vis.fx, fy = vis.fy, bf = vis.bf;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            JX[q] = -fx * R[q] / z + fx * x * R[6 + q] / z_2;
+            JX[3 + q] = -fy * R[3 + q] / z + fy * y * R[6 + q] / z_2;
+            JX[6 + q] = JX[q] - bf * R[6 + q] / z_2;
+        }
+        JP[0] = x * y / z_2 * fx, JP[1] = -(1 + (x * x / z_2)) * fx, JP[2] = y / z * fx;
+        JP[3] = -1. / z * fx, JP[4] = 0, JP[5] = x / z_2 * fx;
+        JP[6] = (1 + y * y / z_2) * fy, JP[7] = -x * y / z_2 * fy, JP[8] = -x / z * fy;
+        JP[9] = 0, JP[10] = -1. / z * fy, JP[11] = y / z_2 * fy;
+        JP[12] = JP[0] - bf * y / z_2, JP[13] = JP[1] + bf * x / z_2, JP[14] = JP[2];
+        JP[15] = JP[3], JP[16] = 0, JP[17] = JP[5] - bf / z_2;
+    } else {
+        const double *R0 = s.Rcw + (size_t)k * C * 9, *t0 = s.tcw + (size_t)k * C * 3;
+        double Xl[3], pj[6], pr[6];
+        mv3(R0, X, Xl);
+        for (int q = 0; q < 3; ++q) Xl[q] += t0[q];
+        cam_jac(rig, c, Xc, pj);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) pj[q] = -pj[q];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                JX[3 * r + q] = pj[3 * r] * R[q] + pj[3 * r + 1] * R[3 + q] + pj[3 * r + 2] * R[6 + q];
+                pr[3 * r + q] = pj[3 * r] * rig.Rcb[c][q] + pj[3 * r + 1] * rig.Rcb[c][3 + q] + pj[3 * r + 2] * rig.Rcb[c][6 + q];
+            }
+        const double x = Xl[0], y = Xl[1], z = Xl[2];
+        const double se3[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+                JP[6 * r + q] = pr[3 * r] * se3[q] + pr[3 * r + 1] * se3[6 + q] + pr[3 * r + 2] * se3[12 + q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) JX[6 + q] = 0.0;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) JP[12 + q] = 0.0;
+    }
+    double r0, r1;
+    huber0(chi2[e], vis.huber[st ? 1 : 0], r0, r1);
+    const double wi = (double)E.w[e];
+    w = wi * r1;
+    om[0] = -wi * err[2 * e] * r1, om[1] = -wi * err[2 * e + 1] * r1;
+    om[2] = st ? -wi * err3[e] * r1 : 0.0;
+    return st ? 3 : 2;
 }
 
 // EdgeInertial + random-walk errors, one block (threads >= I.n contribute 0 to the fixed-order sum).
@@ -456,6 +604,23 @@ __device__ __forceinline__ int edge_jacobians(const Rig &rig, const State &s, co
     return nr;
 }
 
+// The kind's edge Jacobians / edge error.
+template <bool V>
+__device__ __forceinline__ int kind_jacobians(const Rig &rig, const Kind<V> &kd, const State &s, const Edges &E, int e,
+                                              double delta, double dsqr, double delta_st, double dsqr_st, const double *err,
+                                              const double *err3, const double *chi2, double JX[9], double JP[18],
+                                              double &w, double om[3]) {
+    if constexpr (V) return vis_edge_jacobians(rig, kd, s, E, e, err, err3, chi2, JX, JP, w, om);
+    else return edge_jacobians(rig, s, E, e, delta, dsqr, delta_st, dsqr_st, err, err3, chi2, JX, JP, w, om);
+}
+template <bool V>
+__device__ __forceinline__ double kind_err_edge(const Rig &rig, const Kind<V> &kd, const double *R, const double *t,
+                                                const Edges &E, int e, const double *X, double delta, double dsqr,
+                                                double delta_st, double dsqr_st, double *err, double *err3, double *chi2) {
+    if constexpr (V) return vis_err_edge(rig, kd, R, t, E, e, X, err, err3, chi2);
+    else return mono_err_edge(rig, R, t, E, e, X, delta, dsqr, delta_st, dsqr_st, err, err3, chi2);
+}
+
 // sum over the residual rows r of A[r][ia] B[r][ib] (row-major, row strides lda / ldb): the EdgeStereo row last
 // (zero on an EdgeMono, where the sum is the two-row sum exactly)
 __device__ __forceinline__ double rows3(const double *A, int ia, int lda, const double *B, int ib, int ldb) {
@@ -500,7 +665,8 @@ static_assert(27 * kGrpSlots <= kLdsE, "the slots' diagonal terms fit the edge r
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void land_group(int g, double *sm, const Rig &rig, const State &s, const Edges &E,
+template <bool V>
+__device__ __forceinline__ void land_group(int g, double *sm, const Rig &rig, const Kind<V> &kd, const State &s, const Edges &E,
                                            const Land &L, double lambda, double delta, double dsqr, double delta_st,
                                            double dsqr_st, const double *err, const double *err3, const double *chi2) {
     double *SE = sm, *SX = sm + kLdsE, *SY = SX + kLdsX, *SR = SY + 3 * kGrpLand;
@@ -520,7 +686,7 @@ __device__ __forceinline__ void land_group(int g, double *sm, const Rig &rig, co
     // phase 1: one thread per edge: Jacobians, weight, -W e into LDS (edge-major rows)
     if (tid < ne) {
         double JX[9], JP[18], wt, om[3];
-        edge_jacobians(rig, s, E, e0 + tid, delta, dsqr, delta_st, dsqr_st, err, err3, chi2, JX, JP, wt, om);
+        kind_jacobians<V>(rig, kd, s, E, e0 + tid, delta, dsqr, delta_st, dsqr_st, err, err3, chi2, JX, JP, wt, om);
         double *o = SE + kSE * tid;
 #pragma unroll
         for (int q = 0; q < 18; ++q) o[q] = JP[q];
@@ -739,7 +905,8 @@ __device__ __forceinline__ void land_group(int g, double *sm, const Rig &rig, co
 // thread 0 walks them in edge order (Hll, bl, per slot Hpl and the pose terms), then one thread per slot forms M_s,
 // one thread per keyframe pair the block.
 constexpr int kBigWin = 64;
-__device__ __forceinline__ void land_group_big(int g, double *sm, const Rig &rig, const State &s, const Edges &E,
+template <bool V>
+__device__ __forceinline__ void land_group_big(int g, double *sm, const Rig &rig, const Kind<V> &kd, const State &s, const Edges &E,
                                             const Land &L, double lambda, double delta, double dsqr, double delta_st,
                                             double dsqr_st, const double *err, const double *err3, const double *chi2) {
     double *T = sm;                       // [57][kBigWin]
@@ -765,7 +932,7 @@ __device__ __forceinline__ void land_group_big(int g, double *sm, const Rig &rig
     for (int base = e0; base < e1; base += kBigWin) {
         if (tid < kBigWin && base + tid < e1) {
             double JX[9], JP[18], wt, om[3];
-            edge_jacobians(rig, s, E, base + tid, delta, dsqr, delta_st, dsqr_st, err, err3, chi2, JX, JP, wt, om);
+            kind_jacobians<V>(rig, kd, s, E, base + tid, delta, dsqr, delta_st, dsqr_st, err, err3, chi2, JX, JP, wt, om);
             for (int r = 0; r < 3; ++r) {
                 T[(9 + r) * kBigWin + tid] = rows3(JX, r, 3, om, 0, 1);
                 for (int q = 0; q < 3; ++q) T[(3 * r + q) * kBigWin + tid] = wt * rows3(JX, r, 3, JX, q, 3);
@@ -911,7 +1078,8 @@ __device__ __forceinline__ void imu_contrib_block(int i, double *sm, State s, Im
 // The whole build in one launch: blocks [0, n_imu) the inertial edges' quadratic forms, blocks from n_imu_pad (n_imu
 // rounded up to 8, so the landmark groups keep their XCD-aware order) the landmark groups.  Independent halves, side by
 // side.  Dynamic LDS: kBuildLds.
-__global__ void __launch_bounds__(kGrpEdges) build_all_kernel(Rig rig, State s0, State s1, Edges E, Land L, int n_grp,
+template <bool V>
+__global__ void __launch_bounds__(kGrpEdges) build_all_kernel(Rig rig, Kind<V> kd, State s0, State s1, Edges E, Land L, int n_grp,
                                                               Imu I, int n_imu, int n_imu_pad, double lambda,
                                                               double delta, double dsqr, double delta_st, double dsqr_st,
                                                               double delta_imu, double dsqr_imu, ErrBufs e0, ErrBufs e1,
@@ -938,12 +1106,13 @@ __global__ void __launch_bounds__(kGrpEdges) build_all_kernel(Rig rig, State s0,
     const int g = (bl & 7) * chunk + (bl >> 3);
     if (g >= n_grp) return;
     if (L.grp_w[g] < 0) return;   // build_big_kernel's
-    land_group(g, sm, rig, s, E, L, lambda, delta, dsqr, delta_st, dsqr_st, eb.err, eb.err3, eb.chi2);
+    land_group<V>(g, sm, rig, kd, s, E, L, lambda, delta, dsqr, delta_st, dsqr_st, eb.err, eb.err3, eb.chi2);
 }
 
 // The one-landmark groups past the LDS limits (rare: a landmark with > 256 edges, > 128 slots or > 32 optimisable
 // keyframes), one workgroup each, launched only when the problem has any.
-__global__ void __launch_bounds__(kGrpEdges) build_big_kernel(Rig rig, State s0, State s1, Edges E, Land L,
+template <bool V>
+__global__ void __launch_bounds__(kGrpEdges) build_big_kernel(Rig rig, Kind<V> kd, State s0, State s1, Edges E, Land L,
                                                               const int *big, int n_big, double lambda, double delta,
                                                               double dsqr, double delta_st, double dsqr_st, ErrBufs e0,
                                                               ErrBufs e1, const LmCtl *ctl) {
@@ -953,7 +1122,7 @@ __global__ void __launch_bounds__(kGrpEdges) build_big_kernel(Rig rig, State s0,
     const int bi = role_buf(ctl, 0);
     const State s = bi ? s1 : s0;
     const ErrBufs eb = bi ? e1 : e0;
-    land_group_big(big[blockIdx.x], sm, rig, s, E, L, lambda, delta, dsqr, delta_st, dsqr_st, eb.err, eb.err3, eb.chi2);
+    land_group_big<V>(big[blockIdx.x], sm, rig, kd, s, E, L, lambda, delta, dsqr, delta_st, dsqr_st, eb.err, eb.err3, eb.chi2);
 }
 
 // ---- trial: the reduced system, assembled per block -------------------------------------------------------
@@ -1094,6 +1263,20 @@ __device__ __forceinline__ void kf_trial_pose(const Rig &rig, const State &a, co
     mm3(rig.Rcb[c], Rbw, Rc);
     mv3(rig.Rcb[c], tbw, tc);
     for (int q = 0; q < 3; ++q) tc[q] += rig.tcb[c][q];
+}
+
+// The kind's keyframe update.  Visual: VertexSE3Expmap::oplusImpl, exp(u) * T with u = (omega, upsilon); the new q
+// comes back in Rn[0..3] (the rest of the slot zero) and the new t in twb.
+template <bool V>
+__device__ __forceinline__ void kind_trial_pose(const Rig &rig, const Kind<V> &kd, const State &a, const double *u, int k,
+                                                int c, bool norm, double Rn[9], double twb[3], double Rc[9], double tc[3]) {
+    if constexpr (V) {
+        se3_oplus(u, a.Rwb + 9 * k, a.twb + 3 * k, Rn, twb);
+        for (int q = 4; q < 9; ++q) Rn[q] = 0.0;
+        vis_cam_pose(rig, kd, c, Rn, twb, Rc, tc);
+    } else {
+        kf_trial_pose(rig, a, u, k, c, norm, Rn, twb, Rc, tc);
+    }
 }
 
 // ---- trial: block LDL^T of the reduced system (one workgroup, 16x16 f64 MFMA tiles) -------------
@@ -1454,7 +1637,8 @@ struct ErrTrial {
     const int16_t *e_lkf;    // [E] the edge keyframe's index in its group's list, -1 fixed
     const int *lkf_kf;       // per group (at Land::grp_kf[g]) its keyframes
 };
-__global__ void __launch_bounds__(256) err_kernel(int n_grp, int lead, int has_imu, Rig rig, State s0, State s1, Edges E,
+template <bool V>
+__global__ void __launch_bounds__(256) err_kernel(int n_grp, int lead, int has_imu, Rig rig, Kind<V> kd, State s0, State s1, Edges E,
                                                   Land L, Red R, ErrTrial T, double delta, double dsqr, double delta_st,
                                                   double dsqr_st, ErrBufs e0, ErrBufs e1, double *partial,
                                                   double *scale_partial, Imu I, double delta_imu, double dsqr_imu,
@@ -1479,7 +1663,7 @@ __global__ void __launch_bounds__(256) err_kernel(int n_grp, int lead, int has_i
                 for (int t = tid; t < T.n_opt * C; t += blockDim.x) {
                     const int k = t / C, c = t - k * C;
                     double Rn[9], twb[3], Rc[9], tc[3];
-                    kf_trial_pose(rig, a, T.xp + R.offP[k], k, c, norm, Rn, twb, Rc, tc);
+                    kind_trial_pose<V>(rig, kd, a, T.xp + R.offP[k], k, c, norm, Rn, twb, Rc, tc);
                     for (int q = 0; q < 9; ++q) s.Rcw[((size_t)k * C + c) * 9 + q] = Rc[q];
                     for (int q = 0; q < 3; ++q) s.tcw[((size_t)k * C + c) * 3 + q] = tc[q];
                     if (c == 0) {
@@ -1540,7 +1724,7 @@ __global__ void __launch_bounds__(256) err_kernel(int n_grp, int lead, int has_i
         for (int t = tid - kGrpLand; t < w * C; t += blockDim.x - kGrpLand) {
             const int la = t / C, c = t - la * C, k = T.lkf_kf[L.grp_kf[g] + la];
             double Rn[9], twb[3];
-            kf_trial_pose(rig, a, T.xp + R.offP[k], k, c, norm, Rn, twb, PS + 12 * t, PS + 12 * t + 9);
+            kind_trial_pose<V>(rig, kd, a, T.xp + R.offP[k], k, c, norm, Rn, twb, PS + 12 * t, PS + 12 * t + 9);
         }
     }
     __syncthreads();
@@ -1558,10 +1742,10 @@ __global__ void __launch_bounds__(256) err_kernel(int n_grp, int lead, int has_i
             for (int q = 0; q < 3; ++q) tc[q] = o[9 + q];
         } else {   // the scalar group: per edge
             double Rn[9], twb[3];
-            kf_trial_pose(rig, a, T.xp + R.offP[E.kf[e]], E.kf[e], cam, norm, Rn, twb, Rc, tc);
+            kind_trial_pose<V>(rig, kd, a, T.xp + R.offP[E.kf[e]], E.kf[e], cam, norm, Rn, twb, Rc, tc);
         }
-        r0 += mono_err_edge(rig, Rc, tc, E, e, X + 3 * (E.pt[e] - p0), delta, dsqr, delta_st, dsqr_st, eb.err, eb.err3,
-                            eb.chi2);
+        r0 += kind_err_edge<V>(rig, kd, Rc, tc, E, e, X + 3 * (E.pt[e] - p0), delta, dsqr, delta_st, dsqr_st, eb.err,
+                               eb.err3, eb.chi2);
     }
     const double t = block_reduce_sum(r0, sh);
     if (tid == 0) partial[g] = t;
@@ -1576,6 +1760,9 @@ __global__ void __launch_bounds__(256) err_kernel(int n_grp, int lead, int has_i
 // (Optimizer.cc:3282-3311: EdgeMono chi2 > 5.991, or > 1.5 * 5.991 when the point's trackDepth < 10, or a
 // non-positive depth; EdgeStereo chi2 > 7.815) at the final state, written in the caller's edge order with
 // the chi2, and the points in the caller's order; the host reads one staging block.
+// The visual kind: chi2 > 5.991 (7.815 on a stereo edge) || !isDepthPositive on every edge (Optimizer.cc:1729-1783), the
+// depth being the z of the edge's own camera.
+template <bool V>
 __global__ void epilogue_kernel(Rig rig, State s0, State s1, size_t n_state, Edges E, const int *perm_edge,
                                 int n_mono_all, const float *track_depth, const int *perm_pt, int n_pts, uint8_t *flags,
                                 double *chi2_out, double *pts_out, const double *chi2_0, const double *chi2_1,
@@ -1593,7 +1780,13 @@ __global__ void epilogue_kernel(Rig rig, State s0, State s1, size_t n_state, Edg
         const int e = q, o = perm_edge[e];
         const double c2 = chi2[e];
         uint8_t f;
-        if (o >= n_mono_all) {
+        if constexpr (V) {
+            const int k = E.kf[e], c = E.cam[e], p = E.pt[e], C = rig.n_cams;
+            const double *R = s.Rcw + ((size_t)k * C + c) * 9, *t = s.tcw + ((size_t)k * C + c) * 3;
+            const double *X = s.pts + 3 * (size_t)p;
+            const bool depth_pos = (R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2]) > 0.0;
+            f = (c2 > (o >= n_mono_all ? 7.815 : 5.991) || !depth_pos) ? 1 : 0;
+        } else if (o >= n_mono_all) {
             f = c2 > 7.815f ? 1 : 0;
         } else {
             const int k = E.kf[e], c = E.cam[e], p = E.pt[e], C = rig.n_cams;
@@ -1643,6 +1836,85 @@ __global__ void mono_jac_kernel(Rig rig, State s, Edges E, double *jx, double *j
             jp[18 * e + 6 * r + q] = pr[3 * r] * se3[q] + pr[3 * r + 1] * se3[6 + q] + pr[3 * r + 2] * se3[12 + q];
 }
 
+// The visual kind's Jacobians for parity, in the same layout.
+__global__ void vis_jac_kernel(Rig rig, Kind<true> kd, State s, Edges E, const double *err, const double *err3,
+                               const double *chi2, double *jx, double *jp) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E.n) return;
+    double JX[9], JP[18], w, om[3];
+    vis_edge_jacobians(rig, kd, s, E, e, err, err3, chi2, JX, JP, w, om);
+    for (int q = 0; q < 9; ++q) jx[9 * (size_t)e + q] = JX[q];
+    for (int q = 0; q < 18; ++q) jp[18 * (size_t)e + q] = JP[q];
+}
+
+// Every keyframe's per-camera Rcw / tcw from its (q, t) (set_problem: the same arithmetic as a trial's).
+__global__ void vis_cams_kernel(Rig rig, Kind<true> kd, State s, int n_kf) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x, C = rig.n_cams;
+    if (q >= n_kf * C) return;
+    const int k = q / C, c = q - k * C;
+    double Rc[9], tc[3];
+    vis_cam_pose(rig, kd, c, s.Rwb + 9 * k, s.twb + 3 * k, Rc, tc);
+    for (int i = 0; i < 9; ++i) s.Rcw[(size_t)q * 9 + i] = Rc[i];
+    for (int i = 0; i < 3; ++i) s.tcw[(size_t)q * 3 + i] = tc[i];
+}
+
+// computeLambdaInit (optimization_algorithm_levenberg.cpp:171-185): max |H(j,j)| over the active vertices at the
+// current errors -- block k < n_opt: keyframe k's sum w JP^T JP diagonal over its edges (kf_edge, ascending: a fixed
+// order); block n_opt + g: the landmarks of group g, one thread each (sum w JX^T JX diagonal in edge order) -- one
+// maximum per block into `out`.  Runs at the first step of an optimize() whose lambda_init is <= 0.
+__global__ void __launch_bounds__(256) vis_diag_kernel(Rig rig, Kind<true> kd, State s0, Edges E, Land L, int n_opt,
+                                                       const int *kf_edge_start, const int *kf_edge, ErrBufs eb,
+                                                       double *out, const LmCtl *c) {
+    __shared__ double sh[8];
+    __shared__ double mx[256];
+    if (!c->init_pending || c->lambda_init > 0) return;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    double m = 0;
+    if (b < n_opt) {
+        double d[6] = {0, 0, 0, 0, 0, 0};
+        for (int q = kf_edge_start[b] + tid; q < kf_edge_start[b + 1]; q += blockDim.x) {
+            double JX[9], JP[18], w, om[3];
+            vis_edge_jacobians(rig, kd, s0, E, kf_edge[q], eb.err, eb.err3, eb.chi2, JX, JP, w, om);
+            for (int j = 0; j < 6; ++j) d[j] += w * rows3(JP, j, 6, JP, j, 6);
+        }
+        for (int j = 0; j < 6; ++j) {
+            const double t = block_reduce_sum(d[j], sh);
+            m = fmax(m, fabs(t));
+        }
+        if (tid == 0) out[b] = m;
+        return;
+    }
+    const int g = b - n_opt, p0 = L.grp_pt[g], np = L.grp_pt[g + 1] - p0;
+    for (int pl = tid; pl < np; pl += blockDim.x) {
+        double d[3] = {0, 0, 0};
+        for (int e = L.edge_start[p0 + pl]; e < L.edge_start[p0 + pl + 1]; ++e) {
+            double JX[9], JP[18], w, om[3];
+            vis_edge_jacobians(rig, kd, s0, E, e, eb.err, eb.err3, eb.chi2, JX, JP, w, om);
+            for (int j = 0; j < 3; ++j) d[j] += w * rows3(JX, j, 3, JX, j, 3);
+        }
+        m = fmax(m, fmax(fabs(d[0]), fmax(fabs(d[1]), fabs(d[2]))));
+    }
+    mx[tid] = m;
+    __syncthreads();
+    if (tid == 0) {
+        for (int q = 1; q < (int)blockDim.x; ++q) m = fmax(m, mx[q]);
+        out[b] = m;
+    }
+}
+// lambda = tau * max (tau = 1e-5, g2o's default), the maximum of the blocks' maxima.
+__global__ void __launch_bounds__(256) vis_lambda_kernel(const double *part, int n, LmCtl *c) {
+    __shared__ double mx[256];
+    if (!c->init_pending || c->lambda_init > 0) return;
+    double m = 0;
+    for (int q = threadIdx.x; q < n; q += blockDim.x) m = fmax(m, part[q]);
+    mx[threadIdx.x] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < (int)blockDim.x; ++q) m = fmax(m, mx[q]);
+        c->lambda = c->lambda_init = 1e-5 * m;
+    }
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1683,6 +1955,11 @@ struct LbaDeviceProblem {
     double *d_S = nullptr, *d_coef = nullptr, *d_x = nullptr, *d_scratch = nullptr;
     int *d_fail = nullptr;
     double *d_bb = nullptr;    // the trial's copy of b (all-reduced with the packed system when sharded)
+    // the visual kind (omv_vba): its constants, Huber deltas and level mask, and computeLambdaInit's work lists
+    Kind<true> vis{};
+    double *d_huber = nullptr, *d_diag = nullptr;   // [2]; [n_opt + n_lgrp] the blocks' diagonal maxima
+    uint8_t *d_level = nullptr;                     // [E] device order
+    int *d_kf_edge_start = nullptr, *d_kf_edge = nullptr;   // per optimisable keyframe its edges (device order, ascending)
     size_t state_doubles() const { return (size_t)n_kf * (24 + 12 * rig.n_cams) + 3 * (size_t)n_pts; }
 };
 
@@ -1705,6 +1982,7 @@ struct omv_lba : LbaDeviceProblem {
     hipGraphExec_t step4e_exec[2] = {nullptr, nullptr};
     bool timing = false;       // direct launches with per-stage events instead of the captured step
     bool host_lm = false;      // force the host-driven LM loop (parity checks of the device control)
+    bool visual = false;       // an omv_vba handle: the visual kind of every kernel that depends on the parameterisation
     int rank = 0, world = 1;   // landmark sharding (omv_lba_set_comm)
     omv_allreduce_fn allreduce = nullptr;
     void *ar_ctx = nullptr;
@@ -1862,11 +2140,10 @@ omv_status omv_lba_create(int max_kf, int max_cams, int max_pts, int max_mono, i
                 hipFuncSetAttribute((const void *)ldlt_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)kLdltLds) == hipSuccess;
     // the landmark groups of the build take ~77 KB of LDS (two workgroups per CU)
-    if (hipFuncSetAttribute((const void *)build_all_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLds) !=
-            hipSuccess ||
-        hipFuncSetAttribute((const void *)build_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLds) !=
-            hipSuccess)
-        return OMV_ERR_HIP;
+    for (const void *k : {(const void *)build_all_kernel<false>, (const void *)build_big_kernel<false>,
+                          (const void *)build_all_kernel<true>, (const void *)build_big_kernel<true>})
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBuildLds) != hipSuccess)
+            return OMV_ERR_HIP;
     (void)hipGetLastError();
     *out = h.release();
     return OMV_OK;
@@ -1910,14 +2187,19 @@ static omv_status launch_errors(omv_lba *h, const State &s0, const State &s1, co
     const ErrTrial T{xp, n_acc % 3 == 2 ? 1 : 0, h->d_bb, lambda, h->d_offV, h->d_offG, h->d_offA, h->n_opt, h->d_e_lkf,
                      h->d_lkf_kf};
     const size_t lds = (3 * (size_t)kGrpLand + 12 * (size_t)kGrpW * h->rig.n_cams) * sizeof(double);
-    if (blocks > 0)
-        err_kernel<<<blocks, 256, lds, h->stream>>>(ng, lead, h->imu_here ? 1 : 0, h->rig, s0, s1, h->E, h->L, h->R, T,
-                                                    h->delta_mono, h->dsqr_mono, h->delta_st, h->dsqr_st, h->eb(0),
-                                                    one_buffer ? h->eb(0) : h->eb(1),
-                                                    init_partials ? h->d_partial0 : h->d_partial, h->d_scale_partial,
-                                                    h->I, h->delta_imu, h->dsqr_imu,
-                                                    init_partials ? h->d_imu_partial0 : h->d_imu_partial, ctl, gate, role,
-                                                    reset);
+    auto launch = [&](auto kernel, auto kd) {
+        kernel<<<blocks, 256, lds, h->stream>>>(ng, lead, h->imu_here ? 1 : 0, h->rig, kd, s0, s1, h->E, h->L, h->R, T,
+                                                h->delta_mono, h->dsqr_mono, h->delta_st, h->dsqr_st, h->eb(0),
+                                                one_buffer ? h->eb(0) : h->eb(1),
+                                                init_partials ? h->d_partial0 : h->d_partial, h->d_scale_partial, h->I,
+                                                h->delta_imu, h->dsqr_imu,
+                                                init_partials ? h->d_imu_partial0 : h->d_imu_partial, ctl, gate, role,
+                                                reset);
+    };
+    if (blocks > 0) {
+        if (h->visual) launch(err_kernel<true>, h->vis);
+        else launch(err_kernel<false>, Kind<false>{});
+    }
     return hipGetLastError() == hipSuccess ? OMV_OK : OMV_ERR_HIP;
 }
 static int n_grp_err(const omv_lba *h) { return h->n_mono > 0 ? h->plan.n_lgrp : 0; }
@@ -1967,7 +2249,11 @@ static omv_status lba_eval(omv_lba *h, double *mono_err, double *mono_jx, double
     const bool jac = mono_jx || mono_jp || st_jx || st_jp;
     if (jac && E > 0) {
         if (!tmp.alloc(&d_jx, 9 * (size_t)E) || !tmp.alloc(&d_jp, 18 * (size_t)E)) return OMV_ERR_HIP;
-        mono_jac_kernel<<<(E + 255) / 256, 256, 0, h->stream>>>(h->rig, s, h->E, d_jx, d_jp);
+        if (h->visual)
+            vis_jac_kernel<<<(E + 255) / 256, 256, 0, h->stream>>>(h->rig, h->vis, s, h->E, h->d_err, h->d_err3, h->d_chi2,
+                                                                   d_jx, d_jp);
+        else
+            mono_jac_kernel<<<(E + 255) / 256, 256, 0, h->stream>>>(h->rig, s, h->E, d_jx, d_jp);
     }
     HIP_OK(hipStreamSynchronize(h->stream));
     std::vector<double> err(2 * (size_t)E), err3(E), e9(10 * (size_t)h->n_imu);
@@ -2021,14 +2307,18 @@ static omv_status lba_enqueue_epilogue(omv_lba *h, bool want_chi2);
 static omv_status launch_build(omv_lba *h, const State &A, const State &B, const LmCtl *c, double lambda) {
     const int n_imu = h->imu_here ? h->n_imu : 0, n_imu_pad = (n_imu + 7) & ~7;
     const int grid = n_imu_pad + (h->plan.n_lgrp > 0 ? omv::xcd_grid(h->plan.n_lgrp) : 0);
-    if (grid > 0)
-        build_all_kernel<<<grid, kGrpEdges, kBuildLds, h->stream>>>(
-            h->rig, A, B, h->E, h->L, h->plan.n_lgrp, h->I, n_imu, n_imu_pad, lambda, h->delta_mono, h->dsqr_mono,
-            h->delta_st, h->dsqr_st, h->delta_imu, h->dsqr_imu, h->eb(0), h->eb(1), h->d_imu_contrib, c);
-    if (h->plan.n_big > 0)
-        build_big_kernel<<<h->plan.n_big, kGrpEdges, kBuildLds, h->stream>>>(h->rig, A, B, h->E, h->L, h->d_big, h->plan.n_big,
-                                                                        lambda, h->delta_mono, h->dsqr_mono, h->delta_st,
-                                                                        h->dsqr_st, h->eb(0), h->eb(1), c);
+    auto launch = [&](auto all_kernel, auto big_kernel, auto kd) {
+        if (grid > 0)
+            all_kernel<<<grid, kGrpEdges, kBuildLds, h->stream>>>(
+                h->rig, kd, A, B, h->E, h->L, h->plan.n_lgrp, h->I, n_imu, n_imu_pad, lambda, h->delta_mono, h->dsqr_mono,
+                h->delta_st, h->dsqr_st, h->delta_imu, h->dsqr_imu, h->eb(0), h->eb(1), h->d_imu_contrib, c);
+        if (h->plan.n_big > 0)
+            big_kernel<<<h->plan.n_big, kGrpEdges, kBuildLds, h->stream>>>(h->rig, kd, A, B, h->E, h->L, h->d_big,
+                                                                      h->plan.n_big, lambda, h->delta_mono, h->dsqr_mono,
+                                                                      h->delta_st, h->dsqr_st, h->eb(0), h->eb(1), c);
+    };
+    if (h->visual) launch(build_all_kernel<true>, build_big_kernel<true>, h->vis);
+    else launch(build_all_kernel<false>, build_big_kernel<false>, Kind<false>{});
     HIP_OK(hipGetLastError());
     return OMV_OK;
 }
@@ -2062,6 +2352,12 @@ static omv_status lba_step(omv_lba *h, hipEvent_t *ev) {
     const State &A = h->st[0], &B = h->st[1];
     omv_status rs;
     if (ev) HIP_OK(hipEventRecord(ev[0], st));
+    if (h->visual) {   // computeLambdaInit at the first step of an optimize() without a user lambda (gated on the device)
+        const int nd = h->n_opt + h->plan.n_lgrp;
+        vis_diag_kernel<<<nd, 256, 0, st>>>(h->rig, h->vis, A, h->E, h->L, h->n_opt, h->d_kf_edge_start, h->d_kf_edge,
+                                            h->eb(0), h->d_diag, c);
+        vis_lambda_kernel<<<1, 256, 0, st>>>(h->d_diag, nd, c);
+    }
     if ((rs = launch_build(h, A, B, c, 0.0)) != OMV_OK) return rs;
     if (ev) HIP_OK(hipEventRecord(ev[1], st));
     if ((rs = launch_assemble(h, 0.0, c)) != OMV_OK) return rs;
@@ -2348,11 +2644,14 @@ static omv_status lba_enqueue_epilogue(omv_lba *h, bool want_chi2) {
     uint8_t *d_flags = (uint8_t *)(d_pts + 3 * (size_t)P);
     double *d_chi2 = d_pts + 3 * (size_t)P + fl;
     const int n = std::max(std::max(E, P), (int)head);
-    epilogue_kernel<<<(n + 255) / 256, 256, 0, st>>>(h->rig, s, h->st[1], h->state_doubles(), h->E, h->d_perm_edge,
-                                                     h->n_mono_all, h->d_track_depth,
-                                                     h->d_perm_pt, P, d_flags, want_chi2 ? d_chi2 : nullptr, d_pts,
-                                                     h->d_chi2, h->d_chi2_b, h->host_lm ? nullptr : h->d_ctl,
-                                                     h->d_stage, (int)head);
+    auto launch = [&](auto kernel) {
+        kernel<<<(n + 255) / 256, 256, 0, st>>>(h->rig, s, h->st[1], h->state_doubles(), h->E, h->d_perm_edge,
+                                                h->n_mono_all, h->d_track_depth, h->d_perm_pt, P, d_flags,
+                                                want_chi2 ? d_chi2 : nullptr, d_pts, h->d_chi2, h->d_chi2_b,
+                                                h->host_lm ? nullptr : h->d_ctl, h->d_stage, (int)head);
+    };
+    if (h->visual) launch(epilogue_kernel<true>);
+    else launch(epilogue_kernel<false>);
     HIP_OK(hipGetLastError());
     const size_t bytes = (head + 3 * (size_t)P + fl + (want_chi2 ? (size_t)E : 0)) * sizeof(double);
     HIP_OK(hipMemcpyAsync(h->h_stage, h->d_stage, bytes, hipMemcpyDeviceToHost, st));
@@ -2443,6 +2742,7 @@ omv_status omv_lba_reset(omv_lba *h) {
 
 omv_status omv_lba_set_comm(omv_lba *h, int rank, int world, omv_allreduce_fn allreduce, void *ctx) {
     if (!h || world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce)) return OMV_ERR_ARG;
+    if (h->visual) return OMV_ERR_ARG;   // the visual kind is single-rank
     h->rank = rank, h->world = world, h->allreduce = allreduce, h->ar_ctx = ctx;
     return OMV_OK;
 }
@@ -2545,5 +2845,214 @@ omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda,
     for (int l = 0; l < B.n_lev; ++l) plan[4 + l] = lev[l + 1] - lev[l];
     return OMV_OK;
 }
+
+}  // extern "C"
+
+// ---- omv_vba: the visual kind's C ABI ------------------------------------------------------------------------------
+// An omv_vba is an omv_lba created with `visual`: the plan, the arena, the LM driver, the captured steps and the
+// epilogue are the inertial handle's; what follows translates the problem, uploads the kind's own few arrays and reads
+// the result in its own layout.
+static omv_lba *core(omv_vba *h) { return reinterpret_cast<omv_lba *>(h); }
+
+// The visual problem as the planner's input: the same edges, no inertial edge, 6-row keyframe blocks only; q in the
+// first four doubles of the keyframe's Rwb slot, t in twb, the per-camera poses left for vis_cams_kernel.
+struct VbaTranslated {
+    std::vector<double> Rcb, tcb, Rbc, tbc, Rwb, Rcw, tcw, zero3;
+    std::vector<uint8_t> kf_imu;
+    omv_lba_problem lp{};
+};
+static void vba_translate(const omv_vba_problem &p, VbaTranslated &t) {
+    const size_t C = p.n_cams, K = p.n_kf;
+    t.Rcb.assign(9 * C, 0.0), t.tcb.assign(p.t_c0, p.t_c0 + 3 * C), t.Rbc.assign(9 * C, 0.0), t.tbc.assign(3 * C, 0.0);
+    for (size_t c = 0; c < C; ++c) {
+        double *R = &t.Rcb[9 * c], *Rt = &t.Rbc[9 * c];
+        q_to_mat(p.q_c0 + 4 * c, R);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) Rt[3 * i + j] = R[3 * j + i];
+        for (int i = 0; i < 3; ++i)
+            t.tbc[3 * c + i] = -(Rt[3 * i] * t.tcb[3 * c] + Rt[3 * i + 1] * t.tcb[3 * c + 1] + Rt[3 * i + 2] * t.tcb[3 * c + 2]);
+    }
+    t.Rwb.assign(9 * K, 0.0), t.Rcw.assign(9 * K * C, 0.0), t.tcw.assign(3 * K * C, 0.0), t.zero3.assign(3 * K, 0.0);
+    for (size_t k = 0; k < K; ++k) std::copy(p.q_cw + 4 * k, p.q_cw + 4 * k + 4, &t.Rwb[9 * k]);
+    t.kf_imu.assign(K, 0);
+    omv_lba_problem &lp = t.lp;
+    lp.n_cams = p.n_cams, lp.cam = p.cam, lp.cam_model = p.cam_model;
+    lp.Rcb = t.Rcb.data(), lp.tcb = t.tcb.data(), lp.Rbc = t.Rbc.data(), lp.tbc = t.tbc.data();
+    lp.n_kf = p.n_kf, lp.n_opt = p.n_opt, lp.kf_imu = t.kf_imu.data();
+    lp.Rwb = t.Rwb.data(), lp.twb = p.t_cw, lp.Rcw = t.Rcw.data(), lp.tcw = t.tcw.data();
+    lp.vel = lp.bg = lp.ba = t.zero3.data();
+    lp.n_pts = p.n_pts, lp.pts = p.pts, lp.pt_track_depth = nullptr;
+    lp.n_mono = p.n_mono, lp.mono_pt = p.mono_pt, lp.mono_kf = p.mono_kf, lp.mono_cam = p.mono_cam;
+    lp.mono_obs = p.mono_obs, lp.mono_inv_sigma2 = p.mono_inv_sigma2;
+    lp.n_imu = 0;
+    lp.n_stereo = p.n_stereo, lp.stereo_pt = p.stereo_pt, lp.stereo_kf = p.stereo_kf, lp.stereo_obs = p.stereo_obs;
+    lp.stereo_inv_sigma2 = p.stereo_inv_sigma2, lp.bf = (float)p.bf;
+}
+
+// The kind's own device arrays after upload_problem: Huber deltas, levels (all active), the keyframes' edge lists for
+// computeLambdaInit, and every keyframe's per-camera pose derived on the device into all three state buffers.
+static omv_status vba_upload(omv_lba *h, const omv_vba_problem *p) {
+    const LbaPlan &pl = h->plan;
+    const int E = h->n_mono, nb = h->n_opt;
+    std::vector<int> start(nb + 1, 0), list;
+    for (int e = 0; e < E; ++e)
+        if (pl.e_kf[e] < nb) ++start[pl.e_kf[e] + 1];
+    for (int k = 0; k < nb; ++k) start[k + 1] += start[k];
+    list.resize(start[nb]);
+    {
+        std::vector<int> at(start.begin(), start.end() - 1);
+        for (int e = 0; e < E; ++e)
+            if (pl.e_kf[e] < nb) list[at[pl.e_kf[e]]++] = e;
+    }
+    omv::DeviceArena &mem = h->prob;
+    if (!mem.alloc(&h->d_huber, 2) || !mem.alloc(&h->d_level, (size_t)E) || !mem.alloc(&h->d_diag, (size_t)nb + pl.n_lgrp) ||
+        !mem.alloc(&h->d_kf_edge_start, start.size()) || !mem.alloc(&h->d_kf_edge, list.size()))
+        return OMV_ERR_HIP;
+    HIP_OK(hipMemset(h->d_level, 0, std::max(E, 1)));
+    HIP_OK(hipMemset(h->d_huber, 0, 2 * sizeof(double)));
+    HIP_OK(hipMemcpy(h->d_kf_edge_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (!list.empty()) HIP_OK(hipMemcpy(h->d_kf_edge, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
+    Kind<true> &v = h->vis;
+    for (int c = 0; c < p->n_cams; ++c)
+        for (int q = 0; q < 4; ++q) v.qc0[c][q] = p->q_c0[4 * c + q];
+    v.fx = p->fx, v.fy = p->fy, v.cx = p->cx, v.cy = p->cy, v.bf = p->bf;
+    v.huber = h->d_huber, v.level = h->d_level;
+    const int n = h->n_kf * p->n_cams;
+    vis_cams_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(h->rig, v, h->st[2], h->n_kf);
+    HIP_OK(hipGetLastError());
+    for (int b = 0; b < 2; ++b)
+        HIP_OK(hipMemcpyAsync(h->st[b].Rwb, h->st[2].Rwb, h->state_doubles() * sizeof(double), hipMemcpyDeviceToDevice,
+                              h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return OMV_OK;
+}
+
+static omv_status vba_set_huber(omv_lba *h, const omv_vba_opts *o) {
+    if (!(o->huber_mono >= 0.0) || !(o->huber_stereo >= 0.0)) return OMV_ERR_ARG;
+    const double d[2] = {o->huber_mono, o->huber_stereo};
+    HIP_OK(hipMemcpyAsync(h->d_huber, d, sizeof d, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));   // `d` is this frame's
+    return OMV_OK;
+}
+
+extern "C" {
+
+omv_status omv_vba_create(int max_kf, int max_cams, int max_pts, int max_edges, omv_vba **out) {
+    if (!out) return OMV_ERR_ARG;
+    omv_lba *h = nullptr;
+    const omv_status rs = omv_lba_create(max_kf, max_cams, max_pts, max_edges, 0, &h);
+    if (rs != OMV_OK) return rs;
+    h->visual = true;
+    *out = reinterpret_cast<omv_vba *>(h);
+    return OMV_OK;
+}
+
+omv_status omv_vba_destroy(omv_vba *h) { return omv_lba_destroy(core(h)); }
+
+omv_status omv_vba_set_problem(omv_vba *hv, const omv_vba_problem *p) {
+    omv_lba *h = core(hv);
+    if (!h || !h->visual || !p || p->n_cams < 1 || p->n_kf < 1 || p->n_opt < 1 || p->n_opt > p->n_kf || p->n_pts < 0 ||
+        p->n_mono < 0 || p->n_stereo < 0 || !p->cam || !p->q_c0 || !p->t_c0 || !p->q_cw || !p->t_cw ||
+        (p->n_pts > 0 && !p->pts) ||
+        (p->n_mono > 0 && (!p->mono_pt || !p->mono_kf || !p->mono_cam || !p->mono_obs || !p->mono_inv_sigma2)))
+        return OMV_ERR_ARG;
+    if (p->n_kf > h->max_kf || p->n_cams > h->max_cams || p->n_pts > h->max_pts ||
+        (long long)p->n_mono + p->n_stereo > h->max_mono)
+        return OMV_ERR_CAPACITY;
+    VbaTranslated t;
+    vba_translate(*p, t);
+    LbaPlan plan;
+    const LbaLimits lim{h->max_kf, h->max_cams, h->max_pts, h->max_mono, h->max_imu};
+    const omv_status planned = plan_lba(t.lp, 0, 1, lim, h->lds_ok, plan);
+    if (planned != OMV_OK) return planned;
+    free_problem(h);
+    h->plan = std::move(plan);
+    omv_status rs = upload_problem(h, &t.lp);
+    if (rs == OMV_OK) rs = vba_upload(h, p);
+    if (rs != OMV_OK) free_problem(h);
+    return rs;
+}
+
+omv_status omv_vba_set_levels(omv_vba *hv, const uint8_t *mono_level, const uint8_t *stereo_level) {
+    omv_lba *h = core(hv);
+    if (!h || !h->visual || !has_problem(h)) return OMV_ERR_ARG;
+    const int E = h->n_mono, EM = h->n_mono_all;
+    std::vector<uint8_t> lv(std::max(E, 1), 0);
+    for (int e = 0; e < E; ++e) {
+        const int o = h->plan.perm_edge[e];
+        const uint8_t *src = o < EM ? mono_level : stereo_level;
+        lv[e] = src && src[o < EM ? o : o - EM] ? 1 : 0;
+    }
+    HIP_OK(hipMemcpy(h->d_level, lv.data(), E, hipMemcpyHostToDevice));
+    return OMV_OK;
+}
+
+omv_status omv_vba_optimize(omv_vba *hv, const omv_vba_opts *o, omv_vba_problem *p, omv_vba_result *r) {
+    omv_lba *h = core(hv);
+    if (!h || !h->visual || !o || !p || !r || !has_problem(h) || o->max_trials < 1 || !p->q_cw || !p->t_cw ||
+        (h->n_pts > 0 && !p->pts) || p->n_kf != h->n_kf || p->n_pts != h->n_pts)
+        return OMV_ERR_ARG;
+    omv_status rs = vba_set_huber(h, o);
+    if (rs != OMV_OK) return rs;
+    const omv_lba_opts lo{o->iterations, o->lambda_init, o->max_trials, 1};
+    omv_lba_result lr{};
+    lr.mono_chi2 = r->mono_chi2, lr.stereo_chi2 = r->stereo_chi2;
+    for (double &m : h->stage_ms) m = 0;
+    if ((rs = lba_optimize_device(h, &lo, &lr)) != OMV_OK) return rs;
+    const LmCtl &c = *h->h_ctl;
+    r->err = c.err0, r->err_end = c.errors_chi, r->iterations = c.its, r->trials = c.trials, r->lambda = c.lambda;
+    r->lambda_init = c.lambda_init;
+    // the epilogue's staging block: [state head | points | flags | chi2] in the caller's order
+    const bool want_chi2 = r->mono_chi2 || r->stereo_chi2;
+    if (!lba_epilogue_ok(h)) return OMV_ERR_HIP;
+    if (!h->epi_ready || (want_chi2 && !h->epi_chi2)) {
+        if ((rs = lba_enqueue_epilogue(h, want_chi2)) != OMV_OK) return rs;
+        HIP_OK(hipStreamSynchronize(h->stream));
+    }
+    h->epi_ready = false;
+    const int K = h->n_kf, P = h->n_pts, E = h->n_mono, EM = h->n_mono_all, ES = h->n_stereo_all;
+    const size_t head = (size_t)(h->st[0].pts - h->st[0].Rwb);
+    const double *hs = h->h_stage;
+    for (int k = 0; k < K; ++k) {
+        std::memcpy(p->q_cw + 4 * (size_t)k, hs + 9 * (size_t)k, 4 * sizeof(double));
+        std::memcpy(p->t_cw + 3 * (size_t)k, hs + 9 * (size_t)K + 3 * (size_t)k, 3 * sizeof(double));
+    }
+    if (P > 0) std::memcpy(p->pts, hs + head, 3 * sizeof(double) * (size_t)P);
+    const uint8_t *hf = (const uint8_t *)(hs + head + 3 * (size_t)P);
+    const double *hc = hs + head + 3 * (size_t)P + ((size_t)E + 7) / 8;
+    if (r->mono_chi2) std::memcpy(r->mono_chi2, hc, sizeof(double) * EM);
+    if (r->stereo_chi2) std::memcpy(r->stereo_chi2, hc + EM, sizeof(double) * ES);
+    if (r->mono_outlier) std::memcpy(r->mono_outlier, hf, EM);
+    if (r->stereo_outlier) std::memcpy(r->stereo_outlier, hf + EM, ES);
+    return OMV_OK;
+}
+
+omv_status omv_vba_evaluate(omv_vba *hv, const omv_vba_opts *o, double *mono_err, double *mono_jxi, double *mono_jxj,
+                            double *stereo_err, double *stereo_jxi, double *stereo_jxj) {
+    omv_lba *h = core(hv);
+    if (!h || !h->visual || !o || !has_problem(h)) return OMV_ERR_ARG;
+    const omv_status rs = vba_set_huber(h, o);
+    if (rs != OMV_OK) return rs;
+    return lba_eval(h, mono_err, mono_jxi, mono_jxj, nullptr, stereo_err, stereo_jxi, stereo_jxj);
+}
+
+omv_status omv_vba_reset(omv_vba *hv) {
+    omv_lba *h = core(hv);
+    if (!h || !h->visual) return OMV_ERR_ARG;
+    return omv_lba_reset(h);
+}
+
+omv_status omv_vba_debug_solve(omv_vba *hv, const omv_vba_opts *o, double lambda, double *S, double *rhs, double *x,
+                               int32_t *fail, int32_t *plan, int plan_cap) {
+    omv_lba *h = core(hv);
+    if (!h || !h->visual || !o || !has_problem(h)) return OMV_ERR_ARG;
+    const omv_status rs = vba_set_huber(h, o);
+    if (rs != OMV_OK) return rs;
+    const omv_lba_opts lo{o->iterations, o->lambda_init, o->max_trials, 1};
+    return omv_lba_debug_solve(h, &lo, lambda, S, rhs, x, fail, plan, plan_cap);
+}
+
+omv_status omv_vba_enable_timing(omv_vba *hv, int on) { return omv_lba_enable_timing(core(hv), on); }
+omv_status omv_vba_stage_ms(omv_vba *hv, double *ms4, int *trials) { return omv_lba_stage_ms(core(hv), ms4, trials); }
 
 }  // extern "C"

@@ -158,16 +158,6 @@ __device__ __forceinline__ void sim3_map(const Sim3d &a, const double *X, double
     q_rot(a.q, X, r);
     for (int i = 0; i < 3; ++i) Y[i] = a.s * r[i] + a.t[i];
 }
-// Quaterniond::toRotationMatrix, row-major
-__device__ __forceinline__ void q_to_mat(const double *q, double *R) {
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
-    R[3] = txy + twz, R[4] = 1 - (txx + tzz), R[5] = tyz - twx;
-    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1 - (txx + tyy);
-}
 __device__ __forceinline__ void os3_project(int model, const float *k, const double *X, double &u, double &v) {
     if (model == OMV_CAM_PINHOLE) pinhole_project(k, X, u, v);
     else kb8_project(k, X, u, v);

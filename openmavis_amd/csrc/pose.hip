@@ -1823,62 +1823,7 @@ struct PoseOnlyRig {
     double fx, fy, cx, cy, bf;                        // EdgeStereoSE3ProjectXYZOnlyPose
 };
 
-// Eigen's quaternion ops on (x y z w): Quaternion(Matrix3) and SE3Quat::normalizeRotation (q_mul / q_rot: g2o_types.h).
-__device__ void q_from_mat(const double *m, double *q) {
-    double t = m[0] + m[4] + m[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[7] - m[5]) * t, q[1] = (m[2] - m[6]) * t, q[2] = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > m[4 * i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
-        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
-        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
-    }
-}
-__device__ __forceinline__ void q_normalize_pos(double *q) {
-    if (q[3] < 0) q[0] = -q[0], q[1] = -q[1], q[2] = -q[2], q[3] = -q[3];
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    for (int i = 0; i < 4; ++i) q[i] /= n;
-}
-// VertexSE3Expmap::oplusImpl: SE3Quat::exp(dx) * (q, t) (se3quat.h:104-110, :223-257) into (qo, to)
-__device__ void se3_oplus(const double *dx, const double *q, const double *t, double *qo, double *to) {
-    const double w0 = dx[0], w1 = dx[1], w2 = dx[2];
-    const double theta = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-    const double O[9] = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0};
-    double O2[9], R[9], V[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-    if (theta < 0.00001) {
-        for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + O[k] + O2[k], V[k] = R[k];
-    } else {
-        double sn, cs;
-        sincos_d(theta, sn, cs);
-        const double a = sn / theta, b = (1 - cs) / (theta * theta), c = (theta - sn) / (theta * theta * theta);
-        for (int k = 0; k < 9; ++k) {
-            const double I = (k % 4 == 0) ? 1.0 : 0.0;
-            R[k] = I + a * O[k] + b * O2[k];
-            V[k] = I + b * O[k] + c * O2[k];
-        }
-    }
-    double eq[4], et[3];
-    q_from_mat(R, eq);
-    q_normalize_pos(eq);
-    mv3(V, dx + 3, et);
-    double rt[3];
-    q_rot(eq, t, rt);
-    for (int i = 0; i < 3; ++i) to[i] = et[i] + rt[i];
-    q_mul(eq, q, qo);
-    q_normalize_pos(qo);
-}
+// q_from_mat / q_normalize_pos / se3_oplus (VertexSE3Expmap::oplusImpl): g2o_types.h, shared with lba.hip's visual kind.
 
 struct PoseOnlyEdge {
     bool stereo;

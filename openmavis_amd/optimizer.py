@@ -166,6 +166,123 @@ class LocalInertialBA:
         return dict(build=ms[0], schur=ms[1], solve=ms[2], update=ms[3], trials=t.value)
 
 
+HUBER_MONO = float(np.float32(np.sqrt(5.991)))     # thHuberMono / thHuberStereo are floats (Optimizer.cc:1469-1470)
+HUBER_STEREO = float(np.float32(np.sqrt(7.815)))
+
+
+class LocalBundleAdjustment:
+    """Optimizer::LocalBundleAdjustment's optimisation (src/Optimizer.cc:1357-1785) on the visual kind of the device
+    bundle-adjustment solver (omv_vba, openmavis_amd/csrc/lba.hip).  The flattened graph is a problem dict (field list:
+    openmavis_amd.synth_vba.make_vba_problem, which is omv_vba_problem's):
+
+        ba = LocalBundleAdjustment(max_kf=80, max_cams=4, max_pts=10000, max_edges=200000)
+        ba.set_problem(prob)
+        res, state = ba.optimize(10, lambda_init=100.0)      # an inertial map; lambda_init <= 0: computeLambdaInit
+
+    `res`: err / err_end, iterations, trials, lambda_, lambda_init and per-edge chi2 + outlier flags (chi2 > 5.991 /
+    7.815 or a non-positive depth); `state`: q_cw, t_cw, pts.  The state stays on the device between calls, so the
+    merge overload's two rounds are optimize(5), set_levels(...) and optimize(10, huber_mono=0, huber_stereo=0);
+    BundleAdjustment is optimize(nIterations, huber_mono=sqrt(5.99) if bRobust else 0, ...).  No CPU fallback."""
+
+    STATE = ("q_cw", "t_cw", "pts")
+
+    def __init__(self, max_kf=80, max_cams=4, max_pts=40000, max_edges=400000):
+        lib = _lib.load()
+        h = ctypes.c_void_p()
+        _lib.check(lib.omv_vba_create(int(max_kf), int(max_cams), int(max_pts), int(max_edges), ctypes.byref(h)),
+                   "omv_vba_create")
+        self._lib, self._h = lib, h
+        self._s = self._keep = None
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.omv_vba_destroy(self._h)
+            self._h = None
+
+    def set_problem(self, prob):
+        from .synth_vba import as_vba_struct
+        s, keep = as_vba_struct(prob, _lib.VbaProblem)
+        _lib.check(self._lib.omv_vba_set_problem(self._h, ctypes.byref(s)), "omv_vba_set_problem")
+        self._s, self._keep = s, keep
+        return self
+
+    def _need(self, what):
+        if self._s is None:
+            raise _lib.OmvError(f"LocalBundleAdjustment.{what}: no problem set")
+
+    def set_levels(self, mono_level=None, stereo_level=None):
+        """Per-edge levels in the caller's order (0 active, 1 excluded); None: every edge of that kind active."""
+        self._need("set_levels")
+        lv = [None if a is None else np.ascontiguousarray(a, np.uint8) for a in (mono_level, stereo_level)]
+        for a, n in zip(lv, (self._s.n_mono, self._s.n_stereo)):
+            if a is not None and a.size != n:
+                raise ValueError("LocalBundleAdjustment.set_levels: one level per edge")
+        _lib.check(self._lib.omv_vba_set_levels(self._h, _lib.ptr(lv[0]), _lib.ptr(lv[1])), "omv_vba_set_levels")
+        return self
+
+    @staticmethod
+    def _opts(iterations, lambda_init, max_trials, huber_mono, huber_stereo):
+        return _lib.VbaOpts(int(iterations), float(lambda_init), int(max_trials), float(huber_mono), float(huber_stereo))
+
+    def optimize(self, iterations=10, lambda_init=0.0, max_trials=10, huber_mono=HUBER_MONO, huber_stereo=HUBER_STEREO,
+                 chi2=True):
+        self._need("optimize")
+        o = self._opts(iterations, lambda_init, max_trials, huber_mono, huber_stereo)
+        E, S = self._s.n_mono, self._s.n_stereo
+        c_m, c_s = (np.zeros(E), np.zeros(S)) if chi2 else (None, None)
+        o_m, o_s = np.zeros(E, np.uint8), np.zeros(S, np.uint8)
+        r = _lib.VbaResult()
+        r.mono_chi2, r.stereo_chi2 = _lib.ptr(c_m), _lib.ptr(c_s)
+        r.mono_outlier, r.stereo_outlier = _lib.ptr(o_m), _lib.ptr(o_s)
+        _lib.check(self._lib.omv_vba_optimize(self._h, ctypes.byref(o), ctypes.byref(self._s), ctypes.byref(r)),
+                   "omv_vba_optimize")
+        res = dict(err=r.err, err_end=r.err_end, iterations=r.iterations, trials=r.trials, lambda_=r.lambda_,
+                   lambda_init=r.lambda_init, mono_chi2=c_m, mono_outlier=o_m, stereo_chi2=c_s, stereo_outlier=o_s)
+        return res, {k: self._keep[k].copy() for k in self.STATE}
+
+    def reset(self):
+        """The state uploaded by set_problem again (device copy; the levels stay)."""
+        _lib.check(self._lib.omv_vba_reset(self._h), "omv_vba_reset")
+        return self
+
+    def evaluate(self, huber_mono=HUBER_MONO, huber_stereo=HUBER_STEREO):
+        """Errors and Jacobians (JXi = d e / d point, JXj = d e / d pose, (omega, upsilon)) at the device state."""
+        self._need("evaluate")
+        o = self._opts(0, 0.0, 10, huber_mono, huber_stereo)
+        E, S = self._s.n_mono, self._s.n_stereo
+        out = dict(mono_err=np.zeros((E, 2)), mono_jxi=np.zeros((E, 2, 3)), mono_jxj=np.zeros((E, 2, 6)),
+                   stereo_err=np.zeros((S, 3)), stereo_jxi=np.zeros((S, 3, 3)), stereo_jxj=np.zeros((S, 3, 6)))
+        _lib.check(self._lib.omv_vba_evaluate(self._h, ctypes.byref(o), *[_lib.ptr(v) for v in out.values()]),
+                   "omv_vba_evaluate")
+        return out
+
+    def debug_solve(self, lambda_, huber_mono=HUBER_MONO, huber_stereo=HUBER_STEREO):
+        """One reduced-system solve at the device state (omv_vba_debug_solve): as LocalInertialBA.debug_solve."""
+        self._need("debug_solve")
+        o = self._opts(1, 0.0, 10, huber_mono, huber_stereo)
+        nb = int(self._s.n_opt)
+        n = 16 * nb
+        S, rhs, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
+        plan = np.full(4 + nb, -1, np.int32)
+        fail = ctypes.c_int(-1)
+        _lib.check(self._lib.omv_vba_debug_solve(self._h, ctypes.byref(o), ctypes.c_double(lambda_), _lib.ptr(S),
+                                                 _lib.ptr(rhs), _lib.ptr(x), ctypes.byref(fail), _lib.ptr(plan),
+                                                 len(plan)), "omv_vba_debug_solve")
+        n_lev = int(plan[3])
+        return dict(S=S, rhs=rhs, x=x, fail=fail.value, mode=int(plan[0]), n_slots=int(plan[1]), n_lds=int(plan[2]),
+                    n_lev=n_lev, cols=[int(v) for v in plan[4:4 + n_lev]])
+
+    def enable_timing(self, on=True):
+        _lib.check(self._lib.omv_vba_enable_timing(self._h, int(bool(on))), "omv_vba_enable_timing")
+        return self
+
+    def stage_ms(self):
+        ms = np.zeros(4)
+        t = ctypes.c_int(0)
+        _lib.check(self._lib.omv_vba_stage_ms(self._h, _lib.ptr(ms), ctypes.byref(t)), "omv_vba_stage_ms")
+        return dict(build=ms[0], schur=ms[1], solve=ms[2], update=ms[3], trials=t.value)
+
+
 class PoseInertialOptimizer:
     """Host-side mirror of Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:5021-5578)
     for a batch of frames on the device (openmavis_amd/csrc/pose.hip).
