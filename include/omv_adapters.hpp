@@ -1309,6 +1309,41 @@ class LocalInertialBAWindow {
     void *ar_ctx_ = nullptr;
 };
 
+namespace detail {   // the RANSAC frame of Sim3Solver and MLPnPsolver
+// DUtils::Random::RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp:47-50)
+inline int RandomInt(int min, int max) {
+    const int d = max - min + 1;
+    return int(((double)std::rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+}
+
+// a one-job solver's device buffers and the two halves of its iterate round the handle's call
+struct RansacIO {
+    DeviceArray<int32_t> draws, n, flags;
+    DeviceArray<float> T;
+    DeviceArray<uint8_t> inl;
+    void resize(int mN) { T.resize(16), n.resize(1), flags.resize(1), inl.resize(std::max(1, mN)); }
+    // k RandomInt draws for each of n_hyp hypotheses over N correspondences, on the device
+    const int32_t *draw(int k, int N, int n_hyp, hipStream_t st) {
+        std::vector<int32_t> r((size_t)k * std::max(n_hyp, 1));
+        for (int h = 0; h < n_hyp; h++)
+            for (int i = 0; i < k; i++) r[k * h + i] = RandomInt(0, std::max(N - i, 1) - 1);
+        draws.upload(r.data(), r.size(), st);
+        return draws.p;
+    }
+    // T [16], nInliers and vbInliers [mN] of the call; returns its flags
+    int32_t fetch(int mN, hipStream_t st, float *T_out, int &nInliers, std::vector<bool> &vbInliers) {
+        int32_t count = 0, f = 0;
+        std::vector<uint8_t> host(std::max(1, mN));
+        T.download(T_out, 16, st), n.download(&count, 1, st), flags.download(&f, 1, st);
+        inl.download(host.data(), host.size(), st);
+        hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+        nInliers = count;
+        vbInliers.assign(host.begin(), host.begin() + mN);   // non-zero: true
+        return f;
+    }
+};
+}  // namespace detail
+
 // ---- Sim3Solver --------------------------------------------------------------------------------------------
 // The constructor's output (:119-179), flattened by the caller from the reference's objects after its camera-pair
 // vote: per kept correspondence the two world positions, the two level sigma2 and i1; the chosen cameras' poses and
@@ -1332,7 +1367,7 @@ class Sim3Solver {
     explicit Sim3Solver(const Sim3SolverInput &in, int max_iterations = 300, hipStream_t stream = nullptr)
         : in_(in), st_(stream), max_hyp_(std::max(1, max_iterations)) {
         check(omv_sim3_solver_create(1, (int)in_.index1.size(), max_hyp_, &h_), "omv_sim3_solver_create");
-        d_T12_.resize(16), d_n_.resize(1), d_flags_.resize(1), d_inl_.resize(std::max(1, in_.mN1));
+        io_.resize(in_.mN1);
         SetRansacParameters();   // the constructor's last line (:181)
     }
     Sim3Solver(const Sim3Solver &) = delete;
@@ -1356,22 +1391,11 @@ class Sim3Solver {
     std::array<float, 16> iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers,
                                   bool &bConverge) {
         const int n_it = std::min(nIterations, max_hyp_);
-        const int N = (int)in_.index1.size();
-        std::vector<int32_t> draws((size_t)3 * std::max(n_it, 1));
-        for (int k = 0; k < n_it; k++)
-            for (int i = 0; i < 3; i++) draws[3 * k + i] = RandomInt(0, std::max(N - i, 1) - 1);
-        d_draws_.upload(draws.data(), draws.size(), st_);
-        check(omv_sim3_solver_iterate(h_, n_it, d_draws_.p, d_T12_.p, d_n_.p, d_inl_.p, d_flags_.p, st_),
-              "omv_sim3_solver_iterate");
         std::array<float, 16> T12;
-        int32_t n = 0, flags = 0;
-        std::vector<uint8_t> inl(std::max(1, in_.mN1));
-        d_T12_.download(T12.data(), 16, st_), d_n_.download(&n, 1, st_), d_flags_.download(&flags, 1, st_);
-        d_inl_.download(inl.data(), inl.size(), st_);
-        hip_check(hipStreamSynchronize(st_), "hipStreamSynchronize");
-        bNoMore = (flags & OMV_SIM3_NO_MORE) != 0, bConverge = (flags & OMV_SIM3_CONVERGE) != 0, nInliers = n;
-        vbInliers.assign(in_.mN1, false);
-        for (int i = 0; i < in_.mN1; i++) vbInliers[i] = inl[i] != 0;
+        check(omv_sim3_solver_iterate(h_, n_it, io_.draw(3, (int)in_.index1.size(), n_it, st_), io_.T.p, io_.n.p,
+                                      io_.inl.p, io_.flags.p, st_), "omv_sim3_solver_iterate");
+        const int32_t flags = io_.fetch(in_.mN1, st_, T12.data(), nInliers, vbInliers);
+        bNoMore = (flags & OMV_SIM3_NO_MORE) != 0, bConverge = (flags & OMV_SIM3_CONVERGE) != 0;
         return T12;
     }
     // iterate(nIterations, bNoMore, vbInliers, nInliers): identity unless the call converged
@@ -1402,11 +1426,7 @@ class Sim3Solver {
     }
     int ransac_max_its() const { return max_its_; }
 
-    // DUtils::Random::RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp:47-50)
-    static int RandomInt(int min, int max) {
-        const int d = max - min + 1;
-        return int(((double)std::rand() / ((double)RAND_MAX + 1.0)) * d) + min;
-    }
+    static int RandomInt(int min, int max) { return detail::RandomInt(min, max); }
 
   private:
     Sim3SolverInput in_;
@@ -1414,9 +1434,7 @@ class Sim3Solver {
     int max_hyp_;
     int32_t max_its_ = 1;
     omv_sim3_solver *h_ = nullptr;
-    DeviceArray<int32_t> d_draws_, d_n_, d_flags_;
-    DeviceArray<float> d_T12_;
-    DeviceArray<uint8_t> d_inl_;
+    detail::RansacIO io_;
 };
 
 // ---- MLPnPsolver -------------------------------------------------------------------------------------------
@@ -1453,7 +1471,7 @@ class MLPnPsolver {
             index_.push_back(i);
         }
         check(omv_pnp_create(1, (int)index_.size(), max_hyp_, &h_), "omv_pnp_create");
-        d_T_.resize(16), d_n_.resize(1), d_flags_.resize(1), d_inl_.resize(std::max(1, mN_));
+        io_.resize(mN_);
         SetRansacParameters();   // the constructor's last line (:52)
     }
     MLPnPsolver(const MLPnPsolver &) = delete;
@@ -1475,22 +1493,11 @@ class MLPnPsolver {
     // bool iterate(nIterations, bNoMore, vbInliers, nInliers, Tout): Tout [16] row-major
     bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers,
                  std::array<float, 16> &Tout) {
-        const int N = (int)index_.size();
         const int n_draws = std::min(max_hyp_, std::max(nIterations, (int)max_its_));
-        std::vector<int32_t> draws((size_t)6 * std::max(n_draws, 1));
-        for (int k = 0; k < n_draws; k++)
-            for (int i = 0; i < 6; i++) draws[6 * k + i] = Sim3Solver::RandomInt(0, std::max(N - i, 1) - 1);
-        d_draws_.upload(draws.data(), draws.size(), st_);
-        check(omv_pnp_iterate(h_, nIterations, n_draws, d_draws_.p, d_T_.p, d_n_.p, d_inl_.p, d_flags_.p, st_),
-              "omv_pnp_iterate");
-        int32_t n = 0, flags = 0;
-        std::vector<uint8_t> inl(std::max(1, mN_));
-        d_T_.download(Tout.data(), 16, st_), d_n_.download(&n, 1, st_), d_flags_.download(&flags, 1, st_);
-        d_inl_.download(inl.data(), inl.size(), st_);
-        hip_check(hipStreamSynchronize(st_), "hipStreamSynchronize");
-        bNoMore = (flags & OMV_PNP_NO_MORE) != 0, nInliers = n;
-        vbInliers.assign(mN_, false);
-        for (int i = 0; i < mN_; i++) vbInliers[i] = inl[i] != 0;
+        check(omv_pnp_iterate(h_, nIterations, n_draws, io_.draw(6, (int)index_.size(), n_draws, st_), io_.T.p, io_.n.p,
+                              io_.inl.p, io_.flags.p, st_), "omv_pnp_iterate");
+        const int32_t flags = io_.fetch(mN_, st_, Tout.data(), nInliers, vbInliers);
+        bNoMore = (flags & OMV_PNP_NO_MORE) != 0;
         return (flags & OMV_PNP_FOUND) != 0;
     }
     int ransac_max_its() const { return max_its_; }
@@ -1506,9 +1513,7 @@ class MLPnPsolver {
     std::vector<int32_t> index_;
     int32_t max_its_ = 1, min_inliers_ = 0;
     omv_pnp *h_ = nullptr;
-    DeviceArray<int32_t> d_draws_, d_n_, d_flags_;
-    DeviceArray<float> d_T_;
-    DeviceArray<uint8_t> d_inl_;
+    detail::RansacIO io_;
 };
 
 // ---- Optimizer::OptimizeSim3 -------------------------------------------------------------------------------

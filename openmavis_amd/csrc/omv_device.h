@@ -36,6 +36,13 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// The same step where the lanes exchange through global memory too: the LDS / global writes of this wave's lanes
+// become visible to its other lanes.
+__device__ __forceinline__ void wave_mem_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
 
 // Butterfly reductions over the 64 lanes of a wavefront (every lane active): all lanes get the result.
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {

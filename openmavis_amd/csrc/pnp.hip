@@ -27,9 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
-#include <climits>
 #include <cmath>
-#include <cstdio>
 #include <vector>
 
 #include "../../include/omv.h"
@@ -37,6 +35,7 @@
 #include "omv_camera.h"
 #include "omv_device.h"
 #include "omv_host.h"
+#include "omv_ransac.h"
 
 namespace {
 
@@ -55,10 +54,11 @@ constexpr int kOffA = 0, kOffV = 144, kOffM = 288, kOffVM = 297, kOffH = 306, kO
               kOffRows = 366, kSlot = kOffRows + kMinSet * kRow;
 constexpr int kSlotI = 16;     // ints: ldlt transpositions [8], the sampled list [6]
 
-struct JobParams {
-    int corr_start, n, mn, inl_start, word_start, min_inliers, max_its, model;
+struct JobParams : omv_ransac::JobLayout {
+    int min_inliers, max_its, model;
     float cam[8];
 };
+static_assert(sizeof(JobParams) == 16 * 4, "the layout is the head, nothing is padded");
 
 struct JobState {
     int iterations, best_inliers, flags, last_chunk, n_inliers, n_refine;
@@ -70,14 +70,6 @@ struct Pose {
     double R0[9], t0[3], R[9], t[3];
     int planar, its, reason;
 };
-
-// the LDS / global writes of this wave's lanes become visible to its other lanes (the Gauss-Newton rows of Refine are
-// in global memory)
-__device__ __forceinline__ void wave_mem_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 __device__ __forceinline__ double wave_max_f64(double v) {
 #pragma unroll
@@ -443,7 +435,7 @@ __device__ inline void compute_pose_wave(const double *pre, const int *list, int
         double R[9];
         rodrigues2rot(xs, R);
         for (int k = lane; k < n; k += 64) residual_and_jac(xs, R, pre + (size_t)kPre * list[k], rows + (size_t)kRow * k);
-        wave_mem_sync();
+        omv::wave_mem_sync();
         if (lane < 42) {   // A = Jac^T Jac (36 entries), g = Jac^T r (6)
             const int a = lane < 36 ? lane / 6 : lane - 36, b = lane < 36 ? lane % 6 : 12;
             double s = 0.0;
@@ -490,7 +482,7 @@ __device__ inline void compute_pose_wave(const double *pre, const int *list, int
             dl = fmax(dl, fmax(fabs(s0), fabs(s1)));
         }
         dl = wave_max_f64(dl);
-        wave_mem_sync();   // the rows are rewritten by the next iteration
+        omv::wave_mem_sync();   // the rows are rewritten by the next iteration
 #pragma unroll
         for (int i = 0; i < 6; i++) xs[i] = xs[i] - dx[i];
         if (dl < 1e-5) {
@@ -508,50 +500,23 @@ __device__ inline void compute_pose_wave(const double *pre, const int *list, int
 // CheckInliers (:220-247) of the pose (R, t) over the job's n correspondences by one wavefront; returns the count
 __device__ inline int check_inliers_wave(const JobParams &jp, const double *R, const double *t, const double *pre,
                                          const float *P2D, const float *max_err, unsigned long long *mask, int lane) {
-    int count = 0;
     bool finite = true;
 #pragma unroll
     for (int i = 0; i < 9; i++) finite = finite && fabs(R[i]) <= DBL_MAX;
 #pragma unroll
     for (int i = 0; i < 3; i++) finite = finite && fabs(t[i]) <= DBL_MAX;
-    for (int base = 0; base < jp.n; base += 64) {
-        const int i = base + lane;
-        bool inl = false;
-        if (i < jp.n && finite) {
-            const size_t c = (size_t)(jp.corr_start + i);
-            const double *p = pre + kPre * c + 9;
-            float X[3], u, v;
+    return omv_ransac::wave_inlier_mask(jp.n, lane, mask, [&](int i) {
+        if (!finite) return false;
+        const size_t c = (size_t)(jp.corr_start + i);
+        const double *p = pre + kPre * c + 9;
+        float X[3], u, v;
 #pragma unroll
-            for (int r = 0; r < 3; r++) X[r] = (float)(((R[3 * r] * p[0] + R[3 * r + 1] * p[1]) + R[3 * r + 2] * p[2]) + t[r]);
-            omv::cam_project_f(jp.model, jp.cam, X, u, v);
-            const float dx = P2D[2 * c] - u, dy = P2D[2 * c + 1] - v;
-            const float e2 = dx * dx + dy * dy;
-            inl = e2 < max_err[c];
-        }
-        const unsigned long long m = __ballot(inl);
-        if (lane == 0) mask[base >> 6] = m;
-        count += __popcll(m);
-    }
-    return count;
-}
-
-// the i-th pick (:87-98) for i < 6 from raw draws r_i in [0, n-1-i] (clamped) on the shrinking copy of mvAllIndices
-// with swap-with-back removal.  The list is not materialised: position p of the current list holds the value the
-// latest earlier pick that removed from position p moved there, else p.
-__device__ __forceinline__ void replay_sampling(int n, const int32_t *draws, int *idx) {
-    int pos[kMinSet], val[kMinSet];   // pick j removed position pos[j] and wrote the then-back value val[j] there
-#pragma unroll
-    for (int i = 0; i < kMinSet; i++) {
-        const int size = n - i, r = min(max(draws[i], 0), size - 1);
-        int at_r = r, at_back = size - 1;
-#pragma unroll
-        for (int j = 0; j < i; j++) {
-            if (pos[j] == r) at_r = val[j];
-            if (pos[j] == size - 1) at_back = val[j];
-        }
-        idx[i] = at_r;
-        pos[i] = r, val[i] = at_back;
-    }
+        for (int r = 0; r < 3; r++) X[r] = (float)(((R[3 * r] * p[0] + R[3 * r + 1] * p[1]) + R[3 * r + 2] * p[2]) + t[r]);
+        omv::cam_project_f(jp.model, jp.cam, X, u, v);
+        const float dx = P2D[2 * c] - u, dy = P2D[2 * c + 1] - v;
+        const float e2 = dx * dx + dy * dy;
+        return e2 < max_err[c];
+    });
 }
 
 __device__ __forceinline__ void store_pose(double *hd, const Pose &po) {
@@ -582,7 +547,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock)
     double *sm = sm_all[wv];
     int *smi = smi_all[wv];
     int idx[kMinSet];
-    replay_sampling(jp.n, draws + (size_t)kMinSet * gidx, idx);
+    omv_ransac::replay_sampling<kMinSet>(jp.n, draws + (size_t)kMinSet * gidx, idx);
     if (lane < kMinSet) {
         int v = idx[0];
 #pragma unroll
@@ -646,12 +611,12 @@ __global__ void __launch_bounds__(64)
                     if ((m >> lane) & 1ull) lst[n_in + __popcll(m & ((1ull << lane) - 1ull))] = jp.corr_start + 64 * w + lane;
                     n_in += __popcll(m);
                 }
-                wave_mem_sync();
+                omv::wave_mem_sync();
                 Pose po;
                 compute_pose_wave(pre, lst, n_in, sm, smi, rows + (size_t)kRow * jp.corr_start, lane, po);
                 unsigned long long *rec_mask = r_mask + (size_t)n_ref * words_total + jp.word_start;
                 rcount = check_inliers_wave(jp, po.R, po.t, pre, P2D, max_err, rec_mask, lane);
-                wave_mem_sync();
+                omv::wave_mem_sync();
                 for (int w = lane; w < n_words; w += 64) rm[w] = rec_mask[w];
                 ok = rcount > jp.min_inliers, valid = 1;   // :287
                 if (lane < 16) {
@@ -687,14 +652,7 @@ __global__ void __launch_bounds__(64)
         js.n_refine = n_ref, js.refined_valid = valid, js.refined_count = rcount, js.refined_ok = ok, js.out_kind = kind;
         n_inliers_out[job] = n_inl, flags_out[job] = flags;
     }
-    uint8_t *vb = inliers_out + jp.inl_start;
-    for (int i = lane; i < jp.mn; i += 64) vb[i] = 0;
-    wave_mem_sync();   // the zeros land before the scatter
-    if (kind) {
-        const unsigned long long *mk = kind == 1 ? rm : bm;
-        for (int i = lane; i < jp.n; i += 64)
-            if ((mk[i >> 6] >> (i & 63)) & 1ull) vb[index[jp.corr_start + i]] = 1;
-    }
+    omv_ransac::wave_scatter_inliers(jp, lane, kind == 1 ? rm : (kind == 2 ? bm : nullptr), index, inliers_out);
 }
 
 }  // namespace
@@ -715,39 +673,13 @@ struct omv_pnp {
     omv::DeviceArena mem;   // owns the d_* buffers
 };
 
-namespace {
-
-// SetRansacParameters (:177-213) in the reference's types.  Where the reference converts a NaN or an out-of-range
-// double to int (undefined; x86 yields INT_MIN) the result is INT_MIN, so mRansacMaxIts becomes 1.
-void ransac_parameters(int N, double prob, int min_inliers, int max_its, int min_set, float epsilon, int *max_its_out,
-                       int *min_inliers_out) {
-    const float prod = (float)N * epsilon;   // int nMinInliers = N * mRansacEpsilon
-    int n_min = (prod >= -2147483648.f && prod < 2147483648.f) ? (int)prod : INT_MIN;
-    if (n_min < min_inliers) n_min = min_inliers;
-    if (n_min < min_set) n_min = min_set;
-    if (epsilon < (float)n_min / N) epsilon = (float)n_min / N;
-    int n_iterations;
-    if (n_min == N) {
-        n_iterations = 1;
-    } else {
-        const double v = ceil(log(1 - prob) / log(1 - pow((double)epsilon, 3.0)));
-        n_iterations = (v >= -2147483648.0 && v <= 2147483647.0) ? (int)v : INT_MIN;
-    }
-    *max_its_out = std::max(1, std::min(n_iterations, max_its));
-    *min_inliers_out = n_min;
-}
-
-}  // namespace
-
 extern "C" {
 
 omv_status omv_pnp_create(int max_jobs, int max_corr_total, int max_hyp, omv_pnp **out) {
-    if (!out || max_jobs <= 0 || max_corr_total < 0 || max_hyp <= 0) return OMV_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return OMV_ERR_NO_DEVICE;
+    if (const omv_status e = omv_ransac::check_create(out, max_jobs, max_corr_total, max_hyp)) return e;
     auto h = std::make_unique<omv_pnp>();
     h->max_jobs = max_jobs, h->max_corr = max_corr_total, h->max_hyp = max_hyp;
-    h->words_cap = max_corr_total / 64 + max_jobs;
+    h->words_cap = omv_ransac::words_cap(max_corr_total, max_jobs);
     const size_t nc = (size_t)std::max(1, max_corr_total), nh = (size_t)max_jobs * max_hyp;
     const size_t nm = (size_t)max_hyp * h->words_cap;
     omv::DeviceArena &mem = h->mem;
@@ -772,32 +704,21 @@ omv_status omv_pnp_set(omv_pnp *h, int n_jobs, const int32_t *corr_start, const 
                        const float *Xw, const int32_t *index, const int32_t *mN, const float *cam, const int32_t *model,
                        double prob, int min_inliers, int max_its, int min_set, float epsilon, float th2,
                        int32_t *ransac_max_its_out, int32_t *ransac_min_inliers_out, void *stream) {
-    if (!h || n_jobs < 0 || min_set != kMinSet || (n_jobs > 0 && (!corr_start || !mN || !cam || !model)))
-        return OMV_ERR_ARG;
-    if (n_jobs > h->max_jobs) return OMV_ERR_CAPACITY;
-    const int n_corr = n_jobs ? corr_start[n_jobs] : 0;
-    if (n_jobs && corr_start[0] != 0) return OMV_ERR_ARG;
-    for (int j = 0; j < n_jobs; j++) {
-        if (corr_start[j + 1] < corr_start[j] || mN[j] < 0) return OMV_ERR_ARG;
-        if (model[j] != OMV_CAM_KB8 && model[j] != OMV_CAM_PINHOLE) return OMV_ERR_ARG;
-    }
-    if (n_corr > h->max_corr) return OMV_ERR_CAPACITY;
-    if (n_corr > 0 && (!P2D || !sigma2 || !Xw || !index)) return OMV_ERR_ARG;
-    std::vector<JobParams> jobs(n_jobs);
+    if (!h || min_set != kMinSet || (n_jobs > 0 && (!cam || !model))) return OMV_ERR_ARG;
+    std::vector<JobParams> jobs;
+    std::vector<int32_t> corr_job;
+    int words = 0;
+    const auto model_ok = [&](int j) { return model[j] == OMV_CAM_KB8 || model[j] == OMV_CAM_PINHOLE; };
+    if (const omv_status e = omv_ransac::plan_layout(n_jobs, corr_start, mN, index, P2D && sigma2 && Xw && index,
+                                                     h->max_jobs, h->max_corr, h->words_cap, model_ok, &jobs,
+                                                     &corr_job, &words))
+        return e;
+    const int n_corr = (int)corr_job.size();
     std::vector<JobState> state(n_jobs);
-    std::vector<int32_t> corr_job(n_corr);
-    int inl = 0, words = 0;
     for (int j = 0; j < n_jobs; j++) {
         JobParams &p = jobs[j];
-        p.corr_start = corr_start[j], p.n = corr_start[j + 1] - corr_start[j], p.mn = mN[j];
-        for (int i = corr_start[j]; i < corr_start[j + 1]; i++) {
-            if (index[i] < 0 || index[i] >= mN[j]) return OMV_ERR_ARG;
-            corr_job[i] = j;
-        }
-        p.inl_start = inl, p.word_start = words;
-        inl += p.mn, words += (p.n + 63) / 64;
         p.model = model[j];
-        ransac_parameters(p.n, prob, min_inliers, max_its, min_set, epsilon, &p.max_its, &p.min_inliers);
+        omv_ransac::mlpnp_parameters(p.n, prob, min_inliers, max_its, min_set, epsilon, &p.max_its, &p.min_inliers);
         if (ransac_max_its_out) ransac_max_its_out[j] = p.max_its;
         if (ransac_min_inliers_out) ransac_min_inliers_out[j] = p.min_inliers;
         for (int k = 0; k < 8; k++) p.cam[k] = cam[8 * j + k];
@@ -806,7 +727,6 @@ omv_status omv_pnp_set(omv_pnp *h, int n_jobs, const int32_t *corr_start, const 
         s.Tbest[0] = s.Tbest[5] = s.Tbest[10] = s.Tbest[15] = 1.f;
         s.Tref[0] = s.Tref[5] = s.Tref[10] = s.Tref[15] = 1.f;
     }
-    if (words > h->words_cap) return OMV_ERR_CAPACITY;
     hipStream_t st = (hipStream_t)stream;
     h->jobs = jobs, h->n_jobs = n_jobs, h->n_corr = n_corr, h->words_total = words, h->last_n_draws = 0;
     if (n_jobs == 0) return OMV_OK;
@@ -869,22 +789,17 @@ omv_status omv_pnp_debug(omv_pnp *h, int job, int32_t *n_hyp, int32_t *hyp_int, 
     const size_t o = (size_t)job * h->last_n_draws;
     const hipMemcpyKind k = hipMemcpyDeviceToHost;
     const JobParams &p = h->jobs[job];
-    const size_t nw = (size_t)(p.n + 63) / 64;
     if (prepared && p.n)
         HIP_OK(hipMemcpyAsync(prepared, h->d_pre + (size_t)kPre * p.corr_start, (size_t)p.n * kPre * sizeof(double), k, st));
     if (H > 0) {
         if (hyp_int) HIP_OK(hipMemcpyAsync(hyp_int, h->d_hint + kHypI * o, (size_t)H * kHypI * sizeof(int32_t), k, st));
         if (hyp_pose) HIP_OK(hipMemcpyAsync(hyp_pose, h->d_hdbl + kHypD * o, (size_t)H * kHypD * sizeof(double), k, st));
-        if (mask_words && nw)
-            HIP_OK(hipMemcpy2DAsync(mask_words, nw * 8, h->d_hmask + p.word_start, (size_t)h->words_total * 8, nw * 8, H,
-                                    k, st));
+        HIP_OK(omv_ransac::read_mask_rows(mask_words, h->d_hmask, p, h->words_total, H, st));
     }
     if (NR > 0) {
         if (ref_int) HIP_OK(hipMemcpyAsync(ref_int, h->d_rint + kRefI * o, (size_t)NR * kRefI * sizeof(int32_t), k, st));
         if (ref_pose) HIP_OK(hipMemcpyAsync(ref_pose, h->d_rdbl + kHypD * o, (size_t)NR * kHypD * sizeof(double), k, st));
-        if (ref_mask_words && nw)
-            HIP_OK(hipMemcpy2DAsync(ref_mask_words, nw * 8, h->d_rmask + p.word_start, (size_t)h->words_total * 8, nw * 8,
-                                    NR, k, st));
+        HIP_OK(omv_ransac::read_mask_rows(ref_mask_words, h->d_rmask, p, h->words_total, NR, st));
     }
     HIP_OK(hipStreamSynchronize(st));
     return OMV_OK;

@@ -21,26 +21,26 @@
 // same rotation mathematically); tests/test_sim3solver_gpu.py bounds the difference by the problem's conditioning.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
-#include <cstdio>
 #include <vector>
 
 #include "../../include/omv.h"
 #include "omv_camera.h"
 #include "omv_device.h"
 #include "omv_host.h"
+#include "omv_ransac.h"
 
 namespace {
 
 constexpr int kWavesPerBlock = 4;
 constexpr int kFlagNoMore = 1, kFlagConverge = 2;
 
-struct JobParams {
-    int corr_start, n, mn1, inl_start, word_start, min_inliers, max_its, fix_scale, model1, model2;
+struct JobParams : omv_ransac::JobLayout {   // mn: mN1
+    int min_inliers, max_its, fix_scale, model1, model2;
     float pose1[12], pose2[12];   // Riw row-major, tiw
     float cam1[8], cam2[8];
 };
+static_assert(sizeof(JobParams) == 50 * 4, "the layout is the head, nothing is padded");
 
 struct JobState {
     int iterations, best_inliers, flags, last_chunk, n_inliers;
@@ -145,17 +145,6 @@ __device__ __forceinline__ void jacobi4_top_eigenvector(double (&a)[4][4], doubl
     }
 }
 
-// idx of the i-th pick (:230-243) from the raw draws r0 in [0, n-1], r1 in [0, n-2], r2 in [0, n-3] on the shrinking copy
-// of mvAllIndices = 0 .. n-1 with swap-with-back removal.  Draws outside their range are clamped into it.
-__device__ __forceinline__ void replay_sampling(int n, int r0, int r1, int r2, int *idx) {
-    r0 = min(max(r0, 0), n - 1), r1 = min(max(r1, 0), n - 2), r2 = min(max(r2, 0), n - 3);
-    // after pick 0, position p holds (p == r0 ? n - 1 : p) for p < n - 1
-    const int back1 = (r0 == n - 2) ? n - 1 : n - 2;   // the back of the list of n - 1 entries
-    idx[0] = r0;
-    idx[1] = (r1 == r0) ? n - 1 : r1;
-    idx[2] = (r2 == r1) ? back1 : ((r2 == r0) ? n - 1 : r2);
-}
-
 __global__ void __launch_bounds__(64 * kWavesPerBlock)
     sim3_hypothesis_kernel(const JobParams *jobs, const JobState *state, int n_jobs, int n_it, const int32_t *draws,
                            const float *X1, const float *X2, const float *P1, const float *P2, const float *e1,
@@ -170,7 +159,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock)
     if (js.flags != 0 || hyp >= min(n_it, jp.max_its - js.iterations)) return;
     const int n = jp.n, c0 = jp.corr_start;
     int idx[3];
-    replay_sampling(n, draws[3 * (size_t)g], draws[3 * (size_t)g + 1], draws[3 * (size_t)g + 2], idx);
+    omv_ransac::replay_sampling<3>(n, draws + 3 * (size_t)g, idx);
 
     // ---- ComputeSim3 (wave-uniform) ----
     float p1[3][3], p2[3][3];   // [row][col]: column i = the i-th picked point (P3Dc1i, P3Dc2i)
@@ -247,28 +236,20 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock)
     T21[12] = T21[13] = T21[14] = 0.f, T21[15] = 1.f;
 
     // ---- CheckInliers: the lanes stride over the correspondences ----
-    int count = 0;
     unsigned long long *mask = h_mask + (size_t)hyp * words_total + jp.word_start;
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        bool inl = false;
-        if (i < n) {
-            const size_t c = (size_t)(c0 + i);
-            float xa[3] = {X1[3 * c], X1[3 * c + 1], X1[3 * c + 2]}, xb[3] = {X2[3 * c], X2[3 * c + 1], X2[3 * c + 2]};
-            float Y[3], u, v;
-            t44_apply(T12, xb, Y);   // vP2im1 = project(T12 X3Dc2) with camera 1
-            omv::cam_project_f(jp.model1, jp.cam1, Y, u, v);
-            const float d1x = P1[2 * c] - u, d1y = P1[2 * c + 1] - v;
-            t44_apply(T21, xa, Y);   // vP1im2 = project(T21 X3Dc1) with camera 2
-            omv::cam_project_f(jp.model2, jp.cam2, Y, u, v);
-            const float d2x = u - P2[2 * c], d2y = v - P2[2 * c + 1];
-            const float err1 = d1x * d1x + d1y * d1y, err2 = d2x * d2x + d2y * d2y;
-            inl = err1 < e1[c] && err2 < e2[c];   // false for a NaN, as in the reference
-        }
-        const unsigned long long m = __ballot(inl);
-        if (lane == 0) mask[base >> 6] = m;
-        count += __popcll(m);
-    }
+    const int count = omv_ransac::wave_inlier_mask(n, lane, mask, [&](int i) {
+        const size_t c = (size_t)(c0 + i);
+        float xa[3] = {X1[3 * c], X1[3 * c + 1], X1[3 * c + 2]}, xb[3] = {X2[3 * c], X2[3 * c + 1], X2[3 * c + 2]};
+        float Y[3], u, v;
+        t44_apply(T12, xb, Y);   // vP2im1 = project(T12 X3Dc2) with camera 1
+        omv::cam_project_f(jp.model1, jp.cam1, Y, u, v);
+        const float d1x = P1[2 * c] - u, d1y = P1[2 * c + 1] - v;
+        t44_apply(T21, xa, Y);   // vP1im2 = project(T21 X3Dc1) with camera 2
+        omv::cam_project_f(jp.model2, jp.cam2, Y, u, v);
+        const float d2x = u - P2[2 * c], d2y = v - P2[2 * c + 1];
+        const float err1 = d1x * d1x + d1y * d1y, err2 = d2x * d2x + d2y * d2y;
+        return err1 < e1[c] && err2 < e2[c];   // false for a NaN, as in the reference
+    });
     const size_t o = (size_t)g;
     // the per-hypothesis record: written by lane 0 (a few dozen words)
     if (lane == 0) {
@@ -345,12 +326,7 @@ __global__ void __launch_bounds__(64)
     const bool conv = (flags & kFlagConverge) != 0;
     if (lane < 16) T12_out[16 * job + lane] = js.T12[lane];
     if (lane == 0) n_inliers_out[job] = conv ? js.n_inliers : 0, flags_out[job] = flags;
-    uint8_t *vb = inliers_out + jp.inl_start;
-    for (int i = lane; i < jp.mn1; i += 64) vb[i] = 0;
-    __syncthreads();   // the zeros land before the scatter
-    if (conv)
-        for (int i = lane; i < jp.n; i += 64)
-            if ((best_mask[jp.word_start + (i >> 6)] >> (i & 63)) & 1ull) vb[index1[jp.corr_start + i]] = 1;
+    omv_ransac::wave_scatter_inliers(jp, lane, conv ? best_mask + jp.word_start : nullptr, index1, inliers_out);
 }
 
 }  // namespace
@@ -370,33 +346,13 @@ struct omv_sim3_solver {
     omv::DeviceArena mem;   // owns the d_* buffers
 };
 
-namespace {
-
-// SetRansacParameters (:194-204) in the reference's types.  Where the reference converts a NaN or an out-of-range
-// double to int (undefined; x86 yields INT_MIN) the result is INT_MIN, so mRansacMaxIts becomes 1.
-int ransac_max_its(double prob, int min_inliers, int n, int max_its) {
-    int n_iterations;
-    if (min_inliers == n) {
-        n_iterations = 1;
-    } else {
-        const float epsilon = (float)min_inliers / n;
-        const double v = ceil(log(1 - prob) / log(1 - pow((double)epsilon, 3.0)));
-        n_iterations = (v >= -2147483648.0 && v <= 2147483647.0) ? (int)v : INT_MIN;
-    }
-    return std::max(1, std::min(n_iterations, max_its));
-}
-
-}  // namespace
-
 extern "C" {
 
 omv_status omv_sim3_solver_create(int max_jobs, int max_corr_total, int max_hyp, omv_sim3_solver **out) {
-    if (!out || max_jobs <= 0 || max_corr_total < 0 || max_hyp <= 0) return OMV_ERR_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return OMV_ERR_NO_DEVICE;
+    if (const omv_status e = omv_ransac::check_create(out, max_jobs, max_corr_total, max_hyp)) return e;
     auto h = std::make_unique<omv_sim3_solver>();
     h->max_jobs = max_jobs, h->max_corr = max_corr_total, h->max_hyp = max_hyp;
-    h->words_cap = max_corr_total / 64 + max_jobs;
+    h->words_cap = omv_ransac::words_cap(max_corr_total, max_jobs);
     const size_t nc = (size_t)std::max(1, max_corr_total), nh = (size_t)max_jobs * max_hyp;
     omv::DeviceArena &mem = h->mem;
     if (!mem.alloc(&h->d_jobs, max_jobs) || !mem.alloc(&h->d_state, max_jobs) || !mem.alloc(&h->d_corr_job, nc) ||
@@ -420,35 +376,25 @@ omv_status omv_sim3_solver_set(omv_sim3_solver *h, int n_jobs, const int32_t *co
                                const float *cam2, const int32_t *model1, const int32_t *model2, const int32_t *fix_scale,
                                double prob, const int32_t *min_inliers, int max_its, int32_t *ransac_max_its_out,
                                void *stream) {
-    if (!h || n_jobs < 0 || (n_jobs > 0 && (!corr_start || !mN1 || !pose1 || !pose2 || !cam1 || !cam2 || !model1 ||
-                                            !model2 || !fix_scale || !min_inliers)))
+    if (!h || (n_jobs > 0 && (!pose1 || !pose2 || !cam1 || !cam2 || !model1 || !model2 || !fix_scale || !min_inliers)))
         return OMV_ERR_ARG;
-    if (n_jobs > h->max_jobs) return OMV_ERR_CAPACITY;
-    const int n_corr = n_jobs ? corr_start[n_jobs] : 0;
-    if (n_jobs && corr_start[0] != 0) return OMV_ERR_ARG;
-    for (int j = 0; j < n_jobs; j++) {
-        if (corr_start[j + 1] < corr_start[j] || mN1[j] < 0) return OMV_ERR_ARG;
-        if ((model1[j] != OMV_CAM_KB8 && model1[j] != OMV_CAM_PINHOLE) ||
-            (model2[j] != OMV_CAM_KB8 && model2[j] != OMV_CAM_PINHOLE))
-            return OMV_ERR_ARG;
-    }
-    if (n_corr > h->max_corr) return OMV_ERR_CAPACITY;
-    if (n_corr > 0 && (!Xw1 || !Xw2 || !sigma2_1 || !sigma2_2 || !index1)) return OMV_ERR_ARG;
-    std::vector<JobParams> jobs(n_jobs);
+    std::vector<JobParams> jobs;
+    std::vector<int32_t> corr_job;
+    int words = 0;
+    const auto models_ok = [&](int j) {
+        return (model1[j] == OMV_CAM_KB8 || model1[j] == OMV_CAM_PINHOLE) &&
+               (model2[j] == OMV_CAM_KB8 || model2[j] == OMV_CAM_PINHOLE);
+    };
+    if (const omv_status e = omv_ransac::plan_layout(n_jobs, corr_start, mN1, index1,
+                                                     Xw1 && Xw2 && sigma2_1 && sigma2_2 && index1, h->max_jobs,
+                                                     h->max_corr, h->words_cap, models_ok, &jobs, &corr_job, &words))
+        return e;
+    const int n_corr = (int)corr_job.size();
     std::vector<JobState> state(n_jobs);
-    std::vector<int32_t> corr_job(n_corr);
-    int inl = 0, words = 0;
     for (int j = 0; j < n_jobs; j++) {
         JobParams &p = jobs[j];
-        p.corr_start = corr_start[j], p.n = corr_start[j + 1] - corr_start[j], p.mn1 = mN1[j];
-        for (int i = corr_start[j]; i < corr_start[j + 1]; i++) {
-            if (index1[i] < 0 || index1[i] >= mN1[j]) return OMV_ERR_ARG;
-            corr_job[i] = j;
-        }
-        p.inl_start = inl, p.word_start = words;
-        inl += p.mn1, words += (p.n + 63) / 64;
         p.min_inliers = min_inliers[j], p.fix_scale = fix_scale[j] != 0, p.model1 = model1[j], p.model2 = model2[j];
-        p.max_its = p.n > 0 ? ransac_max_its(prob, p.min_inliers, p.n, max_its) : 1;
+        p.max_its = p.n > 0 ? omv_ransac::ransac_its(prob, (float)p.min_inliers / p.n, p.min_inliers == p.n, max_its) : 1;
         if (ransac_max_its_out) ransac_max_its_out[j] = p.max_its;
         for (int k = 0; k < 12; k++) p.pose1[k] = pose1[12 * j + k], p.pose2[k] = pose2[12 * j + k];
         for (int k = 0; k < 8; k++) p.cam1[k] = cam1[8 * j + k], p.cam2[k] = cam2[8 * j + k];
@@ -460,7 +406,6 @@ omv_status omv_sim3_solver_set(omv_sim3_solver *h, int n_jobs, const int32_t *co
         // is undefined there) and are treated the same way: bNoMore, identity, no work
         if (p.n < p.min_inliers || p.n < 3) s.flags = kFlagNoMore;
     }
-    if (words > h->words_cap) return OMV_ERR_CAPACITY;
     hipStream_t st = (hipStream_t)stream;
     h->jobs = jobs, h->n_jobs = n_jobs, h->n_corr = n_corr, h->words_total = words, h->last_n_it = 0;
     if (n_jobs == 0) return OMV_OK;
@@ -547,13 +492,7 @@ omv_status omv_sim3_solver_debug(omv_sim3_solver *h, int job, int32_t *n_hyp, in
     if (t) HIP_OK(hipMemcpyAsync(t, hf + 41 * nh + 3 * o, (size_t)H * 3 * sizeof(float), k, st));
     if (scale) HIP_OK(hipMemcpyAsync(scale, hf + 44 * nh + o, (size_t)H * sizeof(float), k, st));
     if (count) HIP_OK(hipMemcpyAsync(count, h->d_hcount + o, (size_t)H * sizeof(int32_t), k, st));
-    if (mask_words) {
-        const JobParams &p = h->jobs[job];
-        const size_t nw = (size_t)(p.n + 63) / 64;
-        if (nw)
-            HIP_OK(hipMemcpy2DAsync(mask_words, nw * 8, h->d_hmask + p.word_start, (size_t)h->words_total * 8, nw * 8, H,
-                                    k, st));
-    }
+    HIP_OK(omv_ransac::read_mask_rows(mask_words, h->d_hmask, h->jobs[job], h->words_total, H, st));
     HIP_OK(hipStreamSynchronize(st));
     return OMV_OK;
 }

@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .sim3solver import draw
+from .ransac import BatchedRansac
 
 NO_MORE, FOUND = 1, 2
 GN_MAXIT, GN_EPSP, GN_BREAK, GN_NAN = 0, 1, 2, 3
@@ -35,34 +35,13 @@ def select_correspondences(has_mp, is_bad, n_keys):
     return np.nonzero(keep)[0].astype(np.int32)
 
 
-class MLPnPsolver:
+class MLPnPsolver(BatchedRansac):
+    K, _CREATE, _DESTROY = MIN_SET, "omv_pnp_create", "omv_pnp_destroy"
+
     def __init__(self, jobs, max_hyp=300, device="cuda:0", stream=None):
-        import torch
-        self._torch, self._lib, self.device, self.stream = torch, _lib.load(), device, stream
-        self.jobs = list(jobs)
-        J = self.n_jobs = len(self.jobs)
-        self.n = np.array([len(j["index"]) for j in self.jobs], np.int32)
-        self.mN = np.array([int(j["mN"]) for j in self.jobs], np.int32)
-        self.corr_start = np.concatenate([[0], np.cumsum(self.n)]).astype(np.int32)
-        self.inl_start = np.concatenate([[0], np.cumsum(self.mN)]).astype(np.int64)
-        self.max_hyp = int(max_hyp)
-        self._h = ctypes.c_void_p()
-        _lib.check(self._lib.omv_pnp_create(max(J, 1), int(self.corr_start[-1]), self.max_hyp, ctypes.byref(self._h)),
-                   "omv_pnp_create")
-        self.T = torch.zeros((max(J, 1), 16), dtype=torch.float32, device=device)
-        self.n_inliers = torch.zeros(max(J, 1), dtype=torch.int32, device=device)
-        self.flags = torch.zeros(max(J, 1), dtype=torch.int32, device=device)
-        self.inliers = torch.zeros(max(int(self.inl_start[-1]), 1), dtype=torch.uint8, device=device)
+        super().__init__(jobs, "index", "mN", max_hyp, device, stream)
+        self.mN, self.T = self._mn, self._T
         self.SetRansacParameters()   # the constructor's last line (:52): the header's defaults
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.omv_pnp_destroy(self._h)
-            self._h = None
-
-    def _stream(self):
-        s = self.stream if self.stream is not None else self._torch.cuda.current_stream()
-        return ctypes.c_void_p(s.cuda_stream)
 
     def SetRansacParameters(self, probability=0.99, minInliers=8, maxIterations=300, minSet=6, epsilon=0.4, th2=5.991):
         """Uploads the jobs and resets the carried state; mRansacMaxIts / mRansacMinInliers per job are left in
@@ -72,13 +51,7 @@ class MLPnPsolver:
 
     def _set(self, probability=0.99, minInliers=8, maxIterations=300, minSet=6, epsilon=0.4, th2=5.991):
         """omv_pnp_set on self.jobs; returns the status."""
-        J = self.n_jobs
-
-        def cat(key, dt, width):
-            if not J:
-                return np.zeros((0, width), dt)
-            return np.ascontiguousarray(np.concatenate([np.asarray(j[key], dt).reshape(-1, width) for j in self.jobs]))
-
+        J, cat = self.n_jobs, self._cat
         arrs = [self.corr_start, cat("P2D", np.float32, 2), cat("sigma2", np.float32, 1), cat("Xw", np.float32, 3),
                 cat("index", np.int32, 1), self.mN, cat("cam", np.float32, 8),
                 np.array([j["model"] for j in self.jobs], np.int32)]
@@ -90,20 +63,12 @@ class MLPnPsolver:
             self.max_its, self.min_inliers = max_its[:J], min_inl[:J]
         return status
 
-    def draw(self, rng_or_rand, n_draws):
-        """Raw draws [n_jobs][n_draws][6] (int32, host), job after job."""
-        return np.stack([draw(rng_or_rand, n_draws, int(n), MIN_SET) for n in self.n]) if self.n_jobs else \
-            np.zeros((0, n_draws, MIN_SET), np.int32)
-
     def iterate(self, nIterations, draws):
         """iterate(nIterations, bNoMore, vbInliers, nInliers, Tout) for every job.  draws: [n_jobs][H][6] int32, host
         array or device tensor; a job runs min(H, max(nIterations, mRansacMaxIts - mnIterations)) hypotheses unless it
         returns earlier.  Returns device tensors (found [J], Tcw [J][4][4], bNoMore [J], vbInliers (flat uint8; job j at
         inl_start[j]), nInliers [J]); nothing is synchronised."""
-        torch = self._torch
-        if not torch.is_tensor(draws):
-            draws = torch.from_numpy(np.ascontiguousarray(draws, np.int32))
-        draws = draws.to(self.device, torch.int32).contiguous()
+        draws = self._device_draws(draws)
         J = self.n_jobs
         H = draws.numel() // (J * MIN_SET) if J else 0
         assert draws.numel() == J * H * MIN_SET, "draws: [n_jobs][H][6]"
@@ -112,10 +77,6 @@ class MLPnPsolver:
                                              self._stream()), "omv_pnp_iterate")
         return ((self.flags[:J] & FOUND) != 0, self.T[:J].view(J, 4, 4), (self.flags[:J] & NO_MORE) != 0, self.inliers,
                 self.n_inliers[:J])
-
-    def job_inliers(self, j):
-        """vbInliers of job j (host bool [mN])."""
-        return self.inliers[int(self.inl_start[j]):int(self.inl_start[j + 1])].cpu().numpy().astype(bool)
 
     def hypotheses(self, j=0):
         """What job j did in the last iterate call (the library's test hook): dict of host arrays over its H hypotheses
@@ -133,11 +94,6 @@ class MLPnPsolver:
                                            ctypes.byref(n_ref), _lib.ptr(ri), _lib.ptr(rp), _lib.ptr(rw), _lib.ptr(state),
                                            _lib.ptr(prep), self._stream()), "omv_pnp_debug")
 
-        def unpack(words, n):
-            words = words[:n, :W]
-            bits = (words[:, :, None] >> np.arange(64, dtype=np.uint64)[None, None, :]) & np.uint64(1)
-            return bits.reshape(n, 64 * W)[:, :N].astype(bool), words
-
         def poses(p, n):
             p = p[:n]
             return dict(R0=p[:, :9].reshape(n, 3, 3), t0=p[:, 9:12], R=p[:, 12:21].reshape(n, 3, 3), t=p[:, 21:24])
@@ -145,10 +101,10 @@ class MLPnPsolver:
         nh, nr = n_hyp.value, n_ref.value
         o = dict(idx=hi[:nh, :6], planar=hi[:nh, 6].astype(bool), its=hi[:nh, 7], reason=hi[:nh, 8], count=hi[:nh, 9],
                  **poses(hp, nh))
-        o["mask"], o["words"] = unpack(hw, nh)
+        o["mask"], o["words"] = self._unpack(hw, nh, j)
         r = dict(hyp=ri[:nr, 0], n_in=ri[:nr, 1], planar=ri[:nr, 2].astype(bool), its=ri[:nr, 3], reason=ri[:nr, 4],
                  count=ri[:nr, 5], ok=ri[:nr, 6].astype(bool), **poses(rp, nr))
-        r["mask"], r["words"] = unpack(rw, nr)
+        r["mask"], r["words"] = self._unpack(rw, nr, j)
         o["refine"] = r
         o["state"] = dict(zip(("iterations", "best", "refined_valid", "refined_count", "refined_ok", "out_kind"),
                               (int(x) for x in state)))

@@ -18,9 +18,9 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .ransac import RAND_MAX, BatchedRansac, draw   # RAND_MAX and draw stay importable from here
 
 NO_MORE, CONVERGE = 1, 2
-RAND_MAX = 2147483647
 
 
 def select_correspondences(indices1, indices2, valid=None):
@@ -43,19 +43,6 @@ def select_correspondences(indices1, indices2, valid=None):
     return int(c1), int(c2), idx, i1[idx, c1].astype(np.int32), i2[idx, c2].astype(np.int32)
 
 
-def draw(rng_or_rand, n_iterations, n, k=3):
-    """Raw draws [n_iterations][k] for a job with n correspondences by DUtils::Random::RandomInt's formula
-    (Thirdparty/DBoW2/DUtils/Random.cpp:47-50): int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min with
-    d = n - i for the i-th pick (k = 3 for Sim3Solver, 6 for MLPnPsolver).  rng_or_rand: a callable returning rand()
-    values in [0, RAND_MAX], or a numpy.random.Generator (then rand() is its integers(0, RAND_MAX + 1))."""
-    if callable(rng_or_rand):
-        r = np.array([[rng_or_rand() for _ in range(k)] for _ in range(n_iterations)], np.float64).reshape(-1, k)
-    else:
-        r = rng_or_rand.integers(0, RAND_MAX + 1, (n_iterations, k)).astype(np.float64)
-    d = np.maximum(n - np.arange(k), 1).astype(np.float64)
-    return ((r / (RAND_MAX + 1.0)) * d).astype(np.int32)
-
-
 def to_sim3f(R, t, s):
     """(S12, S21) as the omv_sim3f dicts ORBmatcher.SearchBySim3 takes (q = unit quaternion (x, y, z, w) * sqrt(scale),
     scale = |q|^2 in float), from GetEstimatedRotation / Translation / Scale: S12 = (R, t, s), S21 its inverse."""
@@ -70,34 +57,13 @@ def to_sim3f(R, t, s):
     return one(R, t, s), one(R.T, -(R.T @ t) / s, 1.0 / s)
 
 
-class Sim3Solver:
+class Sim3Solver(BatchedRansac):
+    K, _CREATE, _DESTROY = 3, "omv_sim3_solver_create", "omv_sim3_solver_destroy"
+
     def __init__(self, jobs, max_hyp=300, device="cuda:0", stream=None):
-        import torch
-        self._torch, self._lib, self.device, self.stream = torch, _lib.load(), device, stream
-        self.jobs = list(jobs)
-        J = self.n_jobs = len(self.jobs)
-        self.n = np.array([len(j["index1"]) for j in self.jobs], np.int32)
-        self.mN1 = np.array([int(j["mN1"]) for j in self.jobs], np.int32)
-        self.corr_start = np.concatenate([[0], np.cumsum(self.n)]).astype(np.int32)
-        self.inl_start = np.concatenate([[0], np.cumsum(self.mN1)]).astype(np.int64)
-        self.max_hyp = int(max_hyp)
-        self._h = ctypes.c_void_p()
-        _lib.check(self._lib.omv_sim3_solver_create(max(J, 1), int(self.corr_start[-1]), self.max_hyp,
-                                                    ctypes.byref(self._h)), "omv_sim3_solver_create")
-        self.T12 = torch.zeros((max(J, 1), 16), dtype=torch.float32, device=device)
-        self.n_inliers = torch.zeros(max(J, 1), dtype=torch.int32, device=device)
-        self.flags = torch.zeros(max(J, 1), dtype=torch.int32, device=device)
-        self.inliers = torch.zeros(max(int(self.inl_start[-1]), 1), dtype=torch.uint8, device=device)
+        super().__init__(jobs, "index1", "mN1", max_hyp, device, stream)
+        self.mN1, self.T12 = self._mn, self._T
         self.SetRansacParameters()   # the constructor's last line (:181): 0.99, 6, 300
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.omv_sim3_solver_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def _stream(self):
-        s = self.stream if self.stream is not None else self._torch.cuda.current_stream()
-        return ctypes.c_void_p(s.cuda_stream)
 
     def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
         """minInliers: one value or one per job.  Uploads the jobs and resets the carried state; mRansacMaxIts per job is
@@ -109,12 +75,7 @@ class Sim3Solver:
         """omv_sim3_solver_set on self.jobs; returns the status."""
         J = self.n_jobs
         mi = np.broadcast_to(np.asarray(minInliers, np.int32), (J,)).copy()
-
-        def cat(key, dt, width):
-            if not J:
-                return np.zeros((0, width), dt)
-            return np.ascontiguousarray(np.concatenate([np.asarray(j[key], dt).reshape(-1, width) for j in self.jobs]))
-
+        cat = self._cat
         arrs = [self.corr_start, cat("Xw1", np.float32, 3), cat("Xw2", np.float32, 3), cat("sigma2_1", np.float32, 1),
                 cat("sigma2_2", np.float32, 1), cat("index1", np.int32, 1), self.mN1, cat("pose1", np.float32, 12),
                 cat("pose2", np.float32, 12), cat("cam1", np.float32, 8), cat("cam2", np.float32, 8),
@@ -127,19 +88,11 @@ class Sim3Solver:
             self.max_its, self.min_inliers = max_its[:J], mi
         return status
 
-    def draw(self, rng_or_rand, n_iterations):
-        """Raw draws [n_jobs][n_iterations][3] (int32, host), job after job."""
-        return np.stack([draw(rng_or_rand, n_iterations, int(n)) for n in self.n]) if self.n_jobs else \
-            np.zeros((0, n_iterations, 3), np.int32)
-
     def iterate(self, nIterations, draws):
         """The 5-argument iterate for every job.  draws: [n_jobs][nIterations][3] int32, host array or device tensor.
         Returns device tensors (T12 [J][4][4], bNoMore [J], vbInliers (flat uint8; job j at inl_start[j]), nInliers [J],
         bConverge [J]); nothing is synchronised."""
-        torch = self._torch
-        if not torch.is_tensor(draws):
-            draws = torch.from_numpy(np.ascontiguousarray(draws, np.int32))
-        draws = draws.to(self.device, torch.int32).contiguous()
+        draws = self._device_draws(draws)
         assert draws.numel() == self.n_jobs * nIterations * 3, "draws: [n_jobs][nIterations][3]"
         _lib.check(self._lib.omv_sim3_solver_iterate(self._h, int(nIterations), _lib.ptr(draws), _lib.ptr(self.T12),
                                                      _lib.ptr(self.n_inliers), _lib.ptr(self.inliers),
@@ -155,10 +108,6 @@ class Sim3Solver:
         T12, _, vb, n, conv = self.iterate(n_it, draws)
         eye = self._torch.eye(4, dtype=T12.dtype, device=T12.device).expand_as(T12)
         return self._torch.where(conv[:, None, None], T12, eye), vb, n
-
-    def job_inliers(self, j):
-        """vbInliers of job j (host bool [mN1])."""
-        return self.inliers[int(self.inl_start[j]):int(self.inl_start[j + 1])].cpu().numpy().astype(bool)
 
     def _best(self, j):
         R, t = np.zeros(9, np.float32), np.zeros(3, np.float32)
@@ -184,8 +133,7 @@ class Sim3Solver:
     def hypotheses(self, j=0):
         """The hypotheses job j evaluated in the last iterate call (the library's test hook): dict of host arrays idx
         [H][3], R [H][3][3], t [H][3], s [H], T12, T21 [H][4][4], count [H], mask [H][N] bool."""
-        H, N = self.max_hyp, int(self.n[j])
-        W = (N + 63) // 64
+        H, W = self.max_hyp, (int(self.n[j]) + 63) // 64
         n_hyp = ctypes.c_int32()
         o = dict(idx=np.zeros((H, 3), np.int32), R=np.zeros((H, 3, 3), np.float32), t=np.zeros((H, 3), np.float32),
                  s=np.zeros(H, np.float32), T12=np.zeros((H, 4, 4), np.float32), T21=np.zeros((H, 4, 4), np.float32),
@@ -195,8 +143,5 @@ class Sim3Solver:
             _lib.ptr(o[k]) for k in ("idx", "R", "t", "s", "T12", "T21", "count")], _lib.ptr(words), self._stream()),
             "omv_sim3_solver_debug")
         o = {k: v[:n_hyp.value] for k, v in o.items()}
-        words = words[:n_hyp.value, :W]
-        bits = (words[:, :, None] >> np.arange(64, dtype=np.uint64)[None, None, :]) & np.uint64(1)
-        o["mask"] = bits.reshape(len(words), 64 * W)[:, :N].astype(bool)
-        o["words"] = words
+        o["mask"], o["words"] = self._unpack(words, n_hyp.value, j)
         return o

@@ -11,12 +11,12 @@ import math
 
 import numpy as np
 
+import ransac_ref
 from sim3_ref import project
 
 NO_MORE, FOUND = 1, 2
 EPS = float(np.finfo(np.float64).eps)
 DBL_MIN = float(np.finfo(np.float64).tiny)
-INT_MIN = -2 ** 31
 GN_MAXIT, GN_EPSP, GN_BREAK, GN_NAN = 0, 1, 2, 3
 NEAR = 2.0 ** -20
 DEFAULTS = (0.99, 8, 300, 6, 0.4, 5.991)     # include/MLPnPsolver.h:19-25
@@ -30,49 +30,18 @@ def ransac_parameters(n, prob=0.99, min_inliers=8, max_its=300, min_set=6, epsil
     x86) counts as INT_MIN."""
     n_min = int(np.float32(n) * np.float32(epsilon))
     n_min = max(n_min, min_inliers, min_set)
-    eps = np.float32(epsilon)
     with np.errstate(all="ignore"):
-        q = np.float32(n_min) / np.float32(n)
-        if eps < q:
-            eps = q
-        if n_min == n:
-            n_it = 1
-        else:
-            e3 = math.pow(float(eps), 3.0) if np.isfinite(eps) else float(eps)
-            v = np.ceil(np.log(np.float64(1 - prob)) / np.log(np.float64(1) - np.float64(e3)))
-            n_it = int(v) if np.isfinite(v) and -2 ** 31 <= v < 2 ** 31 else INT_MIN
-    return max(1, min(n_it, max_its)), n_min
+        eps = max(np.float32(epsilon), np.float32(n_min) / np.float32(n))
+    return ransac_ref.ransac_its(prob, eps, n_min == n, max_its), n_min
 
 
 # ---- the sampling of iterate (:79-98) ------------------------------------------------------------------------------
 def sample_literal(n, r, k=6):
-    """The k picks by the literal shrinking list with swap-with-back removal; draws are clamped into their range."""
-    avail, out = list(range(n)), []
-    for i in range(k):
-        ri = min(max(int(r[i]), 0), len(avail) - 1)
-        out.append(avail[ri])
-        avail[ri] = avail[-1]
-        avail.pop()
-    return out
+    return ransac_ref.sample_literal(n, r, k)
 
 
 def sample_replay(n, r, k=6):
-    """The same picks without the list (what the device evaluates): position p holds the value the latest earlier pick
-    that removed from p moved there, else p."""
-    pos, val, out = [], [], []
-    for i in range(k):
-        size = n - i
-        ri = min(max(int(r[i]), 0), size - 1)
-        at_r, at_back = ri, size - 1
-        for pj, vj in zip(pos, val):
-            if pj == ri:
-                at_r = vj
-            if pj == size - 1:
-                at_back = vj
-        out.append(at_r)
-        pos.append(ri)
-        val.append(at_back)
-    return out
+    return ransac_ref.sample_replay(n, r, k)
 
 
 # ---- the constructor (:28-45) --------------------------------------------------------------------------------------

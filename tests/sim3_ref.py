@@ -6,49 +6,30 @@ float32-rounded N), whose error against the float64 result is the e_ref of tests
 
 A job is a dict: Xw1, Xw2 [N][3] float32, sigma2_1, sigma2_2 [N] float32, index1 [N] int32, mN1, pose1, pose2 [12]
 (Riw row-major, tiw), cam1, cam2 [8], model1, model2 (0 KB8, 1 Pinhole), fix_scale."""
-import math
-
 import numpy as np
+
+import ransac_ref
 
 U32 = 2.0 ** -24
 NO_MORE, CONVERGE = 1, 2
-INT_MIN = -2 ** 31
 
 
 # ---- SetRansacParameters (:184-207) -------------------------------------------------------------------------------
 def ransac_max_its(prob, min_inliers, n, max_its):
-    """mRansacMaxIts in the reference's types: float epsilon, double pow / log / ceil, int min / max.  A NaN or
-    out-of-range double -> int conversion (undefined in C++, INT_MIN on x86) counts as INT_MIN."""
-    if min_inliers == n:
-        n_it = 1
-    else:
-        eps = float(np.float32(min_inliers) / np.float32(n))
-        with np.errstate(all="ignore"):
-            v = np.ceil(np.log(np.float64(1 - prob)) / np.log(np.float64(1) - np.float64(math.pow(eps, 3.0))))
-        n_it = int(v) if np.isfinite(v) and -2 ** 31 <= v < 2 ** 31 else INT_MIN
-    return max(1, min(n_it, max_its))
+    """mRansacMaxIts: epsilon = (float)mRansacMinInliers / N, then the shared tail."""
+    return ransac_ref.ransac_its(prob, np.float32(min_inliers) / np.float32(n), min_inliers == n, max_its)
 
 
 # ---- the sampling of iterate (:230-243) --------------------------------------------------------------------------
 def sample_literal(n, r):
-    """The three picks by the literal shrinking list with swap-with-back removal."""
-    avail = list(range(n))
-    out = []
-    for i in range(3):
-        assert 0 <= r[i] <= len(avail) - 1
-        out.append(avail[r[i]])
-        avail[r[i]] = avail[-1]
-        avail.pop()
-    return out
+    """The three picks by the literal shrinking list; the draws must be in range."""
+    assert all(0 <= r[i] <= n - 1 - i for i in range(3))
+    return ransac_ref.sample_literal(n, r, 3)
 
 
 def sample_replay(n, r):
-    """The same picks in closed form (what the device evaluates)."""
-    r0, r1, r2 = (int(x) for x in r)
-    back1 = n - 1 if r0 == n - 2 else n - 2
-    i1 = n - 1 if r1 == r0 else r1
-    i2 = back1 if r2 == r1 else (n - 1 if r2 == r0 else r2)
-    return [r0, i1, i2]
+    """The same picks as the device evaluates them."""
+    return ransac_ref.sample_replay(n, r, 3)
 
 
 # ---- cameras, float64 ------------------------------------------------------------------------------------------
