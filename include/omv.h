@@ -168,6 +168,11 @@ omv_status omv_matcher_search_projection(omv_matcher *m, int n_frames, const omv
                                          int far_points, float th_far, float nnratio, const int32_t *l2r,
                                          const int32_t *r2l, const uint8_t *kp_occ_init, int32_t *kp_to_mp,
                                          int *n_matches, void *stream);
+/* Copy the candidate records of the last search_projection call (n_frames frames, M points) to host: out
+ * [n_frames][M][n_cams][16] words, idx | dist << 16 | octave << 25 | bit 31 valid (bit 30 of word 0: the window held
+ * more than 16 unblocked candidates).  Only (point, camera) slots in view with a valid predicted level have a record;
+ * the other slots' words are unspecified. Syncs. */
+omv_status omv_matcher_records_debug(omv_matcher *m, int n_frames, int M, uint32_t *out);
 
 /* Lapping-area stereo candidates of Frame::ComputeMultiFishEyeMatches (src/Frame.cc:1461-1491):
  * knnMatch(k=2) of camera-0 rows [mono0, n0) against camera-1 rows [mono1, n1), Lowe ratio

@@ -287,6 +287,7 @@ SIGNATURES = {
     "omv_matcher_destroy": (_I, [_VP]),
     "omv_matcher_assign_grid": (_I, [_VP, _I, ctypes.POINTER(FrameGeom), _VP, _VP, _VP]),
     "omv_matcher_grid_debug": (_I, [_VP, _I, _I, _VP, _VP]),
+    "omv_matcher_records_debug": (_I, [_VP, _I, _I, _VP]),
     "omv_matcher_enable_timing": (_I, [_VP, _I]),
     "omv_matcher_last_error": (_I, [_VP]),
     "omv_matcher_stage_ms": (_I, [_VP, _VP, _I]),

@@ -246,6 +246,49 @@ struct TopSeq {
     }
 };
 
+// The same list for the lanes that share one window of a camera staged in LDS: 32-bit keys dist << 16 | p, p the
+// entry's position in the camera's cell-sorted keypoints.  A window walks its columns in ascending order and a
+// column's cells are one ascending run of p, so p ascends in window order: keys are unique and sort by (distance,
+// window order), the strict `<` scans' tie rule, whichever lane inserts them and in whatever order.
+struct TopPos {
+    uint32_t key[kTop];
+    int count;
+    __device__ __forceinline__ void reset() {
+#pragma unroll
+        for (int q = 0; q < kTop; ++q) key[q] = ~0u;
+        count = 0;
+    }
+    __device__ __forceinline__ void insert(int p, int dist) {
+        const uint32_t k = ((uint32_t)dist << 16) | (uint32_t)p;
+#pragma unroll
+        for (int q = kTop - 1; q > 0; --q) key[q] = k < key[q - 1] ? key[q - 1] : min(k, key[q]);
+        key[0] = min(k, key[0]);
+    }
+    // The kTop smallest keys of a G-lane group (G a power of two, the same for the whole wavefront) into every lane of
+    // it, counts summed: log2 G rounds in which a lane and its partner lane ^ s exchange their sorted lists.
+    // min(a[q], b[kTop - 1 - q]) holds the kTop smallest of both as a bitonic sequence, which four half-cleaner
+    // stages sort; both partners compute the same list.
+    __device__ __forceinline__ void merge(int G) {
+        for (int s = 1; s < G; s <<= 1) {
+            uint32_t o[kTop];
+#pragma unroll
+            for (int q = 0; q < kTop; ++q) o[q] = (uint32_t)__shfl_xor((int)key[q], s, 64);
+            count += __shfl_xor(count, s, 64);
+#pragma unroll
+            for (int q = 0; q < kTop; ++q) key[q] = min(key[q], o[kTop - 1 - q]);
+#pragma unroll
+            for (int d = kTop / 2; d > 0; d >>= 1) {
+#pragma unroll
+                for (int q = 0; q < kTop; ++q) {
+                    if (q & d) continue;
+                    const uint32_t lo = min(key[q], key[q + d]), hi = max(key[q], key[q + d]);
+                    key[q] = lo, key[q + d] = hi;
+                }
+            }
+        }
+    }
+};
+
 // Window of GetFeaturesInArea(x, y, r, level-1, level, cam), in the reference's iteration order;
 // keeps the kTop best unblocked candidates by (dist, order).
 template <class Blocked, class TopT>
@@ -467,6 +510,10 @@ __global__ void __launch_bounds__(256, 4) cand_kernel(FrameArgs f, MpArgs m, int
 // (cell index -> keypoint and descriptor) per (map point, camera); here a window step is two LDS reads, the
 // descriptor only for entries that pass the level / radius / blocked tests, and the cell-index hop is gone
 // (entries sit in CSR order).  Same window order and tie rule as scan_window, hence the same records.
+// A launch's time is the sum of its workgroups' lifetimes over the CUs' places, and a workgroup lives as long as its
+// slowest wave: the waves draw tasks of 64 windows from one queue, largest first, and a window of more than `split`
+// entries (OMV_CAND_SPLIT) is dealt to several lanes (TopPos, scan_window_lds_coop).  -DOMV_STAGE_PROFILE prints the
+// phases' times of one frame's workgroups.
 constexpr int kStageThreads = 512;
 constexpr uint32_t kStageBlocked = 1u << 31;
 constexpr size_t kStageLdsMax = 80 * 1024;   // two workgroups per CU
@@ -474,9 +521,57 @@ constexpr int kScanGroup = 4;                 // window entries read per LDS rou
 constexpr int kStageUnroll = 3;               // staged entries per thread per pass (1,536 per pass)
 constexpr int kStageMaxIt = 4;                // map points per wave <= 256
 constexpr int kStageBuckets = 32;             // window-size classes: 2 x predicted level (nlevels <= 16)
+constexpr int kStageClasses = 7;              // split classes: a window's entries dealt to G = 1, 2, ... 64 lanes
+constexpr int kStageKeys = kStageClasses * kStageBuckets;   // sort keys: split class, then window-size class
+constexpr int kStageSplit = 64;               // window entries per lane above which a window takes more lanes
 
 __host__ __device__ inline size_t stage_lds_bytes(int kp_cap, int pw) {
     return (size_t)kp_cap * (32 + 8 + 4) + (size_t)(kCells + 1) * 4 + (size_t)(kStageThreads / 64) * pw * 4;
+}
+
+// One run of a staged camera's entries, pb, pb + (1 << sh), ... (cnt of them), against a window: first the cheap
+// tests (level, radius, blocked) on every entry, kScanGroup entries per LDS round trip, the passing ones marked in a
+// 32-bit mask; then the descriptor read, the distance and ins(p, meta, dist) for the marked entries alone, in
+// ascending order.  A wavefront pays the second, expensive part as often as its lane with the most passing entries
+// in the pass, not once per entry that passes on any lane.  Reads past the run repeat its first entry and are
+// masked.  Returns how many entries passed.
+template <class Ins>
+__device__ __forceinline__ int scan_run_lds(int pb, int sh, int cnt, float x, float y, float r, bool checkLevels,
+                                            int minL, int maxL, const uint64_t dmp[4], const float2 *sxy,
+                                            const uint32_t *smeta, const uint4 *sdesc, Ins ins) {
+    int found = 0;
+    for (int k0 = 0; k0 < cnt; k0 += 32) {
+        const int nk = min(32, cnt - k0);
+        uint32_t mask = 0;
+        for (int u0 = 0; u0 < nk; u0 += kScanGroup) {
+            float2 k[kScanGroup];
+            uint32_t meta[kScanGroup];
+#pragma unroll
+            for (int u = 0; u < kScanGroup; ++u) {
+                const int p = pb + ((u0 + u < nk ? k0 + u0 + u : k0) << sh);
+                k[u] = sxy[p], meta[u] = smeta[p];
+            }
+#pragma unroll
+            for (int u = 0; u < kScanGroup; ++u) {
+                const int oct = (int)((meta[u] >> 16) & 0x7f);
+                bool ok = u0 + u < nk;   // then omv::kp_in_window written out
+                if (checkLevels) ok = ok && oct >= minL && !(maxL >= 0 && oct > maxL);
+                ok = ok && fabsf(k[u].x - x) < r && fabsf(k[u].y - y) < r && !(meta[u] & kStageBlocked);
+                mask |= (uint32_t)ok << (u0 + u);
+            }
+        }
+        found += __popc(mask);
+        while (mask) {
+            const int p = pb + ((k0 + __ffs((int)mask) - 1) << sh);
+            mask &= mask - 1;
+            const uint32_t meta = smeta[p];
+            const uint4 a = sdesc[2 * p], b = sdesc[2 * p + 1];
+            const uint64_t d[4] = {(uint64_t)a.x | ((uint64_t)a.y << 32), (uint64_t)a.z | ((uint64_t)a.w << 32),
+                                   (uint64_t)b.x | ((uint64_t)b.y << 32), (uint64_t)b.z | ((uint64_t)b.w << 32)};
+            ins(p, meta, omv::hamming256(dmp, d));
+        }
+    }
+    return found;
 }
 
 __device__ __forceinline__ void scan_window_lds(const FrameArgs &f, float x, float y, float r, int minL, int maxL,
@@ -486,31 +581,48 @@ __device__ __forceinline__ void scan_window_lds(const FrameArgs &f, float x, flo
     omv::GridRange w;
     OMV_GRID_WINDOW_OR(x, y, r, f.min_x, f.min_y, f.invW, f.invH, w, return)
     const bool checkLevels = (minL > 0) || (maxL >= 0);
-    // a column's run in groups of kScanGroup entries: the group's position / meta reads go out together (one LDS
-    // round trip per group instead of per entry; reads past the run stay inside the staged arrays and are masked)
     for (int ix = w.x0; ix <= w.x1; ++ix) {
-        const int e = scs[ix * kGridRows + w.y1 + 1];
-        for (int p0 = scs[ix * kGridRows + w.y0]; p0 < e; p0 += kScanGroup) {
-            float2 k[kScanGroup];
-            uint32_t meta[kScanGroup];
-#pragma unroll
-            for (int u = 0; u < kScanGroup; ++u) k[u] = sxy[p0 + u], meta[u] = smeta[p0 + u];
-#pragma unroll
-            for (int u = 0; u < kScanGroup; ++u) {
-                const int oct = (int)((meta[u] >> 16) & 0x7f);
-                bool ok = p0 + u < e;   // then omv::kp_in_window written out: the call moves the kernel's VGPRs (88 -> 80)
-                if (checkLevels) ok = ok && oct >= minL && !(maxL >= 0 && oct > maxL);
-                ok = ok && fabsf(k[u].x - x) < r && fabsf(k[u].y - y) < r && !(meta[u] & kStageBlocked);
-                if (!ok) continue;
-                const int p = p0 + u;
-                const uint4 a = sdesc[2 * p], b = sdesc[2 * p + 1];
-                const uint64_t d[4] = {(uint64_t)a.x | ((uint64_t)a.y << 32), (uint64_t)a.z | ((uint64_t)a.w << 32),
-                                       (uint64_t)b.x | ((uint64_t)b.y << 32), (uint64_t)b.z | ((uint64_t)b.w << 32)};
-                ++t.count;
-                t.insert((int)(meta[u] & 0xffff), omv::hamming256(dmp, d), oct);
-            }
-        }
+        const int b = scs[ix * kGridRows + w.y0], e = scs[ix * kGridRows + w.y1 + 1];
+        t.count += scan_run_lds(b, 0, e - b, x, y, r, checkLevels, minL, maxL, dmp, sxy, smeta, sdesc,
+                                [&](int, uint32_t meta, int dist) {
+                                    t.insert((int)(meta & 0xffff), dist, (int)((meta >> 16) & 0x7f));
+                                });
     }
+}
+
+// scan_window_lds over G = 1 << sh cooperating lanes (g = the lane's rank in its group): lane g walks window
+// positions g, g + G, ... in the reference's order (columns ascending, each column's CSR run) with the same tests;
+// TopPos keys make the group's merged list the one lane's list.
+__device__ __forceinline__ void scan_window_lds_coop(const omv::GridRange &w, float x, float y, float r, int minL, int maxL,
+                                                     const uint64_t dmp[4], const int *scs, const float2 *sxy,
+                                                     const uint32_t *smeta, const uint4 *sdesc, TopPos &t, int g, int sh) {
+    const bool checkLevels = (minL > 0) || (maxL >= 0);
+    int pos = g, acc = 0;   // this lane's next window position; window positions before the current column
+    for (int ix = w.x0; ix <= w.x1; ++ix) {
+        const int b = scs[ix * kGridRows + w.y0], end = acc + scs[ix * kGridRows + w.y1 + 1] - b;
+        if (pos < end) {
+            const int cnt = (end - pos + (1 << sh) - 1) >> sh;   // this lane's entries of the column
+            t.count += scan_run_lds(b + pos - acc, sh, cnt, x, y, r, checkLevels, minL, maxL, dmp, sxy, smeta, sdesc,
+                                    [&](int p, uint32_t, int dist) { t.insert(p, dist); });
+            pos += cnt << sh;
+        }
+        acc = end;
+    }
+}
+
+// The merged list of a split window as a record: the keypoint index and octave of entry p come from its meta word.
+__device__ __forceinline__ void store_record_pos(Rec *dst, const TopPos &t, const uint32_t *smeta) {
+    uint4 *o4 = reinterpret_cast<uint4 *>(dst);
+    uint32_t w[kTop];
+#pragma unroll
+    for (int q = 0; q < kTop; ++q) {
+        const uint32_t k = t.key[q];
+        const uint32_t meta = smeta[k == ~0u ? 0u : (k & 0xffffu)];
+        w[q] = k == ~0u ? 0u : ((meta & 0xffffu) | ((k >> 16) << 16) | (((meta >> 16) & 0x7fu) << 25) | kRecValid);
+    }
+    w[0] |= t.count > kTop ? kRecOver : 0u;
+#pragma unroll
+    for (int v = 0; v < kTop / 4; ++v) o4[v] = make_uint4(w[4 * v], w[4 * v + 1], w[4 * v + 2], w[4 * v + 3]);
 }
 
 // blockIdx -> (frame, cam, chunk) logical block, XCD-aware: a (frame, camera)'s chunks share one XCD's L2 for
@@ -518,7 +630,7 @@ __device__ __forceinline__ void scan_window_lds(const FrameArgs &f, float x, flo
 __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, MpArgs m, int n_frames, float th,
                                                                    const uint8_t *occ_init, Rec *recs, int *counts,
                                                                    int *flags, int far_points, float th_far,
-                                                                   int n_chunks, int pw, int n_blocks) {
+                                                                   int n_chunks, int pw, int n_blocks, int split) {
     extern __shared__ __align__(16) unsigned char stage_lds[];
     const int C = f.n_cams, cap = f.kp_cap, M = m.M;
     const int blk = omv::xcd_block(n_blocks);
@@ -529,9 +641,11 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
     uint32_t *smeta = reinterpret_cast<uint32_t *>(stage_lds + (size_t)cap * 40);
     int *scs = reinterpret_cast<int *>(stage_lds + (size_t)cap * 44);
     int *queue = scs + kCells + 1;   // [8 * pw] the chunk's active points (workgroup-local index), sorted
-    __shared__ int bucket[kStageBuckets + 1];
+    __shared__ int bucket[kStageKeys + 1];
+    __shared__ int next_task;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (tid <= kStageBuckets) bucket[tid] = 0;
+    if (tid <= kStageKeys) bucket[tid] = 0;
+    if (tid == 0) next_task = 0;
     __syncthreads();
     // Latency chains overlapped: the cell starts and the first staging pass's cell indices are loaded, then the
     // chunk's map-point activity, then the keypoints / descriptors behind those cell indices.
@@ -540,7 +654,11 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
     const omv_kp *kp = f.kps + (size_t)fc * cap;
     const uint4 *dd = reinterpret_cast<const uint4 *>(f.desc + (size_t)fc * cap * 32);
     const uint8_t *occ = occ_init ? occ_init + ((size_t)frame * C + cam) * cap : nullptr;
+#ifdef OMV_STAGE_PROFILE
+    long long tp[4] = {wall_clock64(), 0, 0, 0};
+#endif
     const int n_in = cs[kCells];
+    const bool balance = split < n_in;   // else no window of this camera can hold more than `split` entries
     for (int c = tid; c <= kCells; c += kStageThreads) scs[c] = cs[c];
     int idx[kStageUnroll];
 #pragma unroll
@@ -548,13 +666,14 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
         const int p = u * kStageThreads + tid;
         idx[u] = p < n_in ? ci[p] : -1;
     }
-    // The chunk's map points: the in-view ones with a valid predicted level counting-sorted by window size
-    // (predicted level, RadiusByViewingCos) into one workgroup queue, so that a wavefront's 64 lanes walk windows of
-    // similar length (a wave takes the time of its longest window).
+    // The chunk's map points: the in-view ones with a valid predicted level counting-sorted into one workgroup queue
+    // by split class (the lanes their window is dealt to, below) and inside a class by window size (predicted level,
+    // RadiusByViewingCos), so that a wavefront's 64 lanes walk runs of similar length (a wave takes the time of its
+    // longest lane).
     const int p0 = chunk * (kStageThreads / 64) * pw;
     int key[kStageMaxIt], lv[kStageMaxIt];
     bool iv[kStageMaxIt];
-    float vc[kStageMaxIt];
+    float vc[kStageMaxIt], px[kStageMaxIt], py[kStageMaxIt];
 #pragma unroll
     for (int it = 0; it < kStageMaxIt; ++it) {
         const int i = p0 + wave * pw + it * 64 + lane;
@@ -563,6 +682,7 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
         iv[it] = valid && m.in_view[bc];
         lv[it] = valid ? m.level[bc] : -1;
         vc[it] = valid ? m.view_cos[bc] : 0.0f;
+        px[it] = m.proj_x[bc], py[it] = m.proj_y[bc];
     }
 #pragma unroll
     for (int it = 0; it < kStageMaxIt; ++it) {
@@ -575,7 +695,7 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
         }
         if (iv[it] && lv[it] >= 0 && lv[it] < f.nlevels) {   // only these have records (resolve's visit skips the
             key[it] = 2 * lv[it] + (vc[it] > 0.998 ? 0 : 1);   // others before it reads one)
-            atomicAdd(&bucket[key[it]], 1);
+            if (!balance) atomicAdd(&bucket[key[it]], 1);
         }
     }
     // stage the grid-ordered keypoints: kStageUnroll entries per thread per pass, all cell-index loads first, then all
@@ -608,30 +728,102 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
             sdesc[2 * p] = da[u], sdesc[2 * p + 1] = db[u];
         }
     }
-    __syncthreads();   // staging and bucket counts complete
-    if (tid < 64) {    // exclusive scan of the 32 bucket counts
-        const int c = tid < kStageBuckets ? bucket[tid] : 0;   // lanes past the buckets add 0 behind them
-        const int incl = omv::wave_incl_scan_i32(c, lane);
-        if (tid < kStageBuckets) bucket[tid] = incl - c;
-        if (tid == kStageBuckets - 1) bucket[kStageBuckets] = incl;
+    __syncthreads();   // staging (and, unbalanced, the bucket counts) complete
+#ifdef OMV_STAGE_PROFILE
+    tp[1] = wall_clock64();
+#endif
+    if (balance) {
+        // Split class of each active slot: its window's exact entry count from the staged cell starts, dealt to
+        // G = 2^class lanes, the fewest that leave a lane at most `split` entries (64 at the most).
+#pragma unroll
+        for (int it = 0; it < kStageMaxIt; ++it) {
+            if (key[it] < 0) continue;
+            float r = vc[it] > 0.998 ? 2.5f : 4.0f;   // window_radius() on the values loaded above
+            if (cam == 0 && th != 1.0f) r *= th;
+            r *= f.scale[lv[it]];
+            omv::GridRange w;
+            int entries = 0;
+            if (omv::grid_window(px[it], py[it], r, f.min_x, f.min_y, f.invW, f.invH, w))
+                for (int ix = w.x0; ix <= w.x1; ++ix) entries += scs[ix * kGridRows + w.y1 + 1] - scs[ix * kGridRows + w.y0];
+            int cls = 0;   // split < 2^24 and entries < 2^16: no shift overflows
+#pragma unroll
+            for (int k = 0; k < kStageClasses - 1; ++k) cls += entries > (split << k);
+            key[it] += cls * kStageBuckets;
+            atomicAdd(&bucket[key[it]], 1);
+        }
+        __syncthreads();
+    }
+    if (tid < 64) {    // exclusive scan of the bucket counts, four per lane
+        int c[4], s = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = 4 * tid + k < kStageKeys ? bucket[4 * tid + k] : 0, s += c[k];
+        int run = omv::wave_incl_scan_i32(s, lane) - s;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (4 * tid + k < kStageKeys) bucket[4 * tid + k] = run;
+            run += c[k];
+        }
+        if (tid == 63) bucket[kStageKeys] = run;
     }
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < kStageMaxIt; ++it)
         if (key[it] >= 0) queue[atomicAdd(&bucket[key[it]], 1)] = wave * pw + it * 64 + lane;
     __syncthreads();
-    const int nq = bucket[kStageBuckets];
-    for (int q = wave * 64 + lane; q - lane < nq; q += kStageThreads) {
-        if (q >= nq) break;
+    // Each bucket's cursor now stands at its end.  A class's run of the queue is cut into wave tasks of 64 / G slots,
+    // G lanes each, and the eight waves draw tasks from one counter, the widest class first and each class from its
+    // largest windows down: the long tasks start early on every wave and the short ones fill in behind them (with the
+    // largest windows last, the wave that drew them ran on alone while seven waited).
+#ifdef OMV_STAGE_PROFILE
+    tp[2] = wall_clock64();
+#endif
+    int cend[kStageClasses];
+#pragma unroll
+    for (int k = 0; k < kStageClasses; ++k)
+        cend[k] = __builtin_amdgcn_readfirstlane(bucket[k * kStageBuckets + kStageBuckets - 1]);
+    for (;;) {
+        int rem = 0;
+        if (lane == 0) rem = atomicAdd(&next_task, 1);
+        rem = __builtin_amdgcn_readfirstlane(rem);
+        int cls = -1, q0 = 0, q1 = 0;
+#pragma unroll
+        for (int k = kStageClasses - 1; k >= 0; --k) {
+            const int st = k ? cend[k - 1] : 0, sh = 6 - k, nt = (cend[k] - st + (1 << sh) - 1) >> sh;
+            if (cls < 0 && rem < nt) cls = k, q1 = cend[k] - (rem << sh), q0 = max(st, q1 - (1 << sh));
+            if (cls < 0) rem -= nt;
+        }
+        if (cls < 0) break;
+        const int G = 1 << cls, q = q0 + (lane >> cls);
+        if (q >= q1) continue;   // past the class's last slot: whole groups sit the task out together
         const int i = p0 + queue[q];
         const size_t fm = (size_t)frame * M + i, bc = fm * C + cam;
-        TopSeq t;
         uint64_t dmp[4];
         omv::load_desc(m.desc + fm * 32, dmp);
         const float r = window_radius(f, m, bc, cam, th, th != 1.0f);
-        scan_window_lds(f, m.proj_x[bc], m.proj_y[bc], r, m.level[bc] - 1, m.level[bc], dmp, scs, sxy, smeta, sdesc, t);
-        store_record(&recs[bc], t);
+        const float x = m.proj_x[bc], y = m.proj_y[bc];
+        const int lvl = m.level[bc];
+        if (cls == 0) {
+            TopSeq t;
+            scan_window_lds(f, x, y, r, lvl - 1, lvl, dmp, scs, sxy, smeta, sdesc, t);
+            store_record(&recs[bc], t);
+        } else {
+            TopPos t;
+            t.reset();
+            omv::GridRange w;
+            if (omv::grid_window(x, y, r, f.min_x, f.min_y, f.invW, f.invH, w))
+                scan_window_lds_coop(w, x, y, r, lvl - 1, lvl, dmp, scs, sxy, smeta, sdesc, t, lane & (G - 1), cls);
+            t.merge(G);
+            if ((lane & (G - 1)) == 0) store_record_pos(&recs[bc], t, smeta);
+        }
     }
+#ifdef OMV_STAGE_PROFILE
+    tp[3] = wall_clock64();
+    __syncthreads();
+    if (lane == 0 && frame == 1 && chunk <= 1)
+        printf("cand_stage cam %d chunk %d wave %d slots %d of them split %d ticks(100MHz): stage %lld sort %lld scan %lld wait %lld\n",
+               cam, chunk, wave, cend[kStageClasses - 1], cend[kStageClasses - 1] - cend[0], tp[1] - tp[0], tp[2] - tp[1],
+               tp[3] - tp[2], wall_clock64() - tp[3]);
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2457,6 +2649,7 @@ omv_status omv_matcher_create(int max_frames, int n_cams, int kp_cap, int max_mp
     if (const char *e = getenv("OMV_TRI_WALK")) h->knobs.tri_walk_seq = strcmp(e, "seq") == 0 ? 1 : 0;
     if (const char *e = getenv("OMV_CAND")) h->knobs.cand_mode = strcmp(e, "global") == 0 ? 1 : strcmp(e, "lds") == 0 ? 2 : 0;
     if (const char *e = getenv("OMV_CAND_PW")) h->knobs.cand_pw = atoi(e);
+    if (const char *e = getenv("OMV_CAND_SPLIT")) h->knobs.cand_split = (int)std::min<long long>(atoll(e), (1 << 24) - 1);
     h->knobs.knn_mode = knn_mode_env(), h->knobs.knn_idx_limit = knn_idx_limit_env();
     const size_t fc = (size_t)max_frames * n_cams;
     const size_t knn = (size_t)2 * max_frames * kp_cap;
@@ -2535,6 +2728,13 @@ omv_status omv_matcher_grid_debug(omv_matcher *h, int frame, int cam, int32_t *c
     return OMV_OK;
 }
 
+omv_status omv_matcher_records_debug(omv_matcher *h, int n_frames, int M, uint32_t *out) {
+    if (!h || !out || n_frames <= 0 || n_frames > h->max_frames || M <= 0 || M > h->max_mps) return OMV_ERR_ARG;
+    HIP_OK(hipStreamSynchronize(h->last));
+    HIP_OK(hipMemcpy(out, h->d_recs, sizeof(Rec) * n_frames * M * h->n_cams, hipMemcpyDeviceToHost));
+    return OMV_OK;
+}
+
 omv_status omv_matcher_search_projection(omv_matcher *h, int n_frames, const omv_frame_geom *g, const omv_kp *kps,
                                          const uint8_t *desc, const int *n_kp, const omv_mp_view *mps, int M, float th,
                                          int far_points, float th_far, float nnratio, const int32_t *l2r,
@@ -2565,7 +2765,8 @@ omv_status omv_matcher_search_projection(omv_matcher *h, int n_frames, const omv
             const int n_chunks = (M + 8 * pw - 1) / (8 * pw);
             const int nb = n_frames * h->n_cams * n_chunks;
             cand_stage_kernel<<<omv::xcd_grid(nb), kStageThreads, stage_lds_bytes(h->kp_cap, pw), st>>>(
-                f, m, n_frames, th, kp_occ_init, h->d_recs, h->d_counts, h->d_flags, far_points, th_far, n_chunks, pw, nb);
+                f, m, n_frames, th, kp_occ_init, h->d_recs, h->d_counts, h->d_flags, far_points, th_far, n_chunks, pw, nb,
+                h->knobs.cand_split > 0 ? h->knobs.cand_split : kStageSplit);
         } else if (tot <= 65536) {   // a frame or two: 16 lanes per window (the longest window sets the time)
             const int nb = (int)((tot + 4 * (kCandChunk / 16) - 1) / (4 * (kCandChunk / 16)));
             cand_kernel<16><<<omv::xcd_grid(nb), 256, 0, st>>>(f, m, n_frames, th, kp_occ_init, h->d_recs, h->d_counts,

@@ -101,14 +101,16 @@ __device__ __forceinline__ int mul_u24(int a, int b) { return (int)omv_llvm_mul_
 // nothing is lost above, and its low 16 bits are zero, so the shift by 32 drops the same bits as b s >> 16.
 __device__ __forceinline__ uint32_t mulhi_u24(uint32_t a, uint32_t b) { return omv_llvm_mulhi_u24(a, b); }
 
-// Test knobs of a matcher handle (OMV_BOW_TOP, OMV_TRI_SLICES, OMV_TRI_ECAP, OMV_TRI_WALK, OMV_CAND, OMV_CAND_PW, OMV_KNN,
-// OMV_KNN_IDX_LIMIT),
+// Test knobs of a matcher handle (OMV_BOW_TOP, OMV_TRI_SLICES, OMV_TRI_ECAP, OMV_TRI_WALK, OMV_CAND, OMV_CAND_PW,
+// OMV_CAND_SPLIT, OMV_KNN, OMV_KNN_IDX_LIMIT),
 // read once by omv_matcher_create (not per call); -1 / 0: unset.  Defined in match.hip for the other matcher
 // translation units.
 struct MatcherKnobs {
     int bow_top = -1, tri_slices = -1, tri_ecap = -1, tri_walk_seq = 0;
     int cand_mode = 0;     // OMV_CAND: SearchByProjection candidates 0 by batch size, 1 "global" (no LDS staging), 2 "lds"
     int cand_pw = -1;      // OMV_CAND_PW: map points per wave of the LDS-staged candidate kernel
+    int cand_split = -1;   // OMV_CAND_SPLIT: window entries per lane above which the staged kernel splits a window over
+                           // more lanes (a huge value: one lane per window)
     int knn_mode = 0;      // OMV_KNN: knnMatch(k=2) kernel 0 by shape, 1 "mfma" (matrix cores), 2 "lanes"
     int knn_idx_limit = 1 << 16;   // OMV_KNN_IDX_LIMIT: train capacity from which the matrix-core knn is not used
 };

@@ -178,6 +178,14 @@ class ORBmatcher:
         _lib.check(self._lib.omv_matcher_grid_debug(self._h, frame, cam, _lib.ptr(cs), _lib.ptr(idx)))
         return cs, idx[:cs[-1]]
 
+    def records(self, n_frames, M):
+        """The candidate records of the last SearchByProjection(frames, mps) call: uint32 [n_frames, M, n_cams, 16]
+        (idx | dist << 16 | octave << 25 | bit 31 valid; bit 30 of word 0: more than 16 candidates).  Only slots in
+        view with a valid predicted level hold a record."""
+        out = np.zeros((n_frames, M, self._shape[1], 16), np.uint32)
+        _lib.check(self._lib.omv_matcher_records_debug(self._h, n_frames, M, _lib.ptr(out)))
+        return out
+
     def SearchByProjectionLastFrame(self, frames, last, Tcw, Tlw, cams, Trl, th, bMono=False, mb=0.0, stream=None):
         """ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono)
         (src/ORBmatcher.cc:1985-2413): the last frames' tracked points (`last`: dict of device tensors
