@@ -483,6 +483,8 @@ __global__ void __launch_bounds__(kInT) inertial_opt_kernel(InArgs A) {
     // SparseOptimizer::optimize (anything but OK ends it): OptimizationAlgorithmGaussNewton, optimize(10), in GS mode --
     // without an edge there is no vertex and it returns at once -- otherwise OptimizationAlgorithmLevenberg, optimize(200).
     // GS mode takes one more pass that only evaluates (:3920-3921, err_end).
+    // The Levenberg step control below is omv_lm.h's rules WRITTEN OUT: every form of this loop that calls the header
+    // moved the kernel's AGPR and SGPR-spill counts (profiles/lm_control_ab.log, section 2).  Keep the two in step.
     const int max_it = gsmode ? (E > 0 ? 10 : 0) : 200;
     int n_it = 0, n_trials = 0, most = 0, lm_bad = 0;
     float err0 = 0.f, err1 = 0.f;

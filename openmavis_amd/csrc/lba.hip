@@ -2,7 +2,7 @@
 // src/Optimizer.cc:3270-3321): g2o's Levenberg-Marquardt over EdgeMono / EdgeInertial / EdgeGyroRW /
 // EdgeAccRW with the landmark Schur complement, as batched gfx950 kernels on device-resident state.
 //
-// Per LM iteration (optimization_algorithm_levenberg.cpp:61-169):
+// Per LM iteration (g2o's Levenberg-Marquardt; its step control is omv_lm.h's):
 //   errors   1 thread / visual edge (+1 thread / inertial edge): residual, chi2, Huber rho; deterministic
 //            two-level chi2 reduction (computeActiveErrors + activeRobustChi2)
 //   build    1 thread / landmark (edges sorted landmark-major): EdgeMono / EdgeStereo Jacobians, the
@@ -44,6 +44,7 @@
 #include "lba_plan.h"
 #include "omv_device.h"
 #include "omv_host.h"
+#include "omv_lm.h"
 
 namespace {
 
@@ -54,13 +55,14 @@ static_assert(sizeof(Int4) == sizeof(int4) && alignof(Int4) == alignof(int4), "t
 static_assert(kPreintCov == PreView::C, "the plan reads the covariance where the kernels do");
 
 
-// Device-resident Levenberg-Marquardt control (optimization_algorithm_levenberg.cpp:61-169), for the
+// Device-resident Levenberg-Marquardt control (the rules: omv_lm.h), for the
 // single-rank path: the accept / reject decision, the lambda schedule and the iteration / stop logic run in
 // finish_trial_kernel, so one LM trial is a fixed kernel sequence (captured once as a hipGraph) whose kernels
 // read lambda and their gate from here, and the host reads the outcome back once per optimize().
 struct LmCtl {
-    double lambda, ni, currentChi, iniChi, errors_chi, err0, rho, lambda_init;
-    int it, qmax, nBad, trials, its, opt_it, max_trials;
+    omv_lm::LmState lm;
+    double errors_chi, err0, lambda_init, rho;
+    int it, trials, its, opt_it, max_trials;
     int done;                // the optimisation has ended
     int errors_of_current;   // the last computed errors belong to the current state (A)
     int need_build;          // the next step starts a new iteration (buildSystem)
@@ -84,7 +86,7 @@ __device__ __forceinline__ bool gate_open(const LmCtl *c, int g) {
     if (g == kGateBuild) return c->g_build != 0;
     return c->g_active != 0;
 }
-__device__ __forceinline__ double lm_lambda(const LmCtl *c, double lambda) { return c ? c->lambda : lambda; }
+__device__ __forceinline__ double lm_lambda(const LmCtl *c, double lambda) { return c ? c->lm.lambda : lambda; }
 
 struct ErrBufs {   // per-edge errors of one state: visual [2E], stereo row [E], chi2 [E], inertial [19 NI]
     double *err, *err3, *chi2, *err9;
@@ -321,8 +323,8 @@ __device__ __forceinline__ void set_gates(LmCtl *c) {
     c->g_errA = 0;   // the current errors stay in their buffer (double-buffered): never recomputed
 }
 
-// The LM state reset of optimize()'s start (iteration 0's lambda = lambda_init, ni = 2, nBad = 0,
-// optimization_algorithm_levenberg.cpp:103-108), without the initial chi.
+// The LM state reset of optimize()'s start: iteration 0's, for the kernels that read lambda before the first step's
+// bookkeeping; the initial chi comes with that step.
 struct LmReset {
     LmCtl *c;   // null: no reset
     int opt_it, max_trials;
@@ -333,9 +335,10 @@ __device__ __forceinline__ void ctl_reset(const LmReset &r) {
     c->errors_of_current = 1;
     c->cur = c->last = 0;
     c->need_build = 1;
-    c->it = c->qmax = c->nBad = c->trials = c->its = 0;
+    c->it = c->trials = c->its = 0;
     c->opt_it = r.opt_it, c->max_trials = r.max_trials, c->lambda_init = r.lambda_init;
-    c->lambda = r.lambda_init, c->ni = 2, c->rho = 0, c->accepted = 0, c->n_acc = 0;
+    omv_lm::lm_begin_iteration(c->lm, 0, 0.0, r.lambda_init);
+    c->rho = 0, c->accepted = 0, c->n_acc = 0;
     c->done = r.opt_it <= 0;
     set_gates(c);
 }
@@ -355,11 +358,10 @@ __global__ void __launch_bounds__(256) ctl_init_kernel(LmCtl *c, const double *m
     }
 }
 
-// One step's LM bookkeeping (optimization_algorithm_levenberg.cpp:61-169), after the trial's errors:
-//   a step that started an iteration: ++its, currentChi = iniChi = activeRobustChi2 of the current state (kept with
-//   its buffer: after a rejected trial the reference recomputes the same errors and gets the same sum), qmax = 0;
-//   the trial: rho, accept (the trial state becomes current) or reject (lambda *= ni), then the do-while /
-//   iteration / nBad stop tests in the reference's order, and the next step's gates.
+// One step's LM bookkeeping (omv_lm.h), after the trial's errors:
+//   a step that started an iteration: ++its, the iteration begins at activeRobustChi2 of the current state (kept with
+//   its buffer: after a rejected trial the reference recomputes the same errors and gets the same sum);
+//   the trial: an accepted trial's state becomes current; then what comes next, and the next step's gates.
 __device__ void finish_trial_body(double *sh, LmCtl *c, const double *mono_partial, int n_mono_blocks,
                                   const double *imu_partial, const double *scale_partial, int n_scale, const int *fail,
                                   const double *pre, const double *mono_partial0, const double *imu_partial0) {
@@ -383,48 +385,26 @@ __device__ void finish_trial_body(double *sh, LmCtl *c, const double *mono_parti
     if (initp) c->err0 = c->errors_chi = c->cur_chi = chi0, c->init_pending = 0;
     if (c->g_build) {   // iteration start: the current state's activeRobustChi2 (its errors are in buffer cur)
         ++c->its;
-        c->currentChi = c->iniChi = c->cur_chi;
-        c->qmax = 0;
+        omv_lm::lm_begin_iteration(c->lm, c->it, c->cur_chi, c->lambda_init);
     }
     const int trial_buf = c->cur ^ 1;
     c->last = trial_buf;
     const bool ok = *fail == 0;
-    double tempChi = chi;
     c->errors_chi = chi;
     c->errors_of_current = 0;   // the last computed errors belong to the trial state
-    if (!ok) tempChi = DBL_MAX;
-    double scale = ok ? ssum : 0.0;
-    scale += 1e-3;
-    const double rho = (c->currentChi - tempChi) / scale;
-    c->rho = rho;
+    const omv_lm::LmTrial tr = omv_lm::lm_trial(c->lm, chi, ok, ok ? ssum : 0.0);   // a failed solve: no step, no scale
+    c->rho = tr.rho;
     ++c->trials;
-    c->accepted = 0;
-    if (rho > 0 && isfinite(tempChi)) {
-        double alpha = 1. - pow((2 * rho - 1), 3.0);
-        alpha = fmin(alpha, 2. / 3.);
-        c->lambda *= fmax(1. / 3., alpha);
-        c->ni = 2;
-        c->currentChi = tempChi;
-        c->accepted = 1;
+    c->accepted = tr.accepted ? 1 : 0;
+    if (tr.accepted) {
         ++c->n_acc;
         c->errors_of_current = 1;
         c->cur = trial_buf, c->cur_chi = chi;   // the trial's buffers become current
-    } else {
-        c->lambda *= c->ni;
-        c->ni *= 2;
     }
-    ++c->qmax;
-    if (rho < 0 && c->qmax < c->max_trials) {
-        c->need_build = 0;   // another trial of this iteration
-    } else {
-        c->need_build = 1;
-        if (c->qmax == c->max_trials || rho == 0) {
-            c->done = 1;
-        } else {
-            if ((c->iniChi - c->currentChi) * 1e3 < c->iniChi) ++c->nBad;
-            else c->nBad = 0;
-            if (c->nBad >= 3) c->done = 1;
-        }
+    const omv_lm::LmNext next = omv_lm::lm_next(c->lm, tr.rho, c->max_trials);
+    c->need_build = next != omv_lm::kLmTrial;   // kLmTrial: another trial of this iteration
+    if (c->need_build) {
+        if (next == omv_lm::kLmStop) c->done = 1;
         if (++c->it >= c->opt_it) c->done = 1;
     }
     set_gates(c);
@@ -1901,7 +1881,7 @@ __global__ void __launch_bounds__(256) vis_diag_kernel(Rig rig, Kind<true> kd, S
         out[b] = m;
     }
 }
-// lambda = tau * max (tau = 1e-5, g2o's default), the maximum of the blocks' maxima.
+// lambda = computeLambdaInit of the maximum of the blocks' maxima.
 __global__ void __launch_bounds__(256) vis_lambda_kernel(const double *part, int n, LmCtl *c) {
     __shared__ double mx[256];
     if (!c->init_pending || c->lambda_init > 0) return;
@@ -1911,7 +1891,7 @@ __global__ void __launch_bounds__(256) vis_lambda_kernel(const double *part, int
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int q = 1; q < (int)blockDim.x; ++q) m = fmax(m, mx[q]);
-        c->lambda = c->lambda_init = 1e-5 * m;
+        c->lm.lambda = c->lambda_init = omv_lm::lm_lambda_init(c->lambda_init, m);
     }
 }
 
@@ -2514,7 +2494,7 @@ static omv_status lba_optimize_device(omv_lba *h, const omv_lba_opts *o, omv_lba
     res->err_end = (float)c.errors_chi;
     res->iterations = c.its;
     res->trials = c.trials;
-    res->lambda = c.lambda;
+    res->lambda = c.lm.lambda;
     return OMV_OK;
 }
 
@@ -2535,8 +2515,8 @@ omv_status omv_lba_optimize(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *
     res->err = (float)sc[0];
     double errors_chi = sc[0];
     bool errors_of_current = true;
-    double lambda = 0, ni = 2;
-    int nBad = 0, trials = 0, its = 0, n_acc = 0;   // n_acc: accepted updates (ImuCamPose::its, see LmCtl)
+    omv_lm::LmState lm{0.0, 2.0, 0.0, 0.0, 0, 0};
+    int trials = 0, its = 0, n_acc = 0;   // n_acc: accepted updates (ImuCamPose::its, see LmCtl)
     for (int it = 0; it < o->opt_it; ++it) {
         ++its;
         State &A = h->st[h->cur];
@@ -2547,25 +2527,18 @@ omv_status omv_lba_optimize(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *
             errors_chi = sc[0];
             errors_of_current = true;
         }
-        double currentChi = errors_chi;
-        const double iniChi = currentChi;
-        if (it == 0) {
-            lambda = o->lambda_init;
-            ni = 2;
-            nBad = 0;
-        }
-        double rho = 0;
-        int qmax = 0;
+        omv_lm::lm_begin_iteration(lm, it, errors_chi, o->lambda_init);
+        omv_lm::LmNext next;
         float ms;
         do {
             // buildSystem + the landmark Schur complement at this trial's lambda (a retry rebuilds at the same state; this
             // driver has one error buffer, which the rejected trial overwrote: the current state's errors first)
-            if (qmax > 0 && (rs = lba_errors(h, A)) != OMV_OK) return rs;
+            if (lm.qmax > 0 && (rs = lba_errors(h, A)) != OMV_OK) return rs;
             HIP_OK(hipEventRecord(h->ev[0], st));
-            if ((rs = launch_build(h, A, A, nullptr, lambda)) != OMV_OK) return rs;
+            if ((rs = launch_build(h, A, A, nullptr, lm.lambda)) != OMV_OK) return rs;
             HIP_OK(hipEventRecord(h->ev[1], st));
             HIP_OK(hipEventRecord(h->ev[2], st));
-            if ((rs = launch_assemble(h, lambda, nullptr)) != OMV_OK) return rs;
+            if ((rs = launch_assemble(h, lm.lambda, nullptr)) != OMV_OK) return rs;
             // one exchange: sum the partial reduced systems [blocks | b | Schur rhs] of the landmark shards
             if ((rs = lba_allreduce(h, h->d_S, h->plan.n_reduce)) != OMV_OK) return rs;
             HIP_OK(hipEventRecord(h->ev[3], st));
@@ -2573,7 +2546,7 @@ omv_status omv_lba_optimize(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *
             HIP_OK(hipEventRecord(h->ev[4], st));
             // the keyframe update and the landmarks' back-substitution A -> B, the trial's errors (one launch, this
             // driver's one error buffer)
-            if ((rs = launch_errors(h, A, B, nullptr, kGateAlways, 1, LmReset{}, false, h->d_x, lambda, true, n_acc)) !=
+            if ((rs = launch_errors(h, A, B, nullptr, kGateAlways, 1, LmReset{}, false, h->d_x, lm.lambda, true, n_acc)) !=
                 OMV_OK)
                 return rs;
             if ((rs = lba_read_scalars(h, 1 + h->plan.n_lgrp, sc, true)) != OMV_OK) return rs;
@@ -2589,41 +2562,26 @@ omv_status omv_lba_optimize(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *
             HIP_OK(hipEventElapsedTime(&ms, h->ev[4], h->ev[5]));
             h->stage_ms[3] += ms;
             const bool ok = fail == 0;
-            double tempChi = sc[0];
             errors_chi = sc[0];
             errors_of_current = false;   // the last computed errors belong to the trial state
-            if (!ok) tempChi = std::numeric_limits<double>::max();
-            double scale = ok ? sc[1] : 0.0;
-            scale += 1e-3;
-            rho = (currentChi - tempChi) / scale;
+            const omv_lm::LmTrial tr = omv_lm::lm_trial(lm, sc[0], ok, ok ? sc[1] : 0.0);   // a failed solve: no scale
             ++trials;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                lambda *= std::max(1. / 3., alpha);
-                ni = 2;
-                currentChi = tempChi;
+            if (tr.accepted) {
                 ++n_acc;
                 // fixed keyframes are identical in both buffers; make B the current state
                 h->cur = 1 - h->cur;
                 errors_of_current = true;
                 // the next trial rewrites every optimisable keyframe and every point of the other buffer
-            } else {
-                lambda *= ni;
-                ni *= 2;
             }
-            qmax++;
-        } while (rho < 0 && qmax < o->max_trials);
-        if (qmax == o->max_trials || rho == 0) break;
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++;
-        else nBad = 0;
-        if (nBad >= 3) break;
+            next = omv_lm::lm_next(lm, tr.rho, o->max_trials);
+        } while (next == omv_lm::kLmTrial);
+        if (next == omv_lm::kLmStop) break;
     }
     h->last_trials = trials;
     res->err_end = (float)errors_chi;
     res->iterations = its;
     res->trials = trials;
-    res->lambda = lambda;
+    res->lambda = lm.lambda;
     return lba_finish_result(h, o, p, res);
 }
 
@@ -3000,7 +2958,7 @@ omv_status omv_vba_optimize(omv_vba *hv, const omv_vba_opts *o, omv_vba_problem 
     for (double &m : h->stage_ms) m = 0;
     if ((rs = lba_optimize_device(h, &lo, &lr)) != OMV_OK) return rs;
     const LmCtl &c = *h->h_ctl;
-    r->err = c.err0, r->err_end = c.errors_chi, r->iterations = c.its, r->trials = c.trials, r->lambda = c.lambda;
+    r->err = c.err0, r->err_end = c.errors_chi, r->iterations = c.its, r->trials = c.trials, r->lambda = c.lm.lambda;
     r->lambda_init = c.lambda_init;
     // the epilogue's staging block: [state head | points | flags | chi2] in the caller's order
     const bool want_chi2 = r->mono_chi2 || r->stereo_chi2;

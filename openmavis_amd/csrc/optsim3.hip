@@ -4,7 +4,7 @@
 // The graph: one VertexSim3Expmap (g2o::Sim3 S12: quaternion, t, s; oplus = Sim3(update) * S12 with update[6] forced
 // to 0 under _fix_scale) and per accepted correspondence the pair EdgeSim3ProjectXYZ (obs1 - project1(S12 X2)) /
 // EdgeInverseSim3ProjectXYZ (obs2 - project2(S12^-1 X1)) on fixed points, Huber sqrt(th2).  Two rounds of g2o's
-// Levenberg-Marquardt as pose.hip's pose_only_kernel restates it: optimize(10); the pairs whose stale chi2 exceeds th2
+// Levenberg-Marquardt, the step control from omv_lm.h: optimize(10); the pairs whose stale chi2 exceeds th2
 // removed, the rest without robust kernel; the return before the write-back when fewer than 10 are left; optimize(10
 // or 5); a fresh computeError per kept pair.  The reference differentiates both edges numerically (linearizeOplus is
 // commented out: central differences with delta 1e-9); here the Jacobians are analytic, with Y = S12 X2,
@@ -26,6 +26,7 @@
 #include "g2o_types.h"
 #include "omv_device.h"
 #include "omv_host.h"
+#include "omv_lm.h"
 
 namespace {
 
@@ -239,8 +240,7 @@ __global__ void __launch_bounds__(64) optimize_sim3_kernel(OptSim3Args A) {
         const bool robust = round == 0;
         const int max_it = round == 0 ? 10 : (n_bad > 0 ? 10 : 5);
         int n_it = 0, n_trials = 0, most_trials = 0;
-        double lambda = 0.0, ni = 2.0;
-        int lm_bad = 0;
+        omv_lm::LmState lm{0.0, 2.0, 0.0, 0.0, 0, 0};
         // initializeOptimization finds the vertex through its edges: without one optimize() returns at once
         for (int it = 0; it < max_it && n_active > 0; ++it) {
             // computeActiveErrors + buildSystem at the current estimate
@@ -318,30 +318,25 @@ __global__ void __launch_bounds__(64) optimize_sim3_kernel(OptSim3Args A) {
                 if (lane < 7) gs[lane] = sums[28 + lane];
                 omv::wave_lds_sync();
             }
-            double cur = sums[35];
-            const double ini = cur;
-            if (it == 0) {   // computeLambdaInit: tau * max |H_jj|; _ni and _nBad reset
-                double md = 0;
+            double md = 0;   // computeLambdaInit's maximum of |H_jj|
+            if (it == 0)
                 for (int j = 0; j < 7; ++j) md = fmax(fabs(Hs[8 * j]), md);
-                lambda = 1e-5 * md, ni = 2, lm_bad = 0;
-            }
+            omv_lm::lm_begin_iteration(lm, it, sums[35], omv_lm::lm_lambda_init(0.0, md));
             if (round == 0 && it == 0) {
                 if (lane < 49) dbg->H[lane] = Hs[lane];
                 if (lane < 7) dbg->b[lane] = gs[lane];
-                if (lane == 0) dbg->chi2 = cur, dbg->lambda_init = lambda;
+                if (lane == 0) dbg->chi2 = lm.currentChi, dbg->lambda_init = lm.lambda;
             }
             ++n_it;
-            int qmax = 0;
-            double rho = 0;
-            bool again;
+            omv_lm::LmNext next;
             do {
-                if (lane < 49) Ad[lane] = Hs[lane] + ((lane % 8 == 0) ? lambda : 0.0);
+                if (lane < 49) Ad[lane] = Hs[lane] + ((lane % 8 == 0) ? lm.lambda : 0.0);
                 omv::wave_lds_sync();
                 const bool ok = ldlt_pick_solve<7>(Ad, gs, xs, pick, Lm, lane);
                 omv::wave_lds_sync();
                 double x[7];
                 for (int j = 0; j < 7; ++j) x[j] = xs[j];
-                if (round == 0 && it == 0 && qmax == 0 && lane < 7) dbg->x[lane] = xs[lane];
+                if (round == 0 && it == 0 && lm.qmax == 0 && lane < 7) dbg->x[lane] = xs[lane];
                 if (fix_scale) x[6] = 0;   // oplusImpl
                 const Sim3d St = sim3_mul(sim3_exp(x), S);
                 const Sim3d Sti = sim3_inverse(St);
@@ -368,30 +363,15 @@ __global__ void __launch_bounds__(64) optimize_sim3_kernel(OptSim3Args A) {
                     }
                 }
                 for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-                const double temp = ok ? c : DBL_MAX;
-                double sc = 0;
-                for (int j = 0; j < 7; ++j) sc += x[j] * (lambda * x[j] + gs[j]);
-                sc += 1e-3;
-                rho = (cur - temp) / sc;
-                if (rho > 0 && isfinite(temp)) {
-                    const double a3 = 2 * rho - 1;
-                    double alpha = 1. - a3 * a3 * a3;   // pow(2 rho - 1, 3)
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2;
-                    cur = temp;
-                    S = St;
-                } else {   // pop(): the estimate restored, the edges keep the rejected trial's errors
-                    lambda *= ni;
-                    ni *= 2;
-                }
-                ++qmax, ++n_trials;
-                again = rho < 0 && qmax < 10;
-            } while (again);
-            most_trials = max(most_trials, qmax);
-            if (qmax == 10 || rho == 0) break;
-            lm_bad = (ini - cur) * 1e3 < ini ? lm_bad + 1 : 0;
-            if (lm_bad >= 3) break;
+                double sc = 0;   // computeScale
+                for (int j = 0; j < 7; ++j) sc += x[j] * (lm.lambda * x[j] + gs[j]);
+                const omv_lm::LmTrial tr = omv_lm::lm_trial(lm, c, ok, sc);
+                if (tr.accepted) S = St;   // else pop(): the estimate restored, the edges keep the rejected trial's errors
+                ++n_trials;
+                next = omv_lm::lm_next(lm, tr.rho, 10);
+            } while (next == omv_lm::kLmTrial);
+            most_trials = max(most_trials, lm.qmax);
+            if (next == omv_lm::kLmStop) break;
         }
         if (lane == 0) dbg->iterations[round] = n_it, dbg->trials[round] = n_trials, dbg->max_trials[round] = most_trials;
         if (round == 0) {   // :2660-2696: the stale chi2 of the last computeActiveErrors decides

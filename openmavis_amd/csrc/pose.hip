@@ -2124,7 +2124,8 @@ __global__ void __launch_bounds__(kPoThreads) pose_only_kernel(PoseOnlyRig Parg,
 #ifdef OMV_PO_PROFILE
                     ++n_trials;
 #endif
-                    if (tid == 0) {
+                    if (tid == 0) {   // omv_lm.h's rules WRITTEN OUT: with the header the batch of 256 frames ran 0.6 to
+                                      // 1.7 % slower in every form tried (profiles/lm_control_ab.log, section 4)
                         double tempChi = ok_s ? sums[0] : DBL_MAX;
                         double sc = 0;
                         for (int j = 0; j < 6; ++j) sc += xs[j] * (lambda_s * xs[j] + gs[j]);

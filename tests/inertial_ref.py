@@ -18,11 +18,11 @@ Switches:  deltas = "literal" | "smooth"   (smooth: float64 bias corrections wit
 Column order of an edge's Jacobian J [9][15]: V1 (3) V2 (3) bg (3) ba (3) gdir (2) scale (1)."""
 import numpy as np
 
+import lm_ref
 import oracle   # oracle/oracle.py: the product's float layer on the host (math_map)
 
 FULL, BIAS, GS = 0, 1, 2
 G = float(np.float32(9.81))
-DBL_MAX = np.finfo(np.float64).max
 f32 = np.float32
 
 # offsets inside one preintegration record (csrc/g2o_types.h PreView)
@@ -410,48 +410,34 @@ def optimize(job, deltas="literal", solve="dense"):
                 out["exit"] = "fail"
                 break
     else:
-        lam, ni, n_bad = 0.0, 2.0, 0
+        lm = lm_ref.LmState()   # the step control: lm_ref
         for it in range(200):
             H, b, cur, e = P.build(st)
-            ini = cur
-            if it == 0:
-                user = P.mode == BIAS or P.priorG != 0.0
-                lam = 1e3 if user else 1e-5 * float(np.max(np.abs(np.diag(H)[P.free]))) if P.free.any() else 0.0
-                ni, n_bad = 2.0, 0
+            user, md = 0.0, 0.0
+            if it == 0:   # setUserLambdaInit(1e3) in BIAS mode or with a gravity prior
+                user = 1e3 if P.mode == BIAS or P.priorG != 0.0 else 0.0
+                md = float(np.max(np.abs(np.diag(H)[P.free]))) if P.free.any() else 0.0
+            lm_ref.begin_iteration(lm, it, cur, lm_ref.lambda_init(user, md))
             out["iterations"] += 1
-            qmax, rho = 0, 0.0
-            entry_lam = lam
+            entry_lam = lm.lam
             while True:
-                ok, x = P.solve(H, b, lam, solve)
-                if it == 0 and qmax == 0:
-                    out["first"] = dict(H=H, b=b, chi2=cur, lambda_init=lam, x=x.copy(), e0=e)
+                ok, x = P.solve(H, b, lm.lam, solve)
+                if it == 0 and lm.qmax == 0:
+                    out["first"] = dict(H=H, b=b, chi2=cur, lambda_init=lm.lam, x=x.copy(), e0=e)
                 trial = P.oplus(st, x)
                 with np.errstate(all="ignore"):
-                    temp = P.chi2(trial)[0] if ok else DBL_MAX
-                    if not ok:
-                        temp = DBL_MAX
-                    scale = float(np.sum(x * (lam * x + b))) + 1e-3
-                    rho = (cur - temp) / scale
-                if rho > 0 and np.isfinite(temp):
-                    alpha = min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0)
-                    lam *= max(1.0 / 3.0, alpha)
-                    ni = 2.0
-                    cur = temp
+                    temp = P.chi2(trial)[0] if ok else 0.0   # a failed solve: lm_ref puts DBL_MAX in its place
+                    scale = float(np.sum(x * (lm.lam * x + b)))
+                rho, accepted = lm_ref.trial(lm, temp, ok, scale)
+                if accepted:
                     st = trial
-                else:
-                    lam *= ni
-                    ni *= 2
-                qmax += 1
                 out["trials"] += 1
-                if not (rho < 0 and qmax < 10):
+                nxt = lm_ref.next_step(lm, rho, 10)
+                if nxt != lm_ref.TRIAL:
                     break
-            out["log"].append(dict(chi2=cur, lam=entry_lam, trials=qmax))
-            if qmax == 10 or rho == 0:
-                out["exit"] = "terminate"
-                break
-            n_bad = n_bad + 1 if (ini - cur) * 1e3 < ini else 0
-            if n_bad >= 3:
-                out["exit"] = "n_bad"
+            out["log"].append(dict(chi2=lm.current_chi, lam=entry_lam, trials=lm.qmax))
+            if nxt == lm_ref.STOP:   # _nBad reaches 3 only in the stop that it causes
+                out["exit"] = "n_bad" if lm.n_bad >= 3 else "terminate"
                 break
     if out["first"] is None:
         N = 3 * P.K + 9

@@ -26,9 +26,9 @@ final test), 1 inlier, 2 removed after round one, 3 removed at the end: n_in is 
 import numpy as np
 
 import linalg_ref
+import lm_ref
 import sim3_ref
 
-DBL_MAX = np.finfo(np.float64).max
 NOT_EDGE, INLIER, REMOVED_1, REMOVED_2 = 0, 1, 2, 3
 
 
@@ -339,11 +339,11 @@ def build_system(job, pre, S, active, robust, fix_scale, jac="analytic", proj="l
 
 
 def _lm(job, pre, S, x, active, robust, n_it, fix_scale, jac, proj, c12, c21, dbg):
-    """optimize(n_it) of OptimizationAlgorithmLevenberg on the active pairs.  c12 / c21: the edges' _error-derived chi2,
-    updated in place by every computeActiveErrors (a rejected trial's included).  Returns (S, x)."""
+    """optimize(n_it) of OptimizationAlgorithmLevenberg (its step control: lm_ref) on the active pairs.  c12 / c21: the
+    edges' _error-derived chi2, updated in place by every computeActiveErrors (a rejected trial's included).  Returns
+    (S, x)."""
     its = trials = 0
-    lam = ni = 0.0
-    n_bad = 0
+    lm = lm_ref.LmState()
     if not active.any():   # initializeOptimization finds no vertex: optimize() returns -1
         dbg["iterations"].append(0), dbg["trials"].append(0), dbg["max_trials"].append(0)
         return S, x
@@ -351,19 +351,17 @@ def _lm(job, pre, S, x, active, robust, n_it, fix_scale, jac, proj, c12, c21, db
     for it in range(n_it):
         H, b, chi, a12, a21, e12, e21 = build_system(job, pre, S, active, robust, fix_scale, jac, proj)
         c12[active], c21[active] = a12[active], a21[active]
-        cur = ini = chi
         its += 1
         with np.errstate(all="ignore"):
+            md = 0.0
             if it == 0:
-                md = 0.0
                 for j in range(7):
                     md = np.fmax(abs(H[j, j]), md)
-                lam, ni, n_bad = 1e-5 * md, 2.0, 0
+            lm_ref.begin_iteration(lm, it, chi, lm_ref.lambda_init(0.0, md))
             if "H" not in dbg:
-                dbg.update(H=H.copy(), b=b.copy(), chi2=chi, lambda_init=lam, e12=e12.copy(), e21=e21.copy())
-            qmax, rho = 0, 0.0
+                dbg.update(H=H.copy(), b=b.copy(), chi2=chi, lambda_init=lm.lam, e12=e12.copy(), e21=e21.copy())
             while True:
-                r = linalg_ref.ldlt_replay((H + lam * np.eye(7)).tolist(), b.tolist(), num=float, looking="left")
+                r = linalg_ref.ldlt_replay((H + lm.lam * np.eye(7)).tolist(), b.tolist(), num=float, looking="left")
                 if r["ok"]:
                     x = np.array(r["x"], np.float64)
                 if "x" not in dbg:
@@ -374,29 +372,15 @@ def _lm(job, pre, S, x, active, robust, n_it, fix_scale, jac, proj, c12, c21, db
                 temp = 0.0
                 for c in (t12, t21):
                     temp += (_huber(c, pre["delta"])[0] if robust else c)[active].sum()
-                if not r["ok"]:
-                    temp = DBL_MAX
-                scale = float((x * (lam * x + b)).sum()) + 1e-3
-                rho = (cur - temp) / scale
+                rho, accepted = lm_ref.trial(lm, temp, r["ok"], float((x * (lm.lam * x + b)).sum()))
                 trials += 1
-                if rho > 0 and np.isfinite(temp):
-                    a3 = 2 * rho - 1
-                    alpha = min(1. - a3 * a3 * a3, 2. / 3.)
-                    lam *= max(1. / 3., alpha)
-                    ni = 2.0
-                    cur = temp
+                if accepted:
                     S = St
-                else:
-                    lam *= ni
-                    ni *= 2
-                qmax += 1
-                if not (rho < 0 and qmax < 10):
+                nxt = lm_ref.next_step(lm, rho, 10)
+                if nxt != lm_ref.TRIAL:
                     break
-            max_trials = max(max_trials, qmax)
-            if qmax == 10 or rho == 0:
-                break
-            n_bad = n_bad + 1 if (ini - cur) * 1e3 < ini else 0
-            if n_bad >= 3:
+            max_trials = max(max_trials, lm.qmax)
+            if nxt == lm_ref.STOP:
                 break
     dbg["iterations"].append(its), dbg["trials"].append(trials), dbg["max_trials"].append(max_trials)
     return S, x

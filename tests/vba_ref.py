@@ -18,10 +18,10 @@ edge array e of the functions below lists the 2-row edges first, then the stereo
 """
 import numpy as np
 
+import lm_ref
 import optsim3_ref
 from optsim3_ref import q_from_mat, q_mul, q_rot, q_to_mat, skew
 
-DBL_MAX = np.finfo(np.float64).max
 CHI2_MONO, CHI2_STEREO = 5.991, 7.815
 HUBER_MONO, HUBER_STEREO = float(np.float32(np.sqrt(5.991))), float(np.float32(np.sqrt(7.815)))
 
@@ -262,11 +262,16 @@ def build_system(G, st, e, chi2, hub, jac="analytic", proj="literal"):
     return dict(Hpp=Hpp, Hll=Hll, Hpl=Hpl, bp=bp, bl=bl, active_pt=np.bincount(G.pt[act], minlength=G.P) > 0)
 
 
-def lambda_init(sys_):
-    """computeLambdaInit: 1e-5 * max |H(j,j)| over the active vertices (poses and landmarks)."""
+def max_diagonal(sys_):
+    """max |H(j,j)| over the active vertices (poses and landmarks)."""
     dp = np.abs(np.einsum("kii->ki", sys_["Hpp"]))
     dl = np.abs(np.einsum("pii->pi", sys_["Hll"]))[sys_["active_pt"]]
-    return 1e-5 * max(dp.max(initial=0.0), dl.max(initial=0.0))
+    return max(dp.max(initial=0.0), dl.max(initial=0.0))
+
+
+def lambda_init(sys_):
+    """computeLambdaInit without a user value."""
+    return lm_ref.lambda_init(0.0, max_diagonal(sys_))
 
 
 def reduce_system(sys_, lam):
@@ -315,53 +320,40 @@ def optimize(G, st, iterations=10, lambda_init_user=0.0, max_trials=10, hub=(HUB
     e, chi2, _ = errors(G, st, proj)
     chi, _ = robust_chi2(G, chi2, hub)
     res = dict(err=chi, iterations=0, trials=0, rhos=[], stops=[], lambda_init=lambda_init_user)
-    lam, ni, n_bad = lambda_init_user, 2.0, 0
+    lm = lm_ref.LmState()   # the step control: lm_ref
     cur_e, cur_chi2, cur_chi = e, chi2, chi
     last_chi2, last_chi = chi2, chi
     for it in range(iterations):
         res["iterations"] += 1
-        current_chi = ini_chi = cur_chi
         sys_ = build_system(G, st, cur_e, cur_chi2, hub, jac, proj)
+        md = max_diagonal(sys_) if it == 0 else 0.0
+        lm_ref.begin_iteration(lm, it, cur_chi, lm_ref.lambda_init(lambda_init_user, md))
         if it == 0:
-            if not lambda_init_user > 0:
-                lam = lambda_init(sys_)
-            res["lambda_init"] = lam
-            ni, n_bad = 2.0, 0
-        rho, qmax = 0.0, 0
+            res["lambda_init"] = lm.lam
         while True:
-            ok, xp, xl = solve(sys_, lam)
-            scale = 0.0
+            ok, xp, xl = solve(sys_, lm.lam)
+            scale, temp_chi = 0.0, 0.0   # a failed solve: lm_ref puts DBL_MAX in the chi2's place
             if ok:
                 trial = update(G, st, xp, xl)
                 te, tchi2, _ = errors(G, trial, proj)
                 temp_chi, _ = robust_chi2(G, tchi2, hub)
                 last_chi2, last_chi = tchi2, temp_chi
-                scale = float((xp * (lam * xp + sys_["bp"])).sum() + (xl * (lam * xl + sys_["bl"])).sum())
-            else:
-                temp_chi = DBL_MAX
-            rho = (current_chi - temp_chi) / (scale + 1e-3)
+                scale = float((xp * (lm.lam * xp + sys_["bp"])).sum() + (xl * (lm.lam * xl + sys_["bl"])).sum())
+            rho, accepted = lm_ref.trial(lm, temp_chi, ok, scale)
             res["trials"] += 1
             res["rhos"].append(rho)
-            if rho > 0 and np.isfinite(temp_chi):
-                alpha = min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0)
-                lam *= max(1.0 / 3.0, alpha)
-                ni = 2.0
-                current_chi = temp_chi
+            if accepted:
                 st, cur_e, cur_chi2, cur_chi = trial, te, tchi2, temp_chi
-            else:
-                lam *= ni
-                ni *= 2
-            qmax += 1
-            if not (rho < 0 and qmax < max_trials):
+            stop_sides = lm_ref.gain_sides(lm)
+            nxt = lm_ref.next_step(lm, rho, max_trials)
+            if nxt != lm_ref.TRIAL:
                 break
-        if qmax == max_trials or rho == 0:
-            break
-        res["stops"].append(((ini_chi - current_chi) * 1e3, ini_chi))
-        n_bad = n_bad + 1 if (ini_chi - current_chi) * 1e3 < ini_chi else 0
-        if n_bad >= 3:
+        if nxt == lm_ref.ITERATION or lm.n_bad >= 3:   # the stop rule was reached (no Terminate from the trials)
+            res["stops"].append(stop_sides)
+        if nxt == lm_ref.STOP:
             break
     _, _, depth = errors(G, st, proj)
     thr = np.where(G.stereo, CHI2_STEREO, CHI2_MONO)
-    res.update(err_end=last_chi, lambda_=lam, chi2=last_chi2, depth=depth,
+    res.update(err_end=last_chi, lambda_=lm.lam, chi2=last_chi2, depth=depth,
                outlier=((last_chi2 > thr) | ~(depth > 0.0)).astype(np.uint8))
     return res, st
