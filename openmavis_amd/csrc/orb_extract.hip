@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/omv.h"
+#include "fast_plan.h"
 #include "omv_device.h"
 #include "omv_host.h"
 #include "omv_introsort.h"
@@ -39,8 +40,8 @@ namespace {
 
 constexpr int kMaxLevels = 16;
 constexpr int kOrbStages = 4;   // pyramid, FAST cells, octree, describe (omv_orb_stage_ms)
-constexpr int kEdge = 19;     // EDGE_THRESHOLD
-constexpr int kMinB = kEdge - 3;
+using omv_fast_plan::kEdge;   // EDGE_THRESHOLD
+using omv_fast_plan::kMinB;
 #define OMV_PATTERN_TABLE_BEGIN
 #define OMV_PATTERN_TABLE_END
 constexpr int kPattern[256 * 4] = {
@@ -81,21 +82,9 @@ struct LevelGeom {
     uint32_t m_quads, m_groups, m_w;
 };
 
-struct Cell {
-    int level, y0, y1, x0, x1;   // region rows [y0,y1), cols [x0,x1) in level coordinates
-    // What K2 derives from the rectangle alone, host-computed (fast_cell_constants) and read with the rectangle by
-    // one scalar load; every wave of every image recomputed them, three integer divisions included.  The dword path's
-    // values hold for a dword-aligned level base and pitch, where the region's misalignment is o = x0 & 3 (the
-    // kernel tests the alignment at run time; its byte path has o = 0 and uses ndet and mdw only).
-    int o, nd, rpi;              // dwords of a staged row (x1 - x0 + o + 3) >> 2, rows per 64-lane band 64 / nd
-    uint32_t mnd;                // lane / nd = lane * mnd >> 16 (lane < 64)
-    int ndet;                    // detection window pixels (x1 - x0 - 6) * (y1 - y0 - 6), 0 when empty
-    uint32_t mdw;                // i / dw = i * mdw >> 20
-    int jq0, npr, np;            // first LDS dword of the window, dword pairs per row, pairs of the window
-    uint32_t mp;                 // t / npr = t * mp >> 20
-    int nband;                   // whole bands of rpi rows in the region: (y1 - y0) / rpi
-};
-static_assert(sizeof(Cell) == 64, "Cell: one 64-byte scalar load");
+// A FAST cell and the constants K2 reads instead of deriving, and a slot of its prefilter: fast_plan.h (host-only)
+using omv_fast_plan::Cell;
+using omv_fast_plan::FastSlot;
 
 struct Geom {
     int nlevels;
@@ -526,10 +515,10 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int v) {
 __device__ unsigned long long g_fast_stats[8];
 #endif
 template <int RS>   // LDS row stride in bytes (0: per cell, rounded up to 4)
-__global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cells, const uint8_t *images,
-                                                        size_t img_stride, size_t pitch0, const uint8_t *pyr,
-                                                        int *cell_cnt, uint32_t *cell_kp, int rmax, int smax,
-                                                        int n_blocks) {
+__global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cells, const FastSlot *slots,
+                                                        const uint8_t *images, size_t img_stride, size_t pitch0,
+                                                        const uint8_t *pyr, int *cell_cnt, uint32_t *cell_kp, int rmax,
+                                                        int smax, int n_blocks) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int blk = omv::xcd_block(n_blocks);
     if (blk < 0) return;
@@ -537,6 +526,7 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
     const int ci = blk - img * g.n_cells;
     const Cell c = cells[ci];
     const int lane = threadIdx.x;
+    const FastSlot sl0 = slots[c.slot_off + lane];   // the prefilter's first round (in bounds for every cell)
     const int rw = c.x1 - c.x0, rh = c.y1 - c.y0;
     int sp;
     const uint8_t *src = level_base(g, images, img_stride, pitch0, pyr, img, c.level, &sp);
@@ -598,12 +588,9 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
             // neighbours as whole dwords (up / down rows; left / right as byte windows of the adjacent dwords, one
             // v_perm each), the tests on packed int16 pairs.  The adjacent-pair test (a0&a4)|(a4&a8)|(a8&a12)|(a12&a0) is (a0|a8)&(a4|a12).  Survivors go to the
             // list by a DPP wave scan of the per-lane counts, each lane then writing its set bits.
-            const uint32_t *w32 = reinterpret_cast<const uint32_t *>(smem);
-            // window dwords jq0 = (o + 3) >> 2 .. (o + rw - 4) >> 2 of a row, in pairs
-            const int jq0 = c.jq0, rsw = rs >> 2;
-            const int npr = c.npr;   // dword pairs per row
-            const int np = c.np;
-            const uint32_t mp = c.mp;   // tp / npr, exact while tp * npr < 2^20
+            // window dwords (o + 3) >> 2 .. (o + rw - 4) >> 2 of a row, in pairs
+            const int rsw = rs >> 2;
+            const int np = c.np;   // slots: the window's dword pairs
             const pk16 T0{(short)t, (short)t};
             // bytes s, s+1 (lo) / s+2, s+3 (hi) of the 8-byte {a:b} as a packed int16 pair
             auto lo = [](uint32_t a, uint32_t b, uint32_t s) {
@@ -622,40 +609,56 @@ __global__ void __launch_bounds__(64) fast_cells_kernel(Geom g, const Cell *cell
                 const pk16 lo = __builtin_elementwise_max(__builtin_elementwise_min(n0, n8), __builtin_elementwise_min(n4, n12));
                 return (sg(vp - hi) | sg(lo - vm)) & 0x80008000u;
             };
+            // the 8 pixels of the dword pair whose upper compass neighbour (row r - 3, so that every offset is >= 0)
+            // is at LDS byte `up`: bit k = column q0 + k passes
+            auto compass = [&](uint32_t up) {
+                const uint32_t *wu = reinterpret_cast<const uint32_t *>(smem + up);
+                const uint32_t U0 = wu[0], U1 = wu[1];
+                const uint32_t Wm = wu[3 * rsw - 1], C0 = wu[3 * rsw], C1 = wu[3 * rsw + 1], Wp = wu[3 * rsw + 2];
+                const uint32_t D0 = wu[6 * rsw], D1 = wu[6 * rsw + 1];
+                // left neighbours: {C:prev} from byte 1; right: {next:C} from byte 3
+                const uint32_t p0 = test(lo(C0, C0, 0), lo(D0, D0, 0), lo(C1, C0, 3), lo(U0, U0, 0), lo(C0, Wm, 1));
+                const uint32_t p1 = test(hi(C0, C0, 0), hi(D0, D0, 0), hi(C1, C0, 3), hi(U0, U0, 0), hi(C0, Wm, 1));
+                const uint32_t p2 = test(lo(C1, C1, 0), lo(D1, D1, 0), lo(Wp, C1, 3), lo(U1, U1, 0), lo(C1, C0, 1));
+                const uint32_t p3 = test(hi(C1, C1, 0), hi(D1, D1, 0), hi(Wp, C1, 3), hi(U1, U1, 0), hi(C1, C0, 1));
+                // bit 2k = p_k bit 15, bit 2k + 1 = p_k bit 31: the shifts land the bit-15s on 0, 2, 4, 6 and the
+                // bit-31s on 16, 18, 20, 22
+                const uint32_t xb = (p0 >> 15) | (p1 >> 13) | (p2 >> 11) | (p3 >> 9);
+                return (xb & 0x55u) | ((xb >> 15) & 0xaau);
+            };
+            // the list position as the LDS byte offset of cand[ncand]
+            const uint32_t lpos0 = (uint32_t)(rmax + smax);
+            uint32_t lpos = lpos0;
+            // A round's slot (fast_plan.h) is loaded, not derived: the LDS address of the pair, its entry base and the
+            // mask of its window columns; round n + 1's load is issued before round n's tests.  The table pads a cell's
+            // last round with slots that keep no column, so every lane tests, and adds one round for the last load.
+            const uint8_t *sl = reinterpret_cast<const uint8_t *>(slots + c.slot_off);
+            const uint32_t sl_lane = (uint32_t)lane * (uint32_t)sizeof(FastSlot);
+            FastSlot nx = sl0;
             for (int t0 = 0; t0 < np; t0 += 64) {
-                const int tp = t0 + lane;
-                uint32_t bits = 0;
-                int r = 3, jq = jq0;
-                if (tp < np) {
-                    const int rr = omv::mul_u24(tp, (int)mp) >> 20;   // tp < 2^13, mp <= 2^20 + 1
-                    r = 3 + rr, jq = jq0 + 2 * (tp - omv::mul_u24(rr, npr));
-                    const int j = omv::mul_u24(r, rsw) + jq;
-                    const uint32_t Wm = w32[j - 1], C0 = w32[j], C1 = w32[j + 1], Wp = w32[j + 2];
-                    const uint32_t D0 = w32[j + 3 * rsw], D1 = w32[j + 3 * rsw + 1];
-                    const uint32_t U0 = w32[j - 3 * rsw], U1 = w32[j - 3 * rsw + 1];
-                    // left neighbours: {C:prev} from byte 1; right: {next:C} from byte 3
-                    const uint32_t p0 = test(lo(C0, C0, 0), lo(D0, D0, 0), lo(C1, C0, 3), lo(U0, U0, 0), lo(C0, Wm, 1));
-                    const uint32_t p1 = test(hi(C0, C0, 0), hi(D0, D0, 0), hi(C1, C0, 3), hi(U0, U0, 0), hi(C0, Wm, 1));
-                    const uint32_t p2 = test(lo(C1, C1, 0), lo(D1, D1, 0), lo(Wp, C1, 3), lo(U1, U1, 0), lo(C1, C0, 1));
-                    const uint32_t p3 = test(hi(C1, C1, 0), hi(D1, D1, 0), hi(Wp, C1, 3), hi(U1, U1, 0), hi(C1, C0, 1));
-                    // bit 2k = p_k bit 15, bit 2k + 1 = p_k bit 31: the shifts land the bit-15s on 0, 2, 4, 6 and the
-                    // bit-31s on 16, 18, 20, 22
-                    const uint32_t xb = (p0 >> 15) | (p1 >> 13) | (p2 >> 11) | (p3 >> 9);
-                    bits = (xb & 0x55u) | ((xb >> 15) & 0xaau);
-                    // columns q0 + k of the pair outside [3, rw - 4] (the second dword of a row's last pair
-                    // may lie wholly past it)
-                    const int q0 = 4 * jq - o;
-                    const int klo = min(max(3 - q0, 0), 8), khi = min(max(rw - 3 - q0, 0), 8);
-                    bits &= ((1u << khi) - 1u) & ~((1u << klo) - 1u);
-                }
+                const FastSlot cur = nx;
+                nx = *reinterpret_cast<const FastSlot *>(sl + (size_t)(t0 + 64) * sizeof(FastSlot) + sl_lane);
+                // the slot's mask drops the columns of the pair outside [3, rw - 4] (the second dword of a row's
+                // last pair may lie wholly past it)
+                uint32_t bits = compass(cur.hi) & (cur.lo >> 16);
                 const int cnt = __popc(bits);
                 const int incl = wave_incl_scan_dpp(cnt);
-                int pos = ncand + incl - cnt;
-                const int ebase = (r << 7) + (4 * jq - o);   // entry of column q0
                 // row-major: lanes hold consecutive pairs, bit k = column q0 + k (a few set bits per lane)
-                for (uint32_t b = bits; b; b &= b - 1u) cand[pos++] = (uint16_t)(ebase + __builtin_ctz(b));
-                ncand += __builtin_amdgcn_readlane(incl, 63);
+                if (bits) {
+                    // a trip is five vector instructions: the position advances as the LDS address, and the borrow
+                    // of bits - 1 (the next trip's mask of the lowest set bit) is the loop's test
+                    uint16_t *cp = reinterpret_cast<uint16_t *>(smem + lpos + 2u * (uint32_t)(incl - cnt)) - 1;
+                    const uint32_t ebase = cur.lo & 0xffffu;   // entry of column q0
+                    uint32_t below = bits - 1u;
+                    for (;;) {
+                        *++cp = (uint16_t)(ebase + __builtin_ctz(bits));
+                        bits &= below;
+                        if (__builtin_usub_overflow(bits, 1u, &below)) break;
+                    }
+                }
+                lpos += 2u * (uint32_t)__builtin_amdgcn_readlane(incl, 63);
             }
+            ncand = (int)((lpos - lpos0) >> 1);
         } else {
             for (int i0 = 0; i0 < ndet; i0 += 64) {
                 const int i = i0 + lane;
@@ -1305,6 +1308,7 @@ struct DescArgs {
     int n_images;
     const uint32_t *disc;    // [64][8] per lane: (row-sum mask, weight mask) of its four centroid dot4 items
     float *harris;           // optional [n_images][n_max]: OpenCV ORB's Harris response per output row
+    const uint64_t *bop;     // [4][64] per (po, lane): the Toeplitz operand of the horizontal sums (describe_bop_table)
 };
 
 constexpr int kRawRows = 43, kRawDw = 12;   // raw patch: rows cy-21 .. cy+21, 48 bytes each (43 used + alignment)
@@ -1379,8 +1383,12 @@ __global__ void __launch_bounds__(256, 2) describe_kernel(Geom g, DescArgs a, in
     // stay inside [0, w): three 16-byte loads per lane; raw byte po + c is column cx - 21 + c.
     const int x0 = cx - 21;
     const bool dw_rows = ((((uintptr_t)src) | (uintptr_t)sp) & 3) == 0;
-    int po = dw_rows ? (x0 & 3) : 0;
-    if (dw_rows && x0 - po >= 0 && x0 - po + 4 * kRawDw <= L.w) {
+    // (the whole choice is wave-uniform: the keypoint is the wave's)
+    const bool dw_patch = dw_rows && x0 - (x0 & 3) >= 0 && x0 - (x0 & 3) + 4 * kRawDw <= L.w;
+    const int po = dw_patch ? (x0 & 3) : 0;   // raw byte of the patch's column 0
+    // the lane's Toeplitz operand of the horizontal sums for this po, in flight with the patch
+    const long Bop = (long)a.bop[po * 64 + lane];
+    if (dw_patch) {
         const uint8_t *base = src + (x0 - po);
         u32x4a pv[3];
 #pragma unroll
@@ -1394,7 +1402,7 @@ __global__ void __launch_bounds__(256, 2) describe_kernel(Geom g, DescArgs a, in
         for (int t = 0; t < 3; ++t)
             if (lane + 64 * t < kRawRows * 3) reinterpret_cast<u32x4a *>(raw)[lane + 64 * t] = pv[t];
     } else {
-        po = 0;   // byte loads, columns reflected (near the level's left / right edge, or rows not dword aligned)
+        // byte loads, columns reflected (near the level's left / right edge, or rows not dword aligned)
         for (int i = lane; i < kRawRows * kRawDw; i += 64) {
             const int r = i / kRawDw, d = i - kRawDw * r;
             const uint8_t *row = src + (size_t)omv::reflect101(cy - 21 + r, L.h) * sp;
@@ -1455,15 +1463,13 @@ __global__ void __launch_bounds__(256, 2) describe_kernel(Geom g, DescArgs a, in
     // horizontal 7-tap sums H(r, c) = sum_j g[j] raw[r][po + c + j] (column c = level column cx - 18 + c) on the
     // matrix cores: per (row tile rt, column tile t) of 16 x 16 sums, the product of 16 raw rows' bytes 16t .. 16t + 31
     // (A, as i8: x - 128) and the banded Toeplitz B[k][c'] = g[k - c' - po] (zero outside the 7 taps; the same for
-    // every tile, k <= 15 + 3 + 6 < 32), with the accumulator started at 128 * sum(g) = 128 * 256: integer, exact.
+    // every tile, k <= 15 + 3 + 6 < 32; a host table per (po, lane): describe_bop_table), with the accumulator started
+    // at 128 * sum(g) = 128 * 256: integer, exact.
     // v_mfma_i32_16x16x32_i8: lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15]
     // (byte j of a 64-bit operand); D[i] = sum at (row 4 (l >> 4) + i, col l & 15).  Rows 43 .. 47 and columns 40 .. 47
     // of the last tiles read bytes past the patch / multiply zeros and are not stored.  Every operand is read before
     // the first sum is stored: the sums take the patch's place.
     {
-        const int sB = 8 * (lane >> 4) - (lane & 15) - po;   // B byte j = g[j + sB]
-        constexpr uint64_t kG7 = 0x0012223038302212ull;     // g[0..6] = 18, 34, 48, 56, 48, 34, 18 (byte i = g[i])
-        const long Bop = (long)(sB >= 8 || sB <= -8 ? 0ull : sB >= 0 ? kG7 >> (8 * sB) : kG7 << (-8 * sB));
         const uint8_t *rawb = reinterpret_cast<const uint8_t *>(raw);
         const int m0 = 2 * (lane >> 4);   // this lane's first row pair inside a row tile
         uint64_t av[3][3];
@@ -1474,17 +1480,22 @@ __global__ void __launch_bounds__(256, 2) describe_kernel(Geom g, DescArgs a, in
                 av[rt][t] = *reinterpret_cast<const uint64_t *>(rawb + (16 * rt + (lane & 15)) * (4 * kRawDw) + 16 * t +
                                                                 8 * (lane >> 4));
         omv::wave_lds_sync();   // every lane's patch reads before any sum overwrites the patch
+        // column c = 16 t + (lane & 15), row pair m = 8 rt + m0: one base address, the tile as a constant offset
+        uint32_t *hb = H + (lane & 15) * kHStride + m0;
+        const bool okc = (lane & 15) < kHCols - 32, okm = m0 < 22 - 16;
 #pragma unroll
         for (int rt = 0; rt < 3; ++rt) {
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
                 const i32x4 d = __builtin_amdgcn_mfma_i32_16x16x32_i8((long)(av[rt][t] ^ 0x8080808080808080ull), Bop,
                                                                       i32x4{32768, 32768, 32768, 32768}, 0, 0, 0);
-                const int c = 16 * t + (lane & 15), m = 8 * rt + m0;
-                if (c < kHCols && m < 22) {   // rows <= 43 (pair 21), columns < 40
-                    uint32_t *hp = H + c * kHStride + m;
-                    hp[0] = (uint32_t)d[0] | ((uint32_t)d[1] << 16);
-                    hp[1] = (uint32_t)d[2] | ((uint32_t)d[3] << 16);
+                // rows <= 43 (pair 21), columns < 40: only the last row tile and the last column tile hold
+                // sums that are not stored (the compile-time part of the test is true for the other four tiles)
+                if ((t < 2 || okc) && (rt < 2 || okm)) {
+                    // d < 2^16: the low halves of a pair of sums as one dword (one v_perm)
+                    uint32_t *hp = hb + (16 * t * kHStride + 8 * rt);
+                    hp[0] = __builtin_amdgcn_perm((uint32_t)d[1], (uint32_t)d[0], 0x05040100u);
+                    hp[1] = __builtin_amdgcn_perm((uint32_t)d[3], (uint32_t)d[2], 0x05040100u);
                 }
             }
         }
@@ -1559,9 +1570,11 @@ struct omv_orb {
     Geom g;
     // device
     Cell *d_cells = nullptr;
+    FastSlot *d_slots = nullptr;   // K2's prefilter slots (fast_plan.h), inside d_cells' buffer
     XTab *d_xt = nullptr, *d_yt = nullptr;
     XQuad *d_xq = nullptr;
     uint32_t *d_disc = nullptr;   // K4's per-lane centroid masks
+    uint64_t *d_bop = nullptr;    // K4's Toeplitz operands [po][lane], inside d_disc's buffer
     float *harris = nullptr;   // optional Harris output of the next batches (omv_orb_set_harris)
     uint8_t *d_pyr = nullptr;
     int *d_cell_cnt = nullptr;
@@ -1616,28 +1629,8 @@ static void mark(omv_orb *o, hipStream_t st) {
     o->ev.push_back(e);
 }
 
-// A FAST cell with the constants K2 reads instead of deriving (struct Cell): the same integer expressions the
-// kernel used to evaluate per wave.
-static Cell fast_cell_constants(int level, int y0, int y1, int x0, int x1) {
-    Cell c{};
-    c.level = level, c.y0 = y0, c.y1 = y1, c.x0 = x0, c.x1 = x1;
-    const int rw = x1 - x0, rh = y1 - y0, dw = rw - 6, dh = rh - 6;
-    c.o = x0 & 3;
-    c.nd = (rw + c.o + 3) >> 2;
-    c.rpi = c.nd > 0 ? 64 / c.nd : 0;
-    c.nband = c.rpi > 0 ? rh / c.rpi : 0;
-    c.mnd = c.nd > 0 ? (1u << 16) / (uint32_t)c.nd + 1u : 0u;   // exact while lane * nd < 2^16
-    c.ndet = (dw > 0 && dh > 0) ? dw * dh : 0;
-    c.mdw = dw > 0 ? (1u << 20) / (uint32_t)dw + 1u : 0u;
-    c.jq0 = (c.o + 3) >> 2;
-    const int jq1 = (c.o + rw - 4) >> 2, nqr = jq1 - c.jq0 + 1;
-    c.npr = (nqr + 1) >> 1;
-    c.np = c.npr * dh;
-    c.mp = c.npr > 0 ? (1u << 20) / (uint32_t)c.npr + 1u : 0u;
-    return c;
-}
-
-static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vector<XTab> &xt, std::vector<XTab> &yt, std::vector<XQuad> &xq) {
+static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vector<FastSlot> &slots, std::vector<XTab> &xt,
+                                  std::vector<XTab> &yt, std::vector<XQuad> &xq) {
     const omv_orb_params &p = o->p;
     const int nl = p.nlevels;
     // ORBextractor ctor tables (:362-391): scaleFactor is a double member
@@ -1688,30 +1681,12 @@ static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vect
         L.scale = o->scale[l];
         L.size = (float)(int)(31 * o->scale[l]);
         L.quota = o->quota[l];
-        // FAST cells (:718-742)
-        const float width = (float)(L.maxBX - kMinB), height = (float)(L.maxBY - kMinB);
-        const int nCols = (int)(width / 35.f), nRows = (int)(height / 35.f);
-        // a level too small for one 35-px cell has no cells: the reference's loops over 0 rows / 0 columns do not
-        // run (its cell size, a float division by zero, is then never used) and the level yields no keypoint
-        const bool has_cells = nCols >= 1 && nRows >= 1;
-        const int wCell = has_cells ? (int)std::ceil(width / nCols) : 0, hCell = has_cells ? (int)std::ceil(height / nRows) : 0;
+        // FAST cells (:718-742): fast_plan.h
         L.cell_begin = (int)cells.size();
-        long long cap_lvl = 0;
-        for (int i = 0; has_cells && i < nRows; ++i) {
-            const float iniY = (float)(kMinB + i * hCell);
-            float maxY = iniY + hCell + 6;
-            if (iniY >= L.maxBY - 3) continue;
-            if (maxY > L.maxBY) maxY = (float)L.maxBY;
-            for (int j = 0; j < nCols; ++j) {
-                const float iniX = (float)(kMinB + j * wCell);
-                float maxX = iniX + wCell + 6;
-                if (iniX >= L.maxBX - 6) continue;
-                if (maxX > L.maxBX) maxX = (float)L.maxBX;
-                const Cell c = fast_cell_constants(l, (int)iniY, (int)maxY, (int)iniX, (int)maxX);
-                cells.push_back(c);
-                max_rw = std::max(max_rw, c.x1 - c.x0);
-                max_rh = std::max(max_rh, c.y1 - c.y0);
-            }
+        omv_fast_plan::fast_level_cells(l, L.w, L.h, cells);
+        for (size_t i = (size_t)L.cell_begin; i < cells.size(); ++i) {
+            max_rw = std::max(max_rw, cells[i].x1 - cells[i].x0);
+            max_rh = std::max(max_rh, cells[i].y1 - cells[i].y0);
         }
         L.cell_end = (int)cells.size();
         max_cells_lvl = std::max(max_cells_lvl, L.cell_end - L.cell_begin);
@@ -1725,7 +1700,6 @@ static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vect
         L.out_off = out_off;
         out_off += L.out_cap;
         max_nodes = std::max(max_nodes, std::max(L.quota + 3, 4 * L.nIni + 4));
-        (void)cap_lvl;
         // resize tables (cv::resize INTER_LINEAR, :1083)
         if (l > 0) {
             const int sw = prev_w, sh = prev_h, dw = L.w, dh = L.h;
@@ -1801,9 +1775,10 @@ static omv_status build_geometry(omv_orb *o, std::vector<Cell> &cells, std::vect
     g.ccnt_cap = (std::max(4 * g.node_cap, max_cells_lvl) + 15) & ~15;
     // K2's row stride: an odd dword count (rows spread over the LDS banks) -- 13 dwords when every cell row plus its
     // misalignment fits, else 17, else per cell; OMV_FAST_RS=68 forces the wider stride (A/B)
-    o->fast_rs = max_rw + 3 <= 52 ? 52 : max_rw + 3 <= 68 ? 68 : 0;
+    o->fast_rs = omv_fast_plan::fast_row_stride(max_rw);
     if (const char *e = getenv("OMV_FAST_RS"))
         if (std::atoi(e) == 68 && max_rw + 3 <= 68) o->fast_rs = 68;
+    omv_fast_plan::plan_fast_slots(cells, o->fast_rs, slots);   // the prefilter's slot table, for this stride
     o->rmax = ((o->fast_rs ? o->fast_rs * max_rh : ((max_rw + 6) & ~3) * max_rh) + 15) & ~15;   // rows: rw + misalignment
     // the strength map over rows / columns 2 .. n-3 (the NMS reach), then the candidate list (u16, worst case every
     // detection-window pixel): the LDS per wave sets K2's occupancy
@@ -1847,9 +1822,10 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
     if (const char *pm = getenv("OMV_PYR_MODE")) o->pyr_mode = std::strcmp(pm, "chain") == 0 ? 1 : 0;
     (void)hipGetDevice(&o->device);
     std::vector<Cell> cells;
+    std::vector<FastSlot> slots;
     std::vector<XTab> xt, yt;
     std::vector<XQuad> xq;
-    omv_status st = build_geometry(o, cells, xt, yt, xq);
+    omv_status st = build_geometry(o, cells, slots, xt, yt, xq);
     if (st != OMV_OK) return st;
     if (o->oct_lds > 160 * 1024) return OMV_ERR_ARG;
     // 1080p levels hold ~1,500 cells: the octree's node lists then exceed the default 64 KB dynamic LDS
@@ -1861,8 +1837,12 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
         return OMV_ERR_HIP;
     const Geom &g = o->g;
     const size_t n = (size_t)max_images;
-    if (!mem.alloc(&o->d_cells, cells.size())) return OMV_ERR_HIP;
+    // the cells and, behind them, their prefilter slots: one buffer
+    const size_t slot_cells = (sizeof(FastSlot) * slots.size() + sizeof(Cell) - 1) / sizeof(Cell);
+    if (!mem.alloc(&o->d_cells, cells.size() + slot_cells)) return OMV_ERR_HIP;
+    o->d_slots = reinterpret_cast<FastSlot *>(o->d_cells + cells.size());
     HIP_OK(hipMemcpy(o->d_cells, cells.data(), sizeof(Cell) * cells.size(), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(o->d_slots, slots.data(), sizeof(FastSlot) * slots.size(), hipMemcpyHostToDevice));
     for (int l = 1; l < g.nlevels; ++l) {   // K1 LDS: the generic path's x table + the most source rows a row block reads
         const LevelGeom &L = g.lv[l];
         int nr = 0;
@@ -1949,9 +1929,15 @@ omv_status omv_orb_create(const omv_orb_params *params, int width, int height, i
     if (!mem.alloc(&o->d_xq, xq.size())) return OMV_ERR_HIP;
     if (!xq.empty()) HIP_OK(hipMemcpy(o->d_xq, xq.data(), sizeof(XQuad) * xq.size(), hipMemcpyHostToDevice));
     {
+        // K4's per-lane tables, one buffer: the centroid masks (2 KB), then the Toeplitz operands
         const std::vector<uint32_t> dt = disc_table(o->umax);
-        if (!mem.alloc(&o->d_disc, dt.size())) return OMV_ERR_HIP;
+        uint64_t bop[4 * 64];
+        omv_fast_plan::describe_bop_table(bop);
+        static_assert(64 * 8 * sizeof(uint32_t) % sizeof(uint64_t) == 0, "the operands follow the masks, 8-byte aligned");
+        if (!mem.alloc(&o->d_disc, dt.size() + sizeof(bop) / sizeof(uint32_t))) return OMV_ERR_HIP;
+        o->d_bop = reinterpret_cast<uint64_t *>(o->d_disc + dt.size());
         HIP_OK(hipMemcpy(o->d_disc, dt.data(), sizeof(uint32_t) * dt.size(), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(o->d_bop, bop, sizeof(bop), hipMemcpyHostToDevice));
     }
     if (!mem.alloc(&o->d_pyr, std::max<size_t>(256, (size_t)g.pyr_bytes * n)) ||
         !mem.alloc(&o->d_cell_cnt, (size_t)g.n_cells * n) || !mem.alloc(&o->d_cell_kp, (size_t)g.n_cells * g.cell_cap * n) ||
@@ -2018,15 +2004,15 @@ omv_status omv_orb_extract_batch(omv_orb *o, int n, const uint8_t *images, size_
     // K2: FAST per cell
     if (o->fast_rs == 52)
         fast_cells_kernel<52><<<omv::xcd_grid(g.n_cells * n), 64, o->fast_lds, st>>>(
-            g, o->d_cells, images, image_stride, pitch, o->d_pyr, o->d_cell_cnt, o->d_cell_kp, o->rmax, o->smax,
+            g, o->d_cells, o->d_slots, images, image_stride, pitch, o->d_pyr, o->d_cell_cnt, o->d_cell_kp, o->rmax, o->smax,
             g.n_cells * n);
     else if (o->fast_rs == 68)
         fast_cells_kernel<68><<<omv::xcd_grid(g.n_cells * n), 64, o->fast_lds, st>>>(
-            g, o->d_cells, images, image_stride, pitch, o->d_pyr, o->d_cell_cnt, o->d_cell_kp, o->rmax, o->smax,
+            g, o->d_cells, o->d_slots, images, image_stride, pitch, o->d_pyr, o->d_cell_cnt, o->d_cell_kp, o->rmax, o->smax,
             g.n_cells * n);
     else
         fast_cells_kernel<0><<<omv::xcd_grid(g.n_cells * n), 64, o->fast_lds, st>>>(
-            g, o->d_cells, images, image_stride, pitch, o->d_pyr, o->d_cell_cnt, o->d_cell_kp, o->rmax, o->smax,
+            g, o->d_cells, o->d_slots, images, image_stride, pitch, o->d_pyr, o->d_cell_cnt, o->d_cell_kp, o->rmax, o->smax,
             g.n_cells * n);
     mark(o, st);
     // K3: octree per (image, level)
@@ -2036,7 +2022,7 @@ omv_status omv_orb_extract_batch(omv_orb *o, int n, const uint8_t *images, size_
     mark(o, st);
     // K4: orientation + blur at the samples + descriptors, one wave per output slot
     DescArgs da{images, image_stride, pitch, o->d_pyr, o->d_lvl_out, o->d_lvl_cls, o->d_lvl_cnt, kps, desc, n_out, mono_index, n,
-                o->d_disc, o->harris};
+                o->d_disc, o->harris, o->d_bop};
     const int waves = g.out_per_img * n;
     describe_kernel<<<omv::xcd_grid((waves + 3) / 4), 256, 0, st>>>(g, da, (waves + 3) / 4);
     mark(o, st);
