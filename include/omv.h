@@ -1460,6 +1460,76 @@ omv_status omv_vba_debug_solve(omv_vba *h, const omv_vba_opts *o, double lambda,
 omv_status omv_vba_enable_timing(omv_vba *h, int on);
 omv_status omv_vba_stage_ms(omv_vba *h, double *ms4, int *trials);
 
+/* ------------------------------------------------------------------------------------------------
+ * Optimizer::FullInertialBA (src/Optimizer.cc:368-853): the whole map's inertial bundle adjustment, as LocalMapping::
+ * InitializeIMU runs it after InertialOptimization and Map::ApplyScaledRotation (src/LocalMapping.cc:1387-1406), VIBA 1 /
+ * VIBA 2 and the global BA of an inertial map.  The full inertial kind of the omv_lba solver: the same edges (EdgeMono,
+ * EdgeStereo, EdgeInertial), Schur complement, block LDL^T, LM control and host plan.  Every EdgeInertial is Huber
+ * sqrt(16.92) at its full information (:514-516); there is no outlier round and no FAIL guard.
+ *   shared_bias == 0 (bInit false): every bImu keyframe has its own VertexGyroBias / VertexAccBias, and every inertial
+ *     edge carries one EdgeGyroRW and one EdgeAccRW (:520-538).
+ *   shared_bias == 1 (bInit): all keyframes share one pair, which vertices G and A of every EdgeInertial are; no
+ *     random-walk edges; EdgePriorGyro / EdgePriorAcc (error 0 - b, information prior * I3, no robust kernel) on the pair
+ *     (:441-450, :484-487, :544-563).  The pair starts at bg0 / ba0 (pIncKF's bias) and every bImu keyframe holds it on
+ *     return (:818-829).  The reduced system then has one more block, bordering every keyframe with an inertial edge.
+ * base: the flattened map as an omv_lba_problem -- with bFixLocal the maxKFid keyframe is listed last and n_opt = n_kf
+ * - 1, otherwise n_opt = n_kf; kf_imu 0: a pose vertex only; inertial edges between two bImu keyframes only (:469);
+ * pt_track_depth, imu_robust and imu_info_scale are not read (may be NULL).  A map point seen by fixed keyframes only
+ * is no vertex (:771-774): it does not move and its edges add nothing.  Single rank.
+ * Left with the caller: SetNewBias(prevKF->GetImuBias()) on every preintegration before the call (:470), the nLoopId
+ * != 0 write-back into the *GBA members, pbStopFlag, Map::ApplyScaledRotation, MergeInertialBA.
+ * ---------------------------------------------------------------------------------------------- */
+struct omv_fiba_problem {
+    omv_lba_problem base;      /* rig, keyframes, points, visual and inertial edges (state in/out) */
+    int shared_bias;           /* bInit */
+    double prior_g, prior_a;   /* priorG / priorA (floats widened to double, :554, :560); >= 0; read when shared_bias */
+    double bg0[3], ba0[3];     /* the shared pair's starting value; read when shared_bias */
+};
+typedef struct omv_fiba_problem omv_fiba_problem;
+
+struct omv_fiba_opts {
+    int iterations;            /* its: optimize(its) */
+    double lambda_init;        /* setUserLambdaInit(1e-5) (:393) */
+    int max_trials;            /* maxTrialsAfterFailure (10) */
+};
+typedef struct omv_fiba_opts omv_fiba_opts;
+
+struct omv_fiba_result {
+    double err, err_end;       /* activeRobustChi2 before optimize() / of the last computed errors */
+    int iterations, trials;
+    double lambda;             /* final lambda */
+    double *mono_chi2;         /* optional [n_mono]: e->chi2() at the final state; 0 on an edge that is not in the graph */
+    double *stereo_chi2;       /* optional [n_stereo] */
+};
+typedef struct omv_fiba_result omv_fiba_result;
+
+typedef struct omv_fiba omv_fiba;
+
+/* Capacities: keyframes, cameras, points, visual edges (EdgeMono + EdgeStereo), inertial edges. */
+omv_status omv_fiba_create(int max_kf, int max_cams, int max_pts, int max_edges, int max_imu, omv_fiba **out);
+omv_status omv_fiba_destroy(omv_fiba *h);
+/* Upload and plan a problem.  OMV_ERR_ARG before any launch, the previous problem kept: a size beyond the capacities
+ * (n_kf > max_kf, n_imu > max_imu, ...), an out-of-range index, and with shared_bias no inertial edge, an inertial edge on a keyframe
+ * that is not bImu, or a negative or non-finite prior.  OMV_ERR_HIP leaves no problem. */
+omv_status omv_fiba_set_problem(omv_fiba *h, const omv_fiba_problem *p);
+/* optimize(o->iterations) from the state on the device (it stays there for the next call); the state arrays of
+ * p->base receive the result.  Synchronous. */
+omv_status omv_fiba_optimize(omv_fiba *h, const omv_fiba_opts *o, omv_fiba_problem *p, omv_fiba_result *r);
+/* Errors and visual Jacobians at the device state for parity, in the caller's edge order (any may be NULL; zero on an
+ * edge that is not in the graph): as omv_lba_evaluate / omv_lba_evaluate_stereo, then prior_err [6]: EdgePriorGyro's and
+ * EdgePriorAcc's errors 0 - b (zero without a shared pair). */
+omv_status omv_fiba_evaluate(omv_fiba *h, double *mono_err, double *mono_jx, double *mono_jp, double *imu_err,
+                             double *stereo_err, double *stereo_jx, double *stereo_jp, double *prior_err);
+/* The state uploaded by the last set_problem again. */
+omv_status omv_fiba_reset(omv_fiba *h);
+/* omv_lba_debug_solve for this kind; n = 16 (n_opt + shared_bias): the shared pair is block n_opt (rows 9..14, the
+ * rest padding); plan_cap >= 4 + n_opt + shared_bias. */
+omv_status omv_fiba_debug_solve(omv_fiba *h, double lambda, double *S, double *rhs, double *x, int32_t *fail,
+                                int32_t *plan, int plan_cap);
+/* omv_lba_enable_timing / omv_lba_stage_ms for this kind. */
+omv_status omv_fiba_enable_timing(omv_fiba *h, int on);
+omv_status omv_fiba_stage_ms(omv_fiba *h, double *ms4, int *trials);
+
 #ifdef __cplusplus
 }
 #endif

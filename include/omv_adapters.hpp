@@ -31,6 +31,8 @@
 //   Sim3Solver              Sim3Solver (src/Sim3Solver.cc) at LoopClosing::DetectCommonRegionsFromBoW's call site
 //                           (src/LoopClosing.cc:812-832): constructor, SetRansacParameters, both iterate overloads,
 //                           find, GetEstimated*; the samples drawn with std::rand() in RandomInt's formula
+//   FullInertialBA          Optimizer::FullInertialBA (src/Optimizer.cc:368-853) on the flattened map: bFixLocal, bInit
+//                           (the shared bias pair under its two priors), the state written back as :786-850 do
 //
 // Errors: every omv_status != OMV_OK throws omv_adapt::Error (the adapters' callers are C++).
 #ifndef OMV_ADAPTERS_HPP
@@ -1853,6 +1855,98 @@ inline void LocalBundleAdjustment(LocalBAView &view, bool *pbStopFlag, bool bIne
     for (int e = 0; e < S; ++e)
         if (so[e]) v.vToErase.emplace_back(v.stereo_kf[e], v.stereo_pt[e]);
     erase_cam(2), erase_cam(3);
+}
+
+// ---- Optimizer::FullInertialBA (src/Optimizer.cc:368-853) --------------------------------------------------------
+// The map flattened by the caller in the order the reference builds its graph (:402-775): the keyframes of
+// GetAllKeyFrames() with mnId <= maxKFid that are not fixed, then -- with bFixLocal -- the maxKFid keyframe; the points
+// of GetAllMapPoints(); per observation of a keyframe with mnId <= maxKFid that is not bad an EdgeMono (camera c) or,
+// on camera 0 with mvuRight >= 0, an EdgeStereo; one inertial edge per keyframe that passes the tests of :461-469
+// (mPrevKF set, neither newer than maxKFid, not bad, both bImu), each preintegration already at
+// SetNewBias(mPrevKF->GetImuBias()) (:470).  bg0 / ba0: pIncKF's bias, read when bInit.
+struct FullInertialMap {
+    int n_cams = 0;
+    std::vector<float> cam;                        // [n_cams][8]
+    std::vector<int32_t> cam_model;                // [n_cams]; empty: all KannalaBrandt8
+    std::vector<double> Rcb, tcb, Rbc, tbc;        // [n_cams][9] / [3]
+    float bf = 0.f;
+    std::vector<uint8_t> kf_imu;                   // [K] KeyFrame::bImu
+    std::vector<double> Rwb, twb, Rcw, tcw, vel, bg, ba;   // [K][9], [K][3], [K][n_cams][9], [K][n_cams][3], [K][3] x 3; in / out
+    std::vector<double> pts;                       // [P][3]; in / out
+    std::vector<int32_t> mono_pt, mono_kf, mono_cam;
+    std::vector<double> mono_obs;                  // [E][2]
+    std::vector<float> mono_inv_sigma2;
+    std::vector<int32_t> stereo_pt, stereo_kf;
+    std::vector<double> stereo_obs;                // [S][3]
+    std::vector<float> stereo_inv_sigma2;
+    std::vector<int32_t> imu_kf1, imu_kf2;         // mPrevKF, the keyframe
+    std::vector<float> preint;                     // [NI][OMV_PREINT_FLOATS]
+    double bg0[3] = {0, 0, 0}, ba0[3] = {0, 0, 0};
+    // outputs (the state arrays above receive the vertices' estimates, as :786-850 write them back; with bInit every
+    // bImu keyframe's bg / ba is the shared pair)
+    std::vector<uint8_t> pt_not_included;          // [P] vbNotIncludedMP: no vertex, not written back
+    double err = 0, err_end = 0;
+    int iterations = 0, trials = 0;
+};
+
+// void Optimizer::FullInertialBA(Map *pMap, int its, const bool bFixLocal, const long unsigned int nLoopId, bool
+// *pbStopFlag, bool bInit, float priorG, float priorA, ...): `map` stands for pMap.  Returns false where the reference
+// returns before optimising (bFixLocal with fewer than three free keyframes, :452-455; *pbStopFlag, :777-779).  The
+// caller keeps nLoopId (where the result goes: the members or their *GBA twins), the stop inside optimize() and what
+// surrounds the call (Map::ApplyScaledRotation, IncreaseChangeIndex).
+inline bool FullInertialBA(FullInertialMap &map, int its, bool bFixLocal, bool *pbStopFlag = nullptr, bool bInit = false,
+                           float priorG = 1e2f, float priorA = 1e6f, omv_fiba *h = nullptr) {
+    FullInertialMap &m = map;
+    const int K = (int)m.kf_imu.size(), P = (int)(m.pts.size() / 3), E = (int)m.mono_pt.size(), S = (int)m.stereo_pt.size();
+    const int NI = (int)m.imu_kf1.size(), C = m.n_cams;
+    if (m.Rwb.size() != (size_t)9 * K || m.twb.size() != (size_t)3 * K || m.Rcw.size() != (size_t)9 * K * C ||
+        m.tcw.size() != (size_t)3 * K * C || m.vel.size() != (size_t)3 * K || m.bg.size() != (size_t)3 * K ||
+        m.ba.size() != (size_t)3 * K || m.mono_kf.size() != (size_t)E || m.mono_cam.size() != (size_t)E ||
+        m.mono_obs.size() != (size_t)2 * E || m.mono_inv_sigma2.size() != (size_t)E || m.stereo_kf.size() != (size_t)S ||
+        m.stereo_obs.size() != (size_t)3 * S || m.stereo_inv_sigma2.size() != (size_t)S || m.imu_kf2.size() != (size_t)NI ||
+        m.preint.size() != (size_t)NI * OMV_PREINT_FLOATS || m.cam.size() != (size_t)8 * C)
+        throw Error("FullInertialBA: array lengths differ");
+    const int n_opt = bFixLocal ? K - 1 : K;
+    if (bFixLocal && n_opt < 3) return false;   // nNonFixed < 3
+    if (pbStopFlag && *pbStopFlag) return false;
+    omv_fiba *own = nullptr;
+    if (!h) {
+        check(omv_fiba_create(K, C, std::max(P, 1), std::max(E + S, 1), std::max(NI, 1), &own), "omv_fiba_create");
+        h = own;
+    }
+    omv_fiba_problem p{};
+    omv_lba_problem &b = p.base;
+    b.n_cams = C, b.cam = m.cam.data(), b.cam_model = m.cam_model.empty() ? nullptr : m.cam_model.data();
+    b.Rcb = m.Rcb.data(), b.tcb = m.tcb.data(), b.Rbc = m.Rbc.data(), b.tbc = m.tbc.data(), b.bf = m.bf;
+    b.n_kf = K, b.n_opt = n_opt, b.kf_imu = m.kf_imu.data();
+    b.Rwb = m.Rwb.data(), b.twb = m.twb.data(), b.Rcw = m.Rcw.data(), b.tcw = m.tcw.data();
+    b.vel = m.vel.data(), b.bg = m.bg.data(), b.ba = m.ba.data();
+    b.n_pts = P, b.pts = m.pts.data();
+    b.n_mono = E, b.mono_pt = m.mono_pt.data(), b.mono_kf = m.mono_kf.data(), b.mono_cam = m.mono_cam.data();
+    b.mono_obs = m.mono_obs.data(), b.mono_inv_sigma2 = m.mono_inv_sigma2.data();
+    b.n_stereo = S, b.stereo_pt = m.stereo_pt.data(), b.stereo_kf = m.stereo_kf.data(), b.stereo_obs = m.stereo_obs.data();
+    b.stereo_inv_sigma2 = m.stereo_inv_sigma2.data();
+    b.n_imu = NI, b.imu_kf1 = m.imu_kf1.data(), b.imu_kf2 = m.imu_kf2.data(), b.preint = m.preint.data();
+    p.shared_bias = bInit ? 1 : 0, p.prior_g = (double)priorG, p.prior_a = (double)priorA;   // double infoPriorG = priorG
+    for (int q = 0; q < 3; ++q) p.bg0[q] = m.bg0[q], p.ba0[q] = m.ba0[q];
+    // vbNotIncludedMP (:583, :771-774): no free keyframe observes the point
+    for (int e = 0; e < E; ++e)
+        if (m.mono_pt[e] < 0 || m.mono_pt[e] >= P) throw Error("FullInertialBA: a map point index out of range");
+    for (int e = 0; e < S; ++e)
+        if (m.stereo_pt[e] < 0 || m.stereo_pt[e] >= P) throw Error("FullInertialBA: a map point index out of range");
+    m.pt_not_included.assign((size_t)P, 1);
+    for (int e = 0; e < E; ++e)
+        if (m.mono_kf[e] < n_opt) m.pt_not_included[m.mono_pt[e]] = 0;
+    for (int e = 0; e < S; ++e)
+        if (m.stereo_kf[e] < n_opt) m.pt_not_included[m.stereo_pt[e]] = 0;
+    const omv_fiba_opts o{its, 1e-5, 10};   // setUserLambdaInit(1e-5) (:393)
+    omv_fiba_result r{};
+    omv_status rc = omv_fiba_set_problem(h, &p);
+    if (rc == OMV_OK) rc = omv_fiba_optimize(h, &o, &p, &r);
+    if (own) (void)omv_fiba_destroy(own);
+    check(rc, "omv_fiba_set_problem / omv_fiba_optimize");
+    m.err = r.err, m.err_end = r.err_end, m.iterations = r.iterations, m.trials = r.trials;
+    return true;
 }
 
 }  // namespace omv_adapt

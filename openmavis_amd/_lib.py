@@ -256,6 +256,22 @@ class VbaResult(ctypes.Structure):
                 ("stereo_chi2", ctypes.c_void_p), ("stereo_outlier", ctypes.c_void_p)]
 
 
+class FibaProblem(ctypes.Structure):
+    """omv_fiba_problem (include/omv.h)."""
+    _fields_ = [("base", LbaProblem), ("shared_bias", ctypes.c_int), ("prior_g", ctypes.c_double),
+                ("prior_a", ctypes.c_double), ("bg0", ctypes.c_double * 3), ("ba0", ctypes.c_double * 3)]
+
+
+class FibaOpts(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("lambda_init", ctypes.c_double), ("max_trials", ctypes.c_int)]
+
+
+class FibaResult(ctypes.Structure):
+    _fields_ = [("err", ctypes.c_double), ("err_end", ctypes.c_double), ("iterations", ctypes.c_int),
+                ("trials", ctypes.c_int), ("lambda_", ctypes.c_double), ("mono_chi2", ctypes.c_void_p),
+                ("stereo_chi2", ctypes.c_void_p)]
+
+
 # numpy dtype with the omv_kp layout (24 bytes)
 try:
     import numpy as _np
@@ -400,6 +416,15 @@ SIGNATURES = {
                                  _VP, _I]),
     "omv_vba_enable_timing": (_I, [_VP, _I]),
     "omv_vba_stage_ms": (_I, [_VP, _VP, ctypes.POINTER(_I)]),
+    "omv_fiba_create": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(_VP)]),
+    "omv_fiba_destroy": (_I, [_VP]),
+    "omv_fiba_set_problem": (_I, [_VP, ctypes.POINTER(FibaProblem)]),
+    "omv_fiba_optimize": (_I, [_VP, ctypes.POINTER(FibaOpts), ctypes.POINTER(FibaProblem), ctypes.POINTER(FibaResult)]),
+    "omv_fiba_evaluate": (_I, [_VP] + [_VP] * 8),
+    "omv_fiba_reset": (_I, [_VP]),
+    "omv_fiba_debug_solve": (_I, [_VP, ctypes.c_double, _VP, _VP, _VP, ctypes.POINTER(_I), _VP, _I]),
+    "omv_fiba_enable_timing": (_I, [_VP, _I]),
+    "omv_fiba_stage_ms": (_I, [_VP, _VP, ctypes.POINTER(_I)]),
     "omv_debug_live_allocations": (_I, [ctypes.POINTER(ctypes.c_int64)]),
     "omv_debug_fail_allocation": (_I, [_I]),
 }

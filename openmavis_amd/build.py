@@ -90,6 +90,8 @@ INERTIAL_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "inertial_opt_consume
 INERTIAL_CONSUMER_BIN = os.path.join(PKG, "bin", "inertial_opt_consumer")
 VBA_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "vba_consumer.cpp")
 VBA_CONSUMER_BIN = os.path.join(PKG, "bin", "vba_consumer")
+FIBA_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "fiba_consumer.cpp")
+FIBA_CONSUMER_BIN = os.path.join(PKG, "bin", "fiba_consumer")
 
 
 def build_consumer(verbose=True, src=CONSUMER_SRC, out=CONSUMER_BIN):
@@ -122,6 +124,7 @@ def build_all(force=False, verbose=True):
     build_consumer(verbose, MLPNP_CONSUMER_SRC, MLPNP_CONSUMER_BIN)
     build_consumer(verbose, INERTIAL_CONSUMER_SRC, INERTIAL_CONSUMER_BIN)
     build_consumer(verbose, VBA_CONSUMER_SRC, VBA_CONSUMER_BIN)
+    build_consumer(verbose, FIBA_CONSUMER_SRC, FIBA_CONSUMER_BIN)
     return lib
 
 

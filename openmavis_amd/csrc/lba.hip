@@ -269,40 +269,66 @@ __device__ __forceinline__ int vis_edge_jacobians(const Rig &rig, const Kind<tru
     return st ? 3 : 2;
 }
 
-// EdgeInertial + random-walk errors, one block (threads >= I.n contribute 0 to the fixed-order sum).
+// EdgeInertial i with its random-walk edges at state s: the errors and chi2 into err9; returns the robust chi2.
+__device__ __forceinline__ double imu_err_edge(const State &s, const Imu &I, int i, double delta, double dsqr, double *err9) {
+    double r0 = 0;
+    double e[9];
+    imu_error(s, I, i, e, err9 + (size_t)10 * I.n + 9 * (size_t)i);   // + the rotation error for buildSystem
+    const double *W = I.info9 + (size_t)i * 81;
+    double c2 = 0;
+    for (int r = 0; r < 9; ++r) {
+        double t = 0;
+        for (int c = 0; c < 9; ++c) t += W[r * 9 + c] * e[c];
+        c2 += e[r] * t;
+    }
+    for (int q = 0; q < 9; ++q) err9[9 * (size_t)i + q] = e[q];
+    err9[(size_t)9 * I.n + i] = c2;   // chi2 after the errors
+    if (I.robust[i]) {
+        double r1;
+        huber(c2, delta, dsqr, r0, r1);
+    } else {
+        r0 = c2;
+    }
+    const int k1 = I.kf1[i], k2 = I.kf2[i];
+    double eg[3], ea[3];
+    for (int q = 0; q < 3; ++q) eg[q] = s.bg[3 * k2 + q] - s.bg[3 * k1 + q], ea[q] = s.ba[3 * k2 + q] - s.ba[3 * k1 + q];
+    double tg[3], ta[3];
+    mv3(I.infoG + 9 * i, eg, tg);
+    mv3(I.infoA + 9 * i, ea, ta);
+    r0 += eg[0] * tg[0] + eg[1] * tg[1] + eg[2] * tg[2];
+    r0 += ea[0] * ta[0] + ea[1] * ta[1] + ea[2] * ta[2];
+    return r0;
+}
+
+// EdgeInertial + random-walk errors of the first kImuLead edges, one block, one edge per thread (threads >= I.n
+// contribute 0 to the fixed-order sum).  A whole map has more edges than that: imu_err_rest_kernel takes the others.
+constexpr int kImuLead = 256;
 __device__ __forceinline__ void imu_err_block(double *sh, State s, Imu I, double delta, double dsqr, double *err9,
                                               double *partial) {
     const int i = threadIdx.x;
     double r0 = 0;
-    if (i < I.n) {
-        double e[9];
-        imu_error(s, I, i, e, err9 + (size_t)10 * I.n + 9 * (size_t)i);   // + the rotation error for buildSystem
-        const double *W = I.info9 + (size_t)i * 81;
-        double c2 = 0;
-        for (int r = 0; r < 9; ++r) {
-            double t = 0;
-            for (int c = 0; c < 9; ++c) t += W[r * 9 + c] * e[c];
-            c2 += e[r] * t;
-        }
-        for (int q = 0; q < 9; ++q) err9[9 * i + q] = e[q];
-        err9[(size_t)9 * I.n + i] = c2;   // chi2 after the errors
-        if (I.robust[i]) {
-            double r1;
-            huber(c2, delta, dsqr, r0, r1);
-        } else {
-            r0 = c2;
-        }
-        const int k1 = I.kf1[i], k2 = I.kf2[i];
-        double eg[3], ea[3];
-        for (int q = 0; q < 3; ++q) eg[q] = s.bg[3 * k2 + q] - s.bg[3 * k1 + q], ea[q] = s.ba[3 * k2 + q] - s.ba[3 * k1 + q];
-        double tg[3], ta[3];
-        mv3(I.infoG + 9 * i, eg, tg);
-        mv3(I.infoA + 9 * i, ea, ta);
-        r0 += eg[0] * tg[0] + eg[1] * tg[1] + eg[2] * tg[2];
-        r0 += ea[0] * ta[0] + ea[1] * ta[1] + ea[2] * ta[2];
-    }
+    if (i < I.n) r0 = imu_err_edge(s, I, i, delta, dsqr, err9);
     const double t = block_reduce_sum(r0, sh);
     if (threadIdx.x == 0) partial[0] = t;
+}
+
+// The inertial edges from kImuLead on, launched after err_kernel only for a problem that has any (err_kernel's block 0
+// has written the state they are evaluated at): one block, thread t takes edges kImuLead + t, + blockDim.x, .. and
+// adds their robust chi2 in that order, then the block's fixed-order sum onto the inertial partial.  A kernel of its
+// own because the same loop inside err_kernel takes that kernel from 146 to 241 VGPRs for every window that never
+// has such edges.  Gated and buffered like err_kernel.
+__global__ void __launch_bounds__(256) imu_err_rest_kernel(State s0, State s1, Imu I, double delta, double dsqr, ErrBufs e0,
+                                                           ErrBufs e1, double *imu_partial, const LmCtl *ctl, int gate,
+                                                           int role) {
+    __shared__ double sh[8];
+    if (!gate_open(ctl, gate)) return;
+    const int bi = role_buf(ctl, role);
+    const State s = bi ? s1 : s0;
+    const ErrBufs eb = bi ? e1 : e0;
+    double acc = 0;
+    for (int i = kImuLead + threadIdx.x; i < I.n; i += blockDim.x) acc += imu_err_edge(s, I, i, delta, dsqr, eb.err9);
+    const double t = block_reduce_sum(acc, sh);
+    if (threadIdx.x == 0) imu_partial[0] += t;
 }
 
 // activeRobustChi2: inertial partial + visual partials in a fixed order (one block of 256).
@@ -1168,7 +1194,23 @@ __device__ __forceinline__ double run_sum(const double *base, int n, int stride,
 // runs (and, on a diagonal block, the 12 right-hand-side runs) is cut into kAsmSplit fixed contiguous pieces summed by
 // separate threads, the pieces then added in piece order -- a fixed order, so the result is the same run to run.
 constexpr int kAsmSplit = 7;
-__global__ void __launch_bounds__(256) assemble_kernel(Gather G, Imu I, BlockPat P, const double *rec,
+
+// FullInertialBA's bInit form (Optimizer.cc:441-450, :484-487, :544-563): one VertexGyroBias / VertexAccBias pair for
+// every keyframe, as block `blk` of the reduced system (rows 9..14 of its 16; -1: every keyframe has its own pair, the
+// other members unused).  An inertial edge then has three sides (LbaPlan::imu_blk): side 2 is the pair's block and
+// takes the G / A variables of the edge's form, local 9..14 (kf1's in the per-keyframe form; the residual reads
+// bg[kf1], and every bImu keyframe holds the pair's value), sides 0 / 1 keep P and V (local 0..8, 15..23).
+// EdgePriorGyro / EdgePriorAcc (G2oTypes.h:704-747, G2oTypes.cc:787-795): error 0 - b, Jacobian -I, information
+// prior * I3, no robust kernel: prior on the block's diagonal, -J^T Omega e = prior * (0 - b) in its gradient.
+struct SharedB {
+    int blk, kf;               // the pair's block; a keyframe holding its value
+    double prior_g, prior_a;   // infoPriorG / infoPriorA (floats widened, :554, :560)
+    const double *bg[2], *ba[2];   // the two state buffers' bias arrays
+};
+__device__ __forceinline__ int imu_loc(int side, int r) { return side == 2 ? r : 15 * side + r; }
+__device__ __forceinline__ bool imu_loc_ok(int side, int r) { return side == 2 ? r >= 9 : r < 9; }
+
+__global__ void __launch_bounds__(256) assemble_kernel(Gather G, Imu I, BlockPat P, SharedB B, const double *rec,
                                                        const double *rec_rhs, double lambda, int pose_lambda, double *S,
                                                        double *bvec, double *coef, const LmCtl *ctl) {
     if (!gate_open(ctl, kGateTrial)) return;
@@ -1177,6 +1219,7 @@ __global__ void __launch_bounds__(256) assemble_kernel(Gather G, Imu I, BlockPat
     const int t = blockIdx.x, tid = threadIdx.x;
     const int kr = P.slot_kr[t], kc = P.slot_kc[t];
     const bool diag = kr == kc;
+    const bool shared = B.blk >= 0;   // launch-uniform
     if (tid < 36 * kAsmSplit) {
         const int pair = tid % 36, piece = tid / 36;
         const int g0 = G.blk_start[t], n = G.blk_start[t + 1] - g0, chunk = (n + kAsmSplit - 1) / kAsmSplit;
@@ -1199,7 +1242,16 @@ __global__ void __launch_bounds__(256) assemble_kernel(Gather G, Imu I, BlockPat
     if (!diag || c <= r) {
         if (r < 6 && c < 6)
             for (int piece = 0; piece < kAsmSplit; ++piece) v += part[piece][6 * r + c];
-        if (r < 15 && c < 15) {   // inertial edges touching the block (variable groups present in the system)
+        if (shared) {
+            if (r < 15 && c < 15) {   // three-sided inertial edges (a keyframe with one is bImu: the plan's check)
+                for (int q = G.ib_start[t]; q < G.ib_start[t + 1]; ++q) {
+                    const int4 e = G.imu_blk[q];
+                    if (imu_loc_ok(e.y, r) && imu_loc_ok(e.z, c))
+                        v += G.contrib[(size_t)e.x * kImuContrib + imu_loc(e.y, r) * kImuLoc + imu_loc(e.z, c)];
+                }
+                if (kr == B.blk && diag && r == c && r >= 9) v += r < 12 ? B.prior_g : B.prior_a;   // the two priors
+            }
+        } else if (r < 15 && c < 15) {   // inertial edges touching the block (variable groups present in the system)
             const bool rows_ok = r < 6 || I.offV[kr] >= 0, cols_ok = c < 6 || I.offV[kc] >= 0;
             if (rows_ok && cols_ok)
                 for (int q = G.ib_start[t]; q < G.ib_start[t + 1]; ++q) {
@@ -1214,7 +1266,17 @@ __global__ void __launch_bounds__(256) assemble_kernel(Gather G, Imu I, BlockPat
         double bv = 0, cf = 0;
         if (tid < 6)
             for (int piece = 0; piece < kAsmSplit; ++piece) bv += rpart[piece][tid], cf += rpart[piece][6 + tid];
-        if (tid < 15 && (tid < 6 || I.offV[kr] >= 0))
+        if (shared) {
+            if (tid < 15)
+                for (int q = G.iv_start[kr]; q < G.iv_start[kr + 1]; ++q) {
+                    const int2 e = G.imu_vec[q];
+                    if (imu_loc_ok(e.y, tid)) bv += G.contrib[(size_t)e.x * kImuContrib + kImuLoc * kImuLoc + imu_loc(e.y, tid)];
+                }
+            if (kr == B.blk && tid >= 9 && tid < 15) {   // the priors at the current state's pair
+                const int cur = role_buf(ctl, 0);
+                bv += tid < 12 ? B.prior_g * (0.0 - B.bg[cur][3 * B.kf + tid - 9]) : B.prior_a * (0.0 - B.ba[cur][3 * B.kf + tid - 12]);
+            }
+        } else if (tid < 15 && (tid < 6 || I.offV[kr] >= 0))
             for (int q = G.iv_start[kr]; q < G.iv_start[kr + 1]; ++q) {
                 const int2 e = G.imu_vec[q];
                 bv += G.contrib[(size_t)e.x * kImuContrib + kImuLoc * kImuLoc + 15 * e.y + tid];
@@ -1616,6 +1678,10 @@ struct ErrTrial {
     int n_opt;
     const int16_t *e_lkf;    // [E] the edge keyframe's index in its group's list, -1 fixed
     const int *lkf_kf;       // per group (at Land::grp_kf[g]) its keyframes
+    // the shared bias pair (SharedB; shared_kf < 0: none): the fixed keyframes n_opt .. bias_end - 1 take its step too
+    // (offG / offA of every bImu keyframe are the pair's rows), and its two prior edges add prior * |b|^2 to the chi2
+    int shared_kf, bias_end;
+    double prior_g, prior_a;
 };
 template <bool V>
 __global__ void __launch_bounds__(256) err_kernel(int n_grp, int lead, int has_imu, Rig rig, Kind<V> kd, State s0, State s1, Edges E,
@@ -1656,6 +1722,12 @@ __global__ void __launch_bounds__(256) err_kernel(int n_grp, int lead, int has_i
                         }
                     }
                 }
+                for (int k = T.n_opt + tid; k < T.bias_end; k += blockDim.x)   // (shared pair only) fixed bImu keyframes
+                    if (T.offG[k] >= 0)
+                        for (int q = 0; q < 3; ++q) {
+                            s.bg[3 * k + q] = a.bg[3 * k + q] + T.xp[T.offG[k] + q];
+                            s.ba[3 * k + q] = a.ba[3 * k + q] + T.xp[T.offA[k] + q];
+                        }
                 double sc = 0;   // pose part of sum_j x_j (lambda x_j + b_j); b is the assembled gradient (bvec)
                 for (int q = tid; q < R.n; q += blockDim.x) sc += T.xp[q] * (lambda * T.xp[q] + T.b[q]);
                 const double tt = block_reduce_sum(sc, sh);
@@ -1664,6 +1736,11 @@ __global__ void __launch_bounds__(256) err_kernel(int n_grp, int lead, int has_i
                 __syncthreads();
             }
             if (has_imu) imu_err_block(sh, s, I, delta_imu, dsqr_imu, eb.err9, imu_partial);
+            if (T.shared_kf >= 0 && tid == 0) {   // EdgePriorGyro + EdgePriorAcc (thread 0 wrote the partial itself)
+                const double *g = s.bg + 3 * T.shared_kf, *ac = s.ba + 3 * T.shared_kf;
+                imu_partial[0] += T.prior_g * (g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) +
+                                  T.prior_a * (ac[0] * ac[0] + ac[1] * ac[1] + ac[2] * ac[2]);
+            }
             return;
         }
         --bid;
@@ -1914,6 +1991,11 @@ struct LbaDeviceProblem {
     Imu I{};
     BlockPat BP{};
     Gather G{};
+    SharedB sb{-1, -1, 0.0, 0.0, {nullptr, nullptr}, {nullptr, nullptr}};   // the shared bias pair (omv_fiba's bInit form)
+    // omv_fiba: the caller's edges in the graph (a map point seen by fixed keyframes only is no vertex, its edges are
+    // left out): graph edge -> caller edge
+    std::vector<int> fiba_mono, fiba_stereo;
+    int fiba_n_mono = 0, fiba_n_stereo = 0;   // the caller's edge counts
     double *d_imu_contrib = nullptr;   // [n_imu][30 x 30 + 30] per-edge inertial contributions
     const int16_t *d_e_lkf = nullptr;   // per edge: its keyframe's index in the group's list (-1: fixed)
     const int *d_lkf_kf = nullptr;      // per (group, local keyframe): the keyframe
@@ -1963,6 +2045,7 @@ struct omv_lba : LbaDeviceProblem {
     bool timing = false;       // direct launches with per-stage events instead of the captured step
     bool host_lm = false;      // force the host-driven LM loop (parity checks of the device control)
     bool visual = false;       // an omv_vba handle: the visual kind of every kernel that depends on the parameterisation
+    bool fiba = false;         // an omv_fiba handle: FullInertialBA's graph on the inertial kind's kernels
     int rank = 0, world = 1;   // landmark sharding (omv_lba_set_comm)
     omv_allreduce_fn allreduce = nullptr;
     void *ar_ctx = nullptr;
@@ -2007,10 +2090,10 @@ omv_lba::~omv_lba() {   // `mem` frees h_out, h_ctl and d_ctl after this body
 // OMV_ERR_HIP the caller frees the partial problem.
 static omv_status upload_problem(omv_lba *h, const omv_lba_problem *p) {
     const LbaPlan &pl = h->plan;
-    const int C = p->n_cams, K = p->n_kf, NI = p->n_imu, nb = p->n_opt;
+    const int C = p->n_cams, K = p->n_kf, NI = p->n_imu, nb = pl.nb;   // nb: blocks of the reduced system
     const int P = (int)pl.order.size(), E = (int)pl.perm_edge.size(), nred = pl.n_red, n_slots = pl.n_slots;
     const size_t ni = (size_t)std::max(NI, 0);
-    h->n_kf = K, h->n_opt = nb, h->n_imu = NI, h->n_pts = P, h->n_mono = E;
+    h->n_kf = K, h->n_opt = p->n_opt, h->n_imu = NI, h->n_pts = P, h->n_mono = E;
     h->n_mono_all = p->n_mono, h->n_stereo_all = std::max(p->n_stereo, 0);
     h->imu_here = NI > 0 && h->rank == 0;
     Rig &rig = h->rig;
@@ -2060,6 +2143,7 @@ static omv_status upload_problem(omv_lba *h, const omv_lba_problem *p) {
     }
     h->d_offP = upv(pl.offP), h->d_offV = upv(pl.offV), h->d_offG = upv(pl.offG), h->d_offA = upv(pl.offA);
     h->R = Red{nred, h->d_offP, K};
+    h->sb.blk = pl.shared_blk, h->sb.kf = pl.shared_kf;   // (the priors: omv_fiba_set_problem)
     // inertial edges, then the reduction work lists
     std::vector<uint8_t> rob(ni, 0);
     if (p->imu_robust) std::copy(p->imu_robust, p->imu_robust + ni, rob.begin());
@@ -2164,8 +2248,9 @@ static omv_status launch_errors(omv_lba *h, const State &s0, const State &s1, co
     const int ng = h->n_mono > 0 || xp ? h->plan.n_lgrp : 0;
     const int lead = xp || h->imu_here ? 1 : 0;
     const int blocks = (ng > 0 ? omv::xcd_grid(ng) : 0) + lead;
+    const SharedB &sb = h->sb;
     const ErrTrial T{xp, n_acc % 3 == 2 ? 1 : 0, h->d_bb, lambda, h->d_offV, h->d_offG, h->d_offA, h->n_opt, h->d_e_lkf,
-                     h->d_lkf_kf};
+                     h->d_lkf_kf, sb.blk >= 0 ? sb.kf : -1, sb.blk >= 0 ? h->n_kf : h->n_opt, sb.prior_g, sb.prior_a};
     const size_t lds = (3 * (size_t)kGrpLand + 12 * (size_t)kGrpW * h->rig.n_cams) * sizeof(double);
     auto launch = [&](auto kernel, auto kd) {
         kernel<<<blocks, 256, lds, h->stream>>>(ng, lead, h->imu_here ? 1 : 0, h->rig, kd, s0, s1, h->E, h->L, h->R, T,
@@ -2180,6 +2265,10 @@ static omv_status launch_errors(omv_lba *h, const State &s0, const State &s1, co
         if (h->visual) launch(err_kernel<true>, h->vis);
         else launch(err_kernel<false>, Kind<false>{});
     }
+    if (h->imu_here && h->n_imu > kImuLead)   // a whole map: the edges past the lead block's one per thread
+        imu_err_rest_kernel<<<1, 256, 0, h->stream>>>(s0, s1, h->I, h->delta_imu, h->dsqr_imu, h->eb(0),
+                                                      one_buffer ? h->eb(0) : h->eb(1),
+                                                      init_partials ? h->d_imu_partial0 : h->d_imu_partial, ctl, gate, role);
     return hipGetLastError() == hipSuccess ? OMV_OK : OMV_ERR_HIP;
 }
 static int n_grp_err(const omv_lba *h) { return h->n_mono > 0 ? h->plan.n_lgrp : 0; }
@@ -2303,8 +2392,10 @@ static omv_status launch_build(omv_lba *h, const State &A, const State &B, const
     return OMV_OK;
 }
 
-static omv_status launch_assemble(omv_lba *h, double lambda, const LmCtl *c) {
-    assemble_kernel<<<h->BP.n_slots, 256, 0, h->stream>>>(h->G, h->I, h->BP, h->L.rec, h->L.rec_rhs, lambda,
+static omv_status launch_assemble(omv_lba *h, const State &A, const State &B, double lambda, const LmCtl *c) {
+    SharedB sb = h->sb;   // the priors' gradient reads the current state's pair (A; by the control block's `cur`: A or B)
+    sb.bg[0] = A.bg, sb.ba[0] = A.ba, sb.bg[1] = B.bg, sb.ba[1] = B.ba;
+    assemble_kernel<<<h->BP.n_slots, 256, 0, h->stream>>>(h->G, h->I, h->BP, sb, h->L.rec, h->L.rec_rhs, lambda,
                                                           h->rank == 0 ? 1 : 0, h->d_S, h->d_bb, h->d_coef, c);
     HIP_OK(hipGetLastError());
     return OMV_OK;
@@ -2340,7 +2431,7 @@ static omv_status lba_step(omv_lba *h, hipEvent_t *ev) {
     }
     if ((rs = launch_build(h, A, B, c, 0.0)) != OMV_OK) return rs;
     if (ev) HIP_OK(hipEventRecord(ev[1], st));
-    if ((rs = launch_assemble(h, 0.0, c)) != OMV_OK) return rs;
+    if ((rs = launch_assemble(h, A, B, 0.0, c)) != OMV_OK) return rs;
     // sharded: one in-place SUM of this rank's partial reduced system [blocks | b | Schur rhs], ordered on the stream
     if ((rs = lba_allreduce(h, h->d_S, h->plan.n_reduce)) != OMV_OK) return rs;
     if (ev) HIP_OK(hipEventRecord(ev[2], st));
@@ -2538,7 +2629,7 @@ omv_status omv_lba_optimize(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *
             if ((rs = launch_build(h, A, A, nullptr, lm.lambda)) != OMV_OK) return rs;
             HIP_OK(hipEventRecord(h->ev[1], st));
             HIP_OK(hipEventRecord(h->ev[2], st));
-            if ((rs = launch_assemble(h, lm.lambda, nullptr)) != OMV_OK) return rs;
+            if ((rs = launch_assemble(h, A, A, lm.lambda, nullptr)) != OMV_OK) return rs;
             // one exchange: sum the partial reduced systems [blocks | b | Schur rhs] of the landmark shards
             if ((rs = lba_allreduce(h, h->d_S, h->plan.n_reduce)) != OMV_OK) return rs;
             HIP_OK(hipEventRecord(h->ev[3], st));
@@ -2700,7 +2791,7 @@ omv_status omv_lba_reset(omv_lba *h) {
 
 omv_status omv_lba_set_comm(omv_lba *h, int rank, int world, omv_allreduce_fn allreduce, void *ctx) {
     if (!h || world < 1 || rank < 0 || rank >= world || (world > 1 && !allreduce)) return OMV_ERR_ARG;
-    if (h->visual) return OMV_ERR_ARG;   // the visual kind is single-rank
+    if (h->visual || h->fiba) return OMV_ERR_ARG;   // the visual and the full inertial kinds are single-rank
     h->rank = rank, h->world = world, h->allreduce = allreduce, h->ar_ctx = ctx;
     return OMV_OK;
 }
@@ -2774,7 +2865,7 @@ omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda,
     omv_status rs;
     if ((rs = lba_errors(h, A)) != OMV_OK) return rs;
     if ((rs = launch_build(h, A, A, nullptr, lambda)) != OMV_OK) return rs;
-    if ((rs = launch_assemble(h, lambda, nullptr)) != OMV_OK) return rs;
+    if ((rs = launch_assemble(h, A, A, lambda, nullptr)) != OMV_OK) return rs;
     launch_ldlt(h, nullptr);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(h->stream));
@@ -3012,5 +3103,192 @@ omv_status omv_vba_debug_solve(omv_vba *hv, const omv_vba_opts *o, double lambda
 
 omv_status omv_vba_enable_timing(omv_vba *hv, int on) { return omv_lba_enable_timing(core(hv), on); }
 omv_status omv_vba_stage_ms(omv_vba *hv, double *ms4, int *trials) { return omv_lba_stage_ms(core(hv), ms4, trials); }
+
+}  // extern "C"
+
+// ---- omv_fiba: the full inertial kind's C ABI (Optimizer::FullInertialBA, src/Optimizer.cc:368-853) ---------------------
+// An omv_fiba is an omv_lba created with `fiba`: the inertial kind's kernels, plan, LM driver and epilogue; what follows
+// translates the problem (which edges are in the graph, the robust kernels, the shared pair's value), plans it with
+// plan_fiba and reads the result in its own layout.  Single rank: there is no set_comm.
+static omv_lba *core(omv_fiba *h) { return reinterpret_cast<omv_lba *>(h); }
+
+struct FibaTranslated {
+    std::vector<int32_t> mono_pt, mono_kf, mono_cam, stereo_pt, stereo_kf;
+    std::vector<double> mono_obs, stereo_obs, bg, ba;
+    std::vector<float> mono_w, stereo_w;
+    std::vector<uint8_t> robust;
+    std::vector<int> mono_map, stereo_map;   // graph edge -> caller edge
+    omv_lba_problem lp{};
+};
+// OMV_ERR_ARG: what the planner cannot check for itself (it would read through the pointer).
+static omv_status fiba_translate(const omv_fiba_problem &fp, FibaTranslated &t) {
+    const omv_lba_problem &p = fp.base;
+    const int K = p.n_kf, P = p.n_pts, EM = p.n_mono, ES = std::max(p.n_stereo, 0), NI = p.n_imu;
+    if (K < 1 || P < 0 || EM < 0 || NI < 0 || p.n_opt < 1 || p.n_opt > K || !p.kf_imu || !p.Rwb || !p.twb || !p.Rcw ||
+        !p.tcw || !p.vel || !p.bg || !p.ba || (P > 0 && !p.pts) || !p.cam || !p.Rcb || !p.tcb || !p.Rbc || !p.tbc ||
+        (EM > 0 && (!p.mono_pt || !p.mono_kf || !p.mono_cam || !p.mono_obs || !p.mono_inv_sigma2)) ||
+        (ES > 0 && (!p.stereo_pt || !p.stereo_kf || !p.stereo_obs || !p.stereo_inv_sigma2)) ||
+        (NI > 0 && (!p.imu_kf1 || !p.imu_kf2 || !p.preint)))
+        return OMV_ERR_ARG;
+    // A map point all of whose observing keyframes are fixed is removed from the graph with its edges (bAllFixed,
+    // :583, :771-774): it keeps its place in the point array (no edge: it does not move), its edges are left out.
+    std::vector<uint8_t> free_pt((size_t)P, 0);
+    for (int e = 0; e < EM; ++e) {
+        if (p.mono_pt[e] < 0 || p.mono_pt[e] >= P || p.mono_kf[e] < 0 || p.mono_kf[e] >= K) return OMV_ERR_ARG;
+        if (p.mono_kf[e] < p.n_opt) free_pt[p.mono_pt[e]] = 1;
+    }
+    for (int e = 0; e < ES; ++e) {
+        if (p.stereo_pt[e] < 0 || p.stereo_pt[e] >= P || p.stereo_kf[e] < 0 || p.stereo_kf[e] >= K) return OMV_ERR_ARG;
+        if (p.stereo_kf[e] < p.n_opt) free_pt[p.stereo_pt[e]] = 1;
+    }
+    for (int e = 0; e < EM; ++e) {
+        if (!free_pt[p.mono_pt[e]]) continue;
+        t.mono_map.push_back(e);
+        t.mono_pt.push_back(p.mono_pt[e]), t.mono_kf.push_back(p.mono_kf[e]), t.mono_cam.push_back(p.mono_cam[e]);
+        t.mono_obs.push_back(p.mono_obs[2 * (size_t)e]), t.mono_obs.push_back(p.mono_obs[2 * (size_t)e + 1]);
+        t.mono_w.push_back(p.mono_inv_sigma2[e]);
+    }
+    for (int e = 0; e < ES; ++e) {
+        if (!free_pt[p.stereo_pt[e]]) continue;
+        t.stereo_map.push_back(e);
+        t.stereo_pt.push_back(p.stereo_pt[e]), t.stereo_kf.push_back(p.stereo_kf[e]);
+        for (int q = 0; q < 3; ++q) t.stereo_obs.push_back(p.stereo_obs[3 * (size_t)e + q]);
+        t.stereo_w.push_back(p.stereo_inv_sigma2[e]);
+    }
+    omv_lba_problem &lp = t.lp = p;
+    lp.pt_track_depth = nullptr;
+    lp.n_mono = (int)t.mono_map.size();
+    lp.mono_pt = t.mono_pt.data(), lp.mono_kf = t.mono_kf.data(), lp.mono_cam = t.mono_cam.data();
+    lp.mono_obs = t.mono_obs.data(), lp.mono_inv_sigma2 = t.mono_w.data();
+    lp.n_stereo = (int)t.stereo_map.size();
+    lp.stereo_pt = t.stereo_pt.data(), lp.stereo_kf = t.stereo_kf.data(), lp.stereo_obs = t.stereo_obs.data();
+    lp.stereo_inv_sigma2 = t.stereo_w.data();
+    // every EdgeInertial: Huber sqrt(16.92), its information unscaled (:514-516; LocalInertialBA's 1e-2 is not here)
+    t.robust.assign((size_t)std::max(NI, 1), 1);
+    lp.imu_robust = t.robust.data(), lp.imu_info_scale = nullptr;
+    if (fp.shared_bias) {   // the one pair's value in every bImu keyframe (VertexGyroBias(pIncKF), :442-446)
+        t.bg.assign(p.bg, p.bg + 3 * (size_t)K), t.ba.assign(p.ba, p.ba + 3 * (size_t)K);
+        for (int k = 0; k < K; ++k)
+            if (p.kf_imu[k])
+                for (int q = 0; q < 3; ++q) t.bg[3 * k + q] = fp.bg0[q], t.ba[3 * k + q] = fp.ba0[q];
+        lp.bg = t.bg.data(), lp.ba = t.ba.data();
+    }
+    return OMV_OK;
+}
+
+extern "C" {
+
+omv_status omv_fiba_create(int max_kf, int max_cams, int max_pts, int max_edges, int max_imu, omv_fiba **out) {
+    if (!out) return OMV_ERR_ARG;
+    omv_lba *h = nullptr;
+    const omv_status rs = omv_lba_create(max_kf, max_cams, max_pts, max_edges, max_imu, &h);
+    if (rs != OMV_OK) return rs;
+    h->fiba = true;
+    *out = reinterpret_cast<omv_fiba *>(h);
+    return OMV_OK;
+}
+
+omv_status omv_fiba_destroy(omv_fiba *h) { return omv_lba_destroy(core(h)); }
+
+omv_status omv_fiba_set_problem(omv_fiba *hf, const omv_fiba_problem *p) {
+    omv_lba *h = core(hf);
+    if (!h || !h->fiba || !p) return OMV_ERR_ARG;
+    FibaTranslated t;
+    omv_status rs = fiba_translate(*p, t);
+    if (rs != OMV_OK) return rs;
+    LbaPlan plan;
+    const LbaLimits lim{h->max_kf, h->max_cams, h->max_pts, h->max_mono, h->max_imu};
+    rs = plan_fiba(t.lp, p->shared_bias != 0, p->prior_g, p->prior_a, lim, h->lds_ok, plan);
+    if (rs != OMV_OK) return rs;
+    free_problem(h);
+    h->plan = std::move(plan);
+    rs = upload_problem(h, &t.lp);
+    if (rs != OMV_OK) {
+        free_problem(h);
+        return rs;
+    }
+    h->sb.prior_g = p->shared_bias ? p->prior_g : 0.0, h->sb.prior_a = p->shared_bias ? p->prior_a : 0.0;
+    h->fiba_mono = std::move(t.mono_map), h->fiba_stereo = std::move(t.stereo_map);
+    h->fiba_n_mono = p->base.n_mono, h->fiba_n_stereo = std::max(p->base.n_stereo, 0);
+    return OMV_OK;
+}
+
+omv_status omv_fiba_optimize(omv_fiba *hf, const omv_fiba_opts *o, omv_fiba_problem *p, omv_fiba_result *r) {
+    omv_lba *h = core(hf);
+    if (!h || !h->fiba || !o || !p || !r || !has_problem(h) || o->max_trials < 1 || !(o->lambda_init > 0.0) ||
+        p->base.n_kf != h->n_kf || p->base.n_pts != h->n_pts || p->base.n_mono != h->fiba_n_mono ||
+        std::max(p->base.n_stereo, 0) != h->fiba_n_stereo || !p->base.Rwb || !p->base.twb || !p->base.Rcw ||
+        !p->base.tcw || !p->base.vel || !p->base.bg || !p->base.ba || (h->n_pts > 0 && !p->base.pts))
+        return OMV_ERR_ARG;
+    const omv_lba_opts lo{o->iterations, o->lambda_init, o->max_trials, 1};   // large: no FAIL guard here
+    std::vector<double> mc(r->mono_chi2 ? h->fiba_mono.size() + 1 : 0), sc(r->stereo_chi2 ? h->fiba_stereo.size() + 1 : 0);
+    omv_lba_result lr{};
+    lr.mono_chi2 = r->mono_chi2 ? mc.data() : nullptr, lr.stereo_chi2 = r->stereo_chi2 ? sc.data() : nullptr;
+    for (double &m : h->stage_ms) m = 0;
+    omv_status rs = lba_optimize_device(h, &lo, &lr);
+    if (rs != OMV_OK) return rs;
+    const LmCtl &c = *h->h_ctl;
+    r->err = c.err0, r->err_end = c.errors_chi, r->iterations = c.its, r->trials = c.trials, r->lambda = c.lm.lambda;
+    // the state in the caller's order (every bImu keyframe holds the shared pair: the update wrote it to each) and the
+    // chi2 of the graph's edges; no outlier test, no FAIL status: the reference has neither in this function
+    if ((rs = lba_finish_result(h, &lo, &p->base, &lr)) != OMV_OK) return rs;
+    if (r->mono_chi2) {
+        std::fill(r->mono_chi2, r->mono_chi2 + h->fiba_n_mono, 0.0);
+        for (size_t e = 0; e < h->fiba_mono.size(); ++e) r->mono_chi2[h->fiba_mono[e]] = mc[e];
+    }
+    if (r->stereo_chi2) {
+        std::fill(r->stereo_chi2, r->stereo_chi2 + h->fiba_n_stereo, 0.0);
+        for (size_t e = 0; e < h->fiba_stereo.size(); ++e) r->stereo_chi2[h->fiba_stereo[e]] = sc[e];
+    }
+    return OMV_OK;
+}
+
+omv_status omv_fiba_evaluate(omv_fiba *hf, double *mono_err, double *mono_jx, double *mono_jp, double *imu_err,
+                             double *stereo_err, double *stereo_jx, double *stereo_jp, double *prior_err) {
+    omv_lba *h = core(hf);
+    if (!h || !h->fiba || !has_problem(h)) return OMV_ERR_ARG;
+    const size_t EM = h->fiba_mono.size(), ES = h->fiba_stereo.size();
+    // the graph's edges, then scattered into the caller's order
+    std::vector<double> me(2 * EM + 1), mx(6 * EM + 1), mp(12 * EM + 1), se(3 * ES + 1), sx(9 * ES + 1), sp(18 * ES + 1);
+    const omv_status rs = lba_eval(h, me.data(), mx.data(), mp.data(), imu_err, se.data(), sx.data(), sp.data());
+    if (rs != OMV_OK) return rs;
+    auto scatter = [](double *dst, const std::vector<double> &src, const std::vector<int> &map, int n_all, int w) {
+        if (!dst) return;
+        std::fill(dst, dst + (size_t)n_all * w, 0.0);
+        for (size_t e = 0; e < map.size(); ++e) std::copy(&src[e * w], &src[e * w] + w, dst + (size_t)map[e] * w);
+    };
+    scatter(mono_err, me, h->fiba_mono, h->fiba_n_mono, 2), scatter(mono_jx, mx, h->fiba_mono, h->fiba_n_mono, 6);
+    scatter(mono_jp, mp, h->fiba_mono, h->fiba_n_mono, 12);
+    scatter(stereo_err, se, h->fiba_stereo, h->fiba_n_stereo, 3), scatter(stereo_jx, sx, h->fiba_stereo, h->fiba_n_stereo, 9);
+    scatter(stereo_jp, sp, h->fiba_stereo, h->fiba_n_stereo, 18);
+    if (prior_err) {
+        std::fill(prior_err, prior_err + 6, 0.0);
+        if (h->sb.blk >= 0) {   // EdgePriorGyro / EdgePriorAcc::computeError: bprior (zero) - the vertex's estimate
+            const State &s = h->st[h->cur];
+            double b[6];
+            HIP_OK(hipMemcpy(b, s.bg + 3 * h->sb.kf, 3 * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(b + 3, s.ba + 3 * h->sb.kf, 3 * sizeof(double), hipMemcpyDeviceToHost));
+            for (int q = 0; q < 6; ++q) prior_err[q] = 0.0 - b[q];
+        }
+    }
+    return OMV_OK;
+}
+
+omv_status omv_fiba_reset(omv_fiba *hf) {
+    omv_lba *h = core(hf);
+    if (!h || !h->fiba) return OMV_ERR_ARG;
+    return omv_lba_reset(h);
+}
+
+omv_status omv_fiba_debug_solve(omv_fiba *hf, double lambda, double *S, double *rhs, double *x, int32_t *fail,
+                                int32_t *plan, int plan_cap) {
+    omv_lba *h = core(hf);
+    if (!h || !h->fiba || !has_problem(h)) return OMV_ERR_ARG;
+    const omv_lba_opts lo{1, 1e-5, 10, 1};   // validated only
+    return omv_lba_debug_solve(h, &lo, lambda, S, rhs, x, fail, plan, plan_cap);
+}
+
+omv_status omv_fiba_enable_timing(omv_fiba *hf, int on) { return omv_lba_enable_timing(core(hf), on); }
+omv_status omv_fiba_stage_ms(omv_fiba *hf, double *ms4, int *trials) { return omv_lba_stage_ms(core(hf), ms4, trials); }
 
 }  // extern "C"

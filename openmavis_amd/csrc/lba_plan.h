@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <numeric>
 #include <set>
@@ -123,14 +124,18 @@ inline int symbolic_ldlt(int nb, const std::vector<uint8_t> &adj, const std::vec
 // the fewest elimination-tree levels whose blocks fit `max_slots` wins (ties: fewer blocks, then earlier).
 // The solution of the damped system does not depend on the order beyond rounding (SimplicialLDLT's own AMD
 // ordering is a different one again, linear_solver_eigen.h:60).
-inline std::vector<int> plan_order(int nb, const std::vector<uint8_t> &adj, int max_slots) {
+// max_cuts > 0: at most that many cuts are tried, evenly spaced over 1 .. nb - 1 (a whole map's planning time: every
+// cut costs one symbolic factorisation); 0 tries every cut.
+inline std::vector<int> plan_order(int nb, const std::vector<uint8_t> &adj, int max_slots, int max_cuts = 0) {
     std::vector<int> best(nb);
     std::iota(best.begin(), best.end(), 0);
     std::vector<uint8_t> pat;
     std::vector<int> lev;
     int best_slots = 0;
     int best_h = symbolic_ldlt(nb, adj, best, pat, lev, best_slots);
-    for (int cut = 1; cut < nb; ++cut) {
+    const int n_cuts = max_cuts > 0 ? std::min(max_cuts, nb - 1) : nb - 1;
+    for (int ci = 0; ci < n_cuts; ++ci) {
+        const int cut = n_cuts == nb - 1 ? 1 + ci : 1 + (int)((long long)ci * (nb - 2) / std::max(n_cuts - 1, 1));
         std::vector<int> order, sep;
         for (int v = 0; v < cut; ++v) {
             bool s = false;
@@ -160,6 +165,10 @@ struct LbaPlan {
     // reduced-system layout: keyframe block k at 16k: pose 0-5, v 6-8, bg 9-11, ba 12-14, pad 15 (-1: none)
     std::vector<int> offP, offV, offG, offA;
     int n_pt_slots = 0, n_red = 0;   // (landmark, keyframe) slots; rows of the reduced system
+    // blocks of the reduced system: the optimisable keyframes, then (FullInertialBA's bInit form, plan_fiba) the one
+    // VertexGyroBias / VertexAccBias pair every keyframe shares as block `shared_blk` = n_opt (-1: none): rows 9..14 of
+    // its 16, the rest padding; `shared_kf`: the first bImu keyframe, where the kernels read the pair's value
+    int nb = 0, shared_blk = -1, shared_kf = -1;
     // block pattern (slot_kr / slot_kc: the keyframes of each stored block, column-major in positions) and the level
     // schedule of its LDL^T, also packed into `blob` (16-byte aligned sub-arrays at `off`) for the solver
     int n_slots = 0, n_lev = 0;      // stored blocks; elimination-tree levels
@@ -191,11 +200,18 @@ struct PlanWork {   // what one step of plan_lba hands to the next and the devic
 
 // Step 1: the problem's sizes checked, the reduced layout, this rank's landmarks and their edges in device order, and
 // the keyframe adjacency from ALL landmarks (every rank of a sharded solve lays out the identical packed system).
-inline omv_status plan_edge_order(const omv_lba_problem &p, int rank, int world, const LbaLimits &lim, LbaPlan &P,
-                                  PlanWork &W) {
+inline omv_status plan_edge_order(const omv_lba_problem &p, int rank, int world, const LbaLimits &lim, bool shared,
+                                  LbaPlan &P, PlanWork &W) {
     if (p.n_cams <= 0 || p.n_cams > lim.max_cams || p.n_kf > lim.max_kf || p.n_pts < 0 || p.n_mono < 0 ||
         p.n_imu > lim.max_imu || p.n_opt > p.n_kf || p.n_opt < 1)
         return OMV_ERR_ARG;
+    P.nb = p.n_opt + (shared ? 1 : 0);
+    if (shared) {   // the pair's value lives in every bImu keyframe's bg / ba; without one there is no pair
+        for (int k = 0; k < p.n_kf && P.shared_kf < 0; ++k)
+            if (p.kf_imu[k]) P.shared_kf = k;
+        if (P.shared_kf < 0) return OMV_ERR_ARG;
+        P.shared_blk = p.n_opt;
+    }
     const int C = p.n_cams, K = p.n_kf, P_all = p.n_pts;
     const int EM = p.n_mono, ES = p.n_stereo > 0 ? p.n_stereo : 0, E_all = EM + ES;
     if (ES > 0 && (!p.stereo_pt || !p.stereo_kf || !p.stereo_obs || !p.stereo_inv_sigma2)) return OMV_ERR_ARG;
@@ -209,11 +225,14 @@ inline omv_status plan_edge_order(const omv_lba_problem &p, int rank, int world,
     auto e_cam_of = [&](int e) { return e < EM ? p.mono_cam[e] : 0; };
     // reduced-system layout: per optimisable keyframe pose (6) [+ v bg ba (9)]
     P.offP.assign(K, -1), P.offV.assign(K, -1), P.offG.assign(K, -1), P.offA.assign(K, -1);
-    P.n_red = 16 * p.n_opt;
+    P.n_red = 16 * P.nb;
     for (int k = 0; k < p.n_opt; ++k) {
         P.offP[k] = 16 * k;
         if (p.kf_imu[k]) P.offV[k] = 16 * k + 6, P.offG[k] = 16 * k + 9, P.offA[k] = 16 * k + 12;
     }
+    if (shared)   // every bImu keyframe, fixed ones too, takes the pair's step: all hold its value (Optimizer.cc:818-829)
+        for (int k = 0; k < K; ++k)
+            if (p.kf_imu[k]) P.offG[k] = 16 * P.shared_blk + 9, P.offA[k] = 16 * P.shared_blk + 12;
     // landmark order: by the first optimisable keyframe observing them (workgroup keyframe spans stay small)
     std::vector<std::vector<int>> &pe = W.pe = std::vector<std::vector<int>>(P_all);
     for (int e = 0; e < E_all; ++e) {
@@ -228,13 +247,13 @@ inline omv_status plan_edge_order(const omv_lba_problem &p, int rank, int world,
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
     // block pattern of the reduced system (keyframe blocks) from ALL landmarks
-    const int nb = p.n_opt;
+    const int nb = P.nb, n_opt = p.n_opt;
     W.adj.assign((size_t)nb * nb, 0);
     for (int q = 0; q < P_all; ++q)
         for (int a : pe[q])
             for (int b : pe[q]) {
                 const int i = e_kf_of(a), j = e_kf_of(b);
-                if (i < nb && j < nb && i != j) W.adj[(size_t)i * nb + j] = 1;
+                if (i < n_opt && j < n_opt && i != j) W.adj[(size_t)i * nb + j] = 1;
             }
     // this rank's landmarks: a contiguous share of the landmark order
     if (world > 1) {
@@ -280,17 +299,46 @@ inline omv_status plan_edge_order(const omv_lba_problem &p, int rank, int world,
 
 // Step 2: the inertial pairs checked and added to the adjacency, the elimination order (every rank of a sharded solve
 // plans from the same full pattern), its symbolic LDL^T, the stored blocks and the level schedule.
-inline omv_status plan_pattern(const omv_lba_problem &p, bool lds_ok, LbaPlan &P, PlanWork &W) {
-    const int nb = p.n_opt, K = p.n_kf;
+inline omv_status plan_pattern(const omv_lba_problem &p, bool lds_ok, bool whole_map, int max_cuts, LbaPlan &P,
+                               PlanWork &W) {
+    const int nb = P.nb, n_opt = p.n_opt, K = p.n_kf, S = P.shared_blk;
     std::vector<uint8_t> &adj = W.adj, &pat = W.pat;
     for (int i = 0; i < p.n_imu; ++i) {
         const int a = p.imu_kf1[i], b = p.imu_kf2[i];
         if (a < 0 || a >= K || b < 0 || b >= K || a == b) return OMV_ERR_ARG;
-        if (a < nb && b < nb) adj[(size_t)a * nb + b] = adj[(size_t)b * nb + a] = 1;
+        if (a < n_opt && b < n_opt) adj[(size_t)a * nb + b] = adj[(size_t)b * nb + a] = 1;
+        if (S < 0) continue;
+        // the shared pair: vertices G and A of every EdgeInertial, which exists between two bImu keyframes only
+        // (Optimizer.cc:469, :485-486)
+        if (!p.kf_imu[a] || !p.kf_imu[b]) return OMV_ERR_ARG;
+        for (int k : {a, b})
+            if (k < n_opt) adj[(size_t)k * nb + S] = adj[(size_t)S * nb + k] = 1;
     }
     const size_t vec_bytes = 2 * (size_t)P.n_red * sizeof(double);
     const int lds_slots = lds_ok && kLdltLds > vec_bytes ? (int)((kLdltLds - vec_bytes) / (256 * sizeof(double))) : 0;
-    P.perm = plan_order(nb, adj, std::max(lds_slots, 1));
+    // The whole-map entry (plan_fiba), either bias form.  A whole map's blocks rarely fit the LDS: when the
+    // keyframe order itself is past the budget the hybrid storage holds whichever order wins, so the budget no longer
+    // picks among them (fewest levels, then fewest blocks).  plan_lba keeps its budget.
+    auto whole_map_budget = [&](int n, const std::vector<uint8_t> &a, int budget) {
+        if (!whole_map) return budget;
+        int ns0 = 0;
+        std::vector<int> id(n), lev;
+        std::iota(id.begin(), id.end(), 0);
+        symbolic_ldlt(n, a, id, pat, lev, ns0);
+        return ns0 > budget ? std::numeric_limits<int>::max() : budget;
+    };
+    if (S < 0) {
+        P.perm = plan_order(nb, adj, whole_map_budget(nb, adj, std::max(lds_slots, 1)), max_cuts);
+    } else {
+        // The pair's block borders every keyframe with an inertial edge: counted into a dissection it would sit in every
+        // separator and plan_order would reject every cut.  The keyframes are dissected without it (its row of at most
+        // nb blocks taken off the LDS budget) and it is eliminated last.
+        std::vector<uint8_t> sub((size_t)n_opt * n_opt);
+        for (int i = 0; i < n_opt; ++i)
+            for (int j = 0; j < n_opt; ++j) sub[(size_t)i * n_opt + j] = adj[(size_t)i * nb + j];
+        P.perm = plan_order(n_opt, sub, whole_map_budget(n_opt, sub, std::max(lds_slots - nb, 1)), max_cuts);
+        P.perm.push_back(S);
+    }
     const std::vector<int> &perm = P.perm;
     W.ipos.resize(nb);
     for (int q = 0; q < nb; ++q) W.ipos[perm[q]] = q;
@@ -369,7 +417,8 @@ inline omv_status plan_pattern(const omv_lba_problem &p, bool lds_ok, LbaPlan &P
 // its own built by the scalar path (land_group_big).  Per group: its keyframes in elimination order (local index a),
 // its record (w(w+1)/2 blocks a >= b of 36, then w rows of [gradient 6 | Schur rhs 6]), the 16x16 output tiles that
 // hold a co-observed keyframe pair, and per diagonal tile the residual rows of its keyframes' edges.
-inline void plan_groups(int nb, LbaPlan &P, const PlanWork &W) {
+inline void plan_groups(int n_opt, LbaPlan &P, const PlanWork &W) {
+    const int nb = P.nb;   // blocks (n_opt keyframes, then the shared pair if any: it observes no landmark)
     const int np = (int)P.order.size(), n_slots = P.n_slots;
     const std::vector<int> &pt_edge = P.pt_edge, &pt_slot = P.pt_slot, &slot_kf = P.slot_kf, &ipos = W.ipos, &slot = W.slot;
     std::vector<int> &grp_blk = P.grp_blk, &grp_kf = P.grp_kf, &blkoff = P.blkoff, &rhsoff = P.rhsoff;
@@ -381,7 +430,7 @@ inline void plan_groups(int nb, LbaPlan &P, const PlanWork &W) {
         std::set<int> k;
         for (int q = q0; q < q1; ++q)
             for (int a = pt_slot[q]; a < pt_slot[q + 1]; ++a)
-                if (slot_kf[a] < nb) k.insert(slot_kf[a]);
+                if (slot_kf[a] < n_opt) k.insert(slot_kf[a]);
         return k;
     };
     // the MFMA operand panels fit their LDS region
@@ -400,7 +449,7 @@ inline void plan_groups(int nb, LbaPlan &P, const PlanWork &W) {
                    pt_slot[r + 1] - pt_slot[q] <= kGrpSlots) {
                 std::set<int> k2 = k;
                 for (int a = pt_slot[r]; a < pt_slot[r + 1]; ++a)
-                    if (slot_kf[a] < nb) k2.insert(slot_kf[a]);
+                    if (slot_kf[a] < n_opt) k2.insert(slot_kf[a]);
                 if ((int)k2.size() > kGrpW || !panel_ok(r + 1 - q, (int)k2.size())) break;
                 k.swap(k2);
                 ++r;
@@ -411,9 +460,9 @@ inline void plan_groups(int nb, LbaPlan &P, const PlanWork &W) {
         std::vector<int> kl(ks.begin(), ks.end());
         std::sort(kl.begin(), kl.end(), [&](int x, int y) { return ipos[x] < ipos[y]; });
         const int w = (int)kl.size(), nblk = w * (w + 1) / 2;
-        std::vector<int> lk(nb, -1);
+        std::vector<int> lk(n_opt, -1);
         for (int a = 0; a < w; ++a) lk[kl[a]] = a;
-        for (int a = pt_slot[q]; a < pt_slot[r]; ++a) P.slot_lkf[a] = (int16_t)(slot_kf[a] < nb ? lk[slot_kf[a]] : -1);
+        for (int a = pt_slot[q]; a < pt_slot[r]; ++a) P.slot_lkf[a] = (int16_t)(slot_kf[a] < n_opt ? lk[slot_kf[a]] : -1);
         const int g = (int)P.grp_w.size();
         P.grp_w.push_back(big ? -w - 1 : w);
         grp_blk.push_back((int)blkoff.size());
@@ -426,7 +475,7 @@ inline void plan_groups(int nb, LbaPlan &P, const PlanWork &W) {
         for (int x = q; x < r; ++x) {
             std::vector<int> loc;
             for (int a = pt_slot[x]; a < pt_slot[x + 1]; ++a)
-                if (slot_kf[a] < nb) loc.push_back(lk[slot_kf[a]]);
+                if (slot_kf[a] < n_opt) loc.push_back(lk[slot_kf[a]]);
             for (int u : loc)
                 for (int v : loc)
                     if (u >= v) co[(size_t)u * w + v] = 1;
@@ -471,20 +520,27 @@ inline void plan_groups(int nb, LbaPlan &P, const PlanWork &W) {
 // Step 4: inertial edges per block (edge, side of the row keyframe, side of the column keyframe; side 0 = kf1) and per
 // keyframe (edge, side), in edge order, only on the rank that evaluates them; the inertial information (EdgeInertial
 // ctor :486-495) and random-walk information of every edge.
+// With the shared pair an edge has a third side, 2 = the pair's block: its G / A columns (local variables 9..14 of the
+// edge's form, kf1's in the per-keyframe form) belong there, the keyframe sides keep P and V, and there is no
+// random-walk edge (Optimizer.cc:484-487, :520): infoG / infoA stay zero.
 inline void plan_inertial(const omv_lba_problem &p, bool imu_here, LbaPlan &P, const PlanWork &W) {
-    const int nb = p.n_opt, NI = p.n_imu, n_slots = P.n_slots;
+    const int nb = P.nb, n_opt = p.n_opt, NI = p.n_imu, n_slots = P.n_slots, S = P.shared_blk;
+    const int n_sides = S >= 0 ? 3 : 2;
     const std::vector<int> &ipos = W.ipos, &slot = W.slot;
     P.ib_start.assign(n_slots + 1, 0), P.iv_start.assign(nb + 1, 0);
     std::vector<std::vector<Int4>> bl(n_slots);
     std::vector<std::vector<Int2>> vl(nb);
     if (imu_here)
         for (int i = 0; i < NI; ++i) {
-            const int kk[2] = {p.imu_kf1[i], p.imu_kf2[i]};
-            for (int sr = 0; sr < 2; ++sr) {
-                if (kk[sr] >= nb) continue;
+            // the block of each side; a fixed keyframe has none
+            int kk[3] = {p.imu_kf1[i], p.imu_kf2[i], S};
+            for (int sd = 0; sd < 2; ++sd)
+                if (kk[sd] >= n_opt) kk[sd] = -1;
+            for (int sr = 0; sr < n_sides; ++sr) {
+                if (kk[sr] < 0) continue;
                 vl[kk[sr]].push_back(Int2{i, sr});
-                for (int sc = 0; sc < 2; ++sc) {
-                    if (kk[sc] >= nb || ipos[kk[sr]] < ipos[kk[sc]]) continue;
+                for (int sc = 0; sc < n_sides; ++sc) {
+                    if (kk[sc] < 0 || ipos[kk[sr]] < ipos[kk[sc]]) continue;
                     bl[slot[(size_t)ipos[kk[sr]] * nb + ipos[kk[sc]]]].push_back(Int4{i, sr, sc, 0});
                 }
             }
@@ -517,6 +573,7 @@ inline void plan_inertial(const omv_lba_problem &p, bool imu_here, LbaPlan &P, c
         double g[9], a[9];
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) g[3 * r + c] = pr[(9 + r) * 15 + 9 + c], a[3 * r + c] = pr[(12 + r) * 15 + 12 + c];
+        if (S >= 0) continue;   // no EdgeGyroRW / EdgeAccRW beside a shared pair
         omv_g2o::inv3(g, &P.infoG[(size_t)9 * i]);
         omv_g2o::inv3(a, &P.infoA[(size_t)9 * i]);
     }
@@ -563,15 +620,36 @@ inline void plan_lds(bool lds_ok, LbaPlan &P) {
 
 // The plan of problem `p` for rank `rank` of `world` on a handle of capacities `lim`; lds_ok: the solver kernels may
 // take kLdltLds of dynamic LDS.  OMV_ERR_ARG for every problem omv_lba_set_problem rejects (`out` is then unspecified).
-inline omv_status plan_lba(const omv_lba_problem &p, int rank, int world, const LbaLimits &lim, bool lds_ok, LbaPlan &out) {
+// shared: the keyframes share one gyro / acc bias pair (LbaPlan::shared_blk; one rank); max_cuts: plan_order's.
+// whole_map: the LDS budget stops choosing among orders once the keyframe order itself is past it (plan_pattern).
+inline omv_status plan_problem(const omv_lba_problem &p, int rank, int world, const LbaLimits &lim, bool lds_ok, bool shared,
+                               bool whole_map, int max_cuts, LbaPlan &out) {
     out = LbaPlan{};
     PlanWork W;
-    if (plan_edge_order(p, rank, world, lim, out, W) != OMV_OK || plan_pattern(p, lds_ok, out, W) != OMV_OK)
+    if (plan_edge_order(p, rank, world, lim, shared, out, W) != OMV_OK ||
+        plan_pattern(p, lds_ok, whole_map, max_cuts, out, W) != OMV_OK)
         return OMV_ERR_ARG;
     plan_groups(p.n_opt, out, W);
     plan_inertial(p, p.n_imu > 0 && rank == 0, out, W);
     plan_lds(lds_ok, out);
     return OMV_OK;
+}
+inline omv_status plan_lba(const omv_lba_problem &p, int rank, int world, const LbaLimits &lim, bool lds_ok, LbaPlan &out) {
+    return plan_problem(p, rank, world, lim, lds_ok, false, false, 0, out);
+}
+
+// The plan of a FullInertialBA problem (omv_fiba): the whole map on one rank.  shared_bias: the bInit form (one
+// VertexGyroBias / VertexAccBias for every keyframe, Optimizer.cc:441-450), which needs an inertial edge -- with none
+// the pair would hang on its two priors alone -- and non-negative prior informations.  plan_order tries every cut at an
+// O(nb^3) symbolic factorisation each, which a local window of 25 keyframes does not feel and a map of hundreds does
+// (DESIGN has the measured times): here at most kFibaCuts evenly spaced cuts are tried.
+constexpr int kFibaCuts = 32;
+inline omv_status plan_fiba(const omv_lba_problem &p, bool shared_bias, double prior_g, double prior_a,
+                            const LbaLimits &lim, bool lds_ok, LbaPlan &out) {
+    if (shared_bias && (p.n_imu < 1 || !(prior_g >= 0.0) || !(prior_a >= 0.0) || !std::isfinite(prior_g) ||
+                        !std::isfinite(prior_a)))
+        return OMV_ERR_ARG;
+    return plan_problem(p, 0, 1, lim, lds_ok, shared_bias, true, kFibaCuts, out);
 }
 
 }  // namespace omv_lba_plan

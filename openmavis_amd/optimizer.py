@@ -283,6 +283,101 @@ class LocalBundleAdjustment:
         return dict(build=ms[0], schur=ms[1], solve=ms[2], update=ms[3], trials=t.value)
 
 
+class FullInertialBA:
+    """Optimizer::FullInertialBA's optimisation (src/Optimizer.cc:368-853) on the full inertial kind of the device
+    bundle-adjustment solver (omv_fiba, openmavis_amd/csrc/lba.hip): the whole map, every EdgeInertial Huber at its
+    full information, no outlier round.  The flattened map is a problem dict (openmavis_amd.synth_fiba.make_fiba_problem:
+    omv_lba_problem's fields plus shared_bias, prior_g, prior_a, bg0, ba0):
+
+        ba = FullInertialBA(max_kf=200, max_cams=5, max_pts=40000, max_edges=400000, max_imu=200)
+        ba.set_problem(prob)                       # shared_bias=1: bInit, one bias pair under the two priors
+        res, state = ba.optimize(iterations=100)   # lambda_init 1e-5 (:393)
+
+    `res`: err / err_end, iterations, trials, lambda_ and the per-edge chi2 (0 on an edge of a map point that only fixed
+    keyframes see: it is no vertex); `state`: Rwb, twb, Rcw, tcw, vel, bg, ba, pts -- with shared_bias every bImu keyframe
+    holds the pair.  The state stays on the device between calls.  One rank; no CPU fallback."""
+
+    def __init__(self, max_kf=200, max_cams=5, max_pts=40000, max_edges=400000, max_imu=200):
+        lib = _lib.load()
+        h = ctypes.c_void_p()
+        _lib.check(lib.omv_fiba_create(int(max_kf), int(max_cams), int(max_pts), int(max_edges), int(max_imu),
+                                       ctypes.byref(h)), "omv_fiba_create")
+        self._lib, self._h = lib, h
+        self._s = self._keep = None
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.omv_fiba_destroy(self._h)
+            self._h = None
+
+    def set_problem(self, prob):
+        from .synth_fiba import as_fiba_struct
+        s, keep = as_fiba_struct(prob, _lib.FibaProblem, _lib.LbaProblem)
+        _lib.check(self._lib.omv_fiba_set_problem(self._h, ctypes.byref(s)), "omv_fiba_set_problem")
+        self._s, self._keep = s, keep
+        return self
+
+    def _need(self, what):
+        if self._s is None:
+            raise _lib.OmvError(f"FullInertialBA.{what}: no problem set")
+
+    def optimize(self, iterations=100, lambda_init=1e-5, max_trials=10, chi2=True):
+        self._need("optimize")
+        o = _lib.FibaOpts(int(iterations), float(lambda_init), int(max_trials))
+        E, S = self._s.base.n_mono, self._s.base.n_stereo
+        c_m, c_s = (np.zeros(E), np.zeros(S)) if chi2 else (None, None)
+        r = _lib.FibaResult()
+        r.mono_chi2, r.stereo_chi2 = _lib.ptr(c_m), _lib.ptr(c_s)
+        _lib.check(self._lib.omv_fiba_optimize(self._h, ctypes.byref(o), ctypes.byref(self._s), ctypes.byref(r)),
+                   "omv_fiba_optimize")
+        res = dict(err=r.err, err_end=r.err_end, iterations=r.iterations, trials=r.trials, lambda_=r.lambda_,
+                   mono_chi2=c_m, stereo_chi2=c_s)
+        return res, read_state(self._keep)
+
+    def reset(self):
+        """The state uploaded by set_problem again (device copy)."""
+        self._need("reset")
+        _lib.check(self._lib.omv_fiba_reset(self._h), "omv_fiba_reset")
+        return self
+
+    def evaluate(self):
+        """Residuals and visual Jacobians at the device state, in the caller's edge order; prior_err: the two prior
+        edges' errors 0 - b (gyro, acc)."""
+        self._need("evaluate")
+        E, S, I = self._s.base.n_mono, self._s.base.n_stereo, self._s.base.n_imu
+        out = dict(mono_err=np.zeros((E, 2)), mono_jx=np.zeros((E, 6)), mono_jp=np.zeros((E, 12)), imu_err=np.zeros((I, 9)),
+                   stereo_err=np.zeros((S, 3)), stereo_jx=np.zeros((S, 9)), stereo_jp=np.zeros((S, 18)),
+                   prior_err=np.zeros(6))
+        _lib.check(self._lib.omv_fiba_evaluate(self._h, *[_lib.ptr(v) for v in out.values()]), "omv_fiba_evaluate")
+        return out
+
+    def debug_solve(self, lambda_):
+        """One reduced-system solve at the device state (omv_fiba_debug_solve): as LocalInertialBA.debug_solve, with
+        n = 16 (n_opt + shared_bias): the shared pair is the last block, rows 9..14 of it."""
+        self._need("debug_solve")
+        nb = int(self._s.base.n_opt) + int(self._s.shared_bias != 0)
+        n = 16 * nb
+        S, rhs, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
+        plan = np.full(4 + nb, -1, np.int32)
+        fail = ctypes.c_int(-1)
+        _lib.check(self._lib.omv_fiba_debug_solve(self._h, ctypes.c_double(lambda_), _lib.ptr(S), _lib.ptr(rhs),
+                                                  _lib.ptr(x), ctypes.byref(fail), _lib.ptr(plan), len(plan)),
+                   "omv_fiba_debug_solve")
+        n_lev = int(plan[3])
+        return dict(S=S, rhs=rhs, x=x, fail=fail.value, mode=int(plan[0]), n_slots=int(plan[1]), n_lds=int(plan[2]),
+                    n_lev=n_lev, cols=[int(v) for v in plan[4:4 + n_lev]])
+
+    def enable_timing(self, on=True):
+        _lib.check(self._lib.omv_fiba_enable_timing(self._h, int(bool(on))), "omv_fiba_enable_timing")
+        return self
+
+    def stage_ms(self):
+        ms = np.zeros(4)
+        t = ctypes.c_int(0)
+        _lib.check(self._lib.omv_fiba_stage_ms(self._h, _lib.ptr(ms), ctypes.byref(t)), "omv_fiba_stage_ms")
+        return dict(build=ms[0], schur=ms[1], solve=ms[2], update=ms[3], trials=t.value)
+
+
 class PoseInertialOptimizer:
     """Host-side mirror of Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:5021-5578)
     for a batch of frames on the device (openmavis_amd/csrc/pose.hip).
