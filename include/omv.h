@@ -1530,6 +1530,91 @@ omv_status omv_fiba_debug_solve(omv_fiba *h, double lambda, double *S, double *r
 omv_status omv_fiba_enable_timing(omv_fiba *h, int on);
 omv_status omv_fiba_stage_ms(omv_fiba *h, double *ms4, int *trials);
 
+/* ------------------------------------------------------------------------------------------------
+ * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1826-2119), its map-merging overload (:2121-2458) and
+ * Optimizer::OptimizeEssentialGraph4DoF (:6171-6480): the pose graph over every keyframe of the map that
+ * LoopClosing::CorrectLoop and MergeLocal run between the Sim3 alignment and the global BA.  g2o's Levenberg-Marquardt
+ * (20 iterations of up to 10 trials) with the edges' numeric Jacobians (base_binary_edge.hpp:131-205), on the block
+ * LDL^T of the omv_lba solver.  Single rank.
+ *   OMV_ESSGRAPH_SIM3: g2o::VertexSim3Expmap vertices (q x y z w, t, s: 8 doubles), g2o::EdgeSim3 edges, error
+ *     log(C S_i S_j^-1) with vertex 0 = i, vertex 1 = j, C = S_table[j] S_table[i]^-1, information I7, lambda_0 = 1e-16;
+ *     oplus Sim3(update) * estimate, update[6] = 0 under fix_scale.
+ *   OMV_ESSGRAPH_4DOF: VertexPose4DoF vertices ([Rcw 9 | tcw 3 | Rwb 9 | twb 3] row-major: camera 0's pose and the body
+ *     pose of ImuCamPose(pKF) or ImuCamPose(Rwc, twc, pKF); 24 doubles), Edge4DoF edges with the rotation and
+ *     translation of S_table[i] S_table[j]^-1 (scale dropped), information diag(1e3, 1e3, 1, 1, 1, 1), lambda_0 =
+ *     computeLambdaInit; oplus ImuCamPose::UpdateW((0, 0, u0, u1, u2, u3)) with its normalisation of DR after every
+ *     fifth kept update.
+ * The caller walks the map (GetAllKeyFrames, isBad, parents, loop edges, covisibility, sInsertedEdges, the minFeat
+ * test) and hands the graph over flat, the edges in the reference's creation order.  S_a is vScw (the CorrectedSim3
+ * entry where there is one, else the pose with scale 1); S_b the NonCorrectedSim3 entry, else vScw.  The merge overload
+ * is the same call: its two fixed sets are fixed flags, its vpGoodPose / vpBadPose choice is the per-edge table.
+ * Parallel edges between one pair sum; an edge between two fixed vertices adds to chi2 only.
+ * ---------------------------------------------------------------------------------------------- */
+enum { OMV_ESSGRAPH_SIM3 = 0, OMV_ESSGRAPH_4DOF = 1 };
+/* omv_essgraph_recover: which SetPose the poses are for (:2083-2088, :2419-2423, :6443-6450) */
+enum { OMV_ESSGRAPH_RECOVER_LOOP = 0, OMV_ESSGRAPH_RECOVER_MERGE = 1, OMV_ESSGRAPH_RECOVER_4DOF = 2 };
+
+struct omv_essgraph_problem {
+    int n_vertices;
+    const double *vertices;    /* [n_vertices][8] (Sim3 kind) or [n_vertices][24] (4DoF kind): the start values */
+    const uint8_t *fixed;      /* [n_vertices] setFixed */
+    const double *S_a, *S_b;   /* [n_vertices][8] the two Sim3 tables the measurements are composed from */
+    int n_edges;
+    const int32_t *edge_i, *edge_j;   /* g2o's vertex 0 / vertex 1 */
+    const int32_t *edge_table;        /* 0: S_a, 1: S_b */
+    int fix_scale;             /* Sim3 kind: VertexSim3Expmap::_fix_scale of every vertex */
+    const double *Rcb, *tcb;   /* 4DoF kind: [9], [3] the rig's mImuCalib.mTcb (camera 0); not read by the Sim3 kind */
+};
+typedef struct omv_essgraph_problem omv_essgraph_problem;
+
+struct omv_essgraph_result {
+    double err, err_end;       /* activeChi2 before optimize() / of the last computed errors */
+    int iterations, trials;
+    int solver_failed;         /* a linear solve of this optimize() hit a zero or non-finite pivot */
+    double lambda;             /* final lambda */
+    double *vertices;          /* optional [n_vertices][8 or 24]: the final estimates, layout as the problem's */
+};
+typedef struct omv_essgraph_result omv_essgraph_result;
+
+typedef struct omv_essgraph omv_essgraph;
+
+/* OMV_ERR_ARG: an unknown kind, max_vertices < 1 or max_edges < 0. */
+omv_status omv_essgraph_create(int kind, int max_vertices, int max_edges, omv_essgraph **out);
+omv_status omv_essgraph_destroy(omv_essgraph *h);
+/* Upload and plan a graph; the measurements are composed on the device.  OMV_ERR_ARG before any launch, the previous
+ * problem kept: a null array, a problem beyond the capacities, an edge naming a vertex that is not there, i == j, a
+ * table other than 0 / 1, no optimisable vertex.  OMV_ERR_HIP leaves no problem. */
+omv_status omv_essgraph_set_problem(omv_essgraph *h, const omv_essgraph_problem *p);
+/* optimize(iterations) with maxTrialsAfterFailure = max_trials from the state on the device (it stays there).  The LM
+ * control runs on the device: one host wait per call.  Synchronous. */
+omv_status omv_essgraph_optimize(omv_essgraph *h, int iterations, int max_trials, omv_essgraph_result *r);
+/* At the device state, per edge (any may be NULL): err [n_edges][7 or 6]; jac_i / jac_j [n_edges][7 x 7 or 6 x 4]
+ * row-major, g2o's numeric _jacobianOplusXi / Xj (zero for a fixed vertex); meas [n_edges][8] the Sim3 C, or
+ * [n_edges][12] Edge4DoF's [dRij 9 | dtij 3]; chi2 [n_edges]. */
+omv_status omv_essgraph_evaluate(omv_essgraph *h, double *err, double *jac_i, double *jac_j, double *meas, double *chi2);
+/* The state uploaded by the last set_problem again. */
+omv_status omv_essgraph_reset(omv_essgraph *h);
+/* One linear solve at `lambda` from the device state: the n x n system (n = 16 blocks; optimisable vertices in caller
+ * order, two Sim3 vertices per block at rows 0-6 and 7-13, four 4DoF vertices at 4 rows each, pad rows identity / zero),
+ * rhs, x, the solver's failure flag, and plan = [storage mode, stored blocks, blocks in LDS, levels, columns per level
+ * ...] (plan_cap >= 4 + levels). */
+omv_status omv_essgraph_debug_solve(omv_essgraph *h, double lambda, double *S, double *rhs, double *x, int32_t *fail,
+                                    int32_t *plan, int plan_cap);
+/* Blocks of the system of the current problem (for sizing debug_solve's arrays); 0 without a problem. */
+omv_status omv_essgraph_blocks(omv_essgraph *h, int *n_blocks, int *n_levels);
+/* The epilogue of the three functions from the device state.  poses [n_vertices][7] (optional): the Sophus::SE3f
+ * handed to SetPose as unit quaternion (x y z w) and translation -- LOOP: rotation cast to float, t.cast<float>() / s;
+ * MERGE: t / s in double, then the cast; 4DOF: (Rcw, tcw) of camera 0.  points [n_points][3] (in/out, float): point p
+ * becomes correctedSwr.map(Srw.map(P)) in double, cast to float, with r = point_ref[p], Srw = S_a[r] and correctedSwr
+ * the inverse of vertex r's estimate; point_ref -1 leaves the point untouched.  OMV_ERR_ARG: a mode that is not the
+ * handle's kind's, a reference outside -1 .. n_vertices - 1. */
+omv_status omv_essgraph_recover(omv_essgraph *h, int mode, float *poses, int n_points, float *points,
+                                const int32_t *point_ref);
+/* The pose graph is single-rank: always OMV_ERR_ARG. */
+omv_status omv_essgraph_set_comm(omv_essgraph *h, int rank, int world, omv_allreduce_fn allreduce, void *ctx);
+/* Device time of the last optimize() in milliseconds (events around its launches). */
+omv_status omv_essgraph_last_ms(omv_essgraph *h, double *ms);
+
 #ifdef __cplusplus
 }
 #endif

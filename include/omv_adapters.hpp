@@ -1949,6 +1949,73 @@ inline bool FullInertialBA(FullInertialMap &map, int its, bool bFixLocal, bool *
     return true;
 }
 
+// ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1826-2119) / OptimizeEssentialGraph4DoF (:6171-6480) ------
+// The graph flattened by the caller, who walks the map as the reference does: one vertex per keyframe of
+// GetAllKeyFrames() that is not bad; vScw (the CorrectedSim3 entry where there is one, else the pose with scale 1) and
+// vSnc (the NonCorrectedSim3 entry, else vScw), 8 doubles each (q x y z w, t, s); the edges in the reference's creation
+// order with the table their measurement is composed from -- loop connections (:1918-1945, :6248-6282) from vScw
+// (table 0), every edge of the per-keyframe loop (spanning tree, mPrevKF, GetLoopEdges, covisibility) from vSnc (table
+// 1); `fixed` 1 on pLoopKF (and on the initial keyframe of a map without IMU).  The 4DoF graph also takes the rig's Tcb
+// and per keyframe ImuCamPose(pKF) / ImuCamPose(Rwc, twc, pKF) as [Rcw | tcw | Rwb | twb]; the Sim3 graph starts at vScw.
+// The merge overload (:2121-2458) is the same call and has no adapter of its own: its two fixed sets (vpFixedKFs,
+// vpFixedCorrectedKFs) are `fixed` flags, its vpGoodPose / vpBadPose choice of the pose a measurement reads is the
+// per-edge table (0 = vScw: the good pose), and its SetPose is omv_essgraph_recover's OMV_ESSGRAPH_RECOVER_MERGE.
+struct EssentialGraphInput {
+    std::vector<double> vScw, vSnc;                // [n][8]
+    std::vector<uint8_t> fixed;                    // [n]
+    std::vector<int32_t> edge_i, edge_j, edge_table;
+    std::vector<double> pose4;                     // 4DoF: [n][24] Rcw | tcw | Rwb | twb
+    double Rcb[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tcb[3] = {0, 0, 0};   // 4DoF: mImuCalib.mTcb
+    std::vector<float> points;                     // [m][3] GetWorldPos of the map points to correct; in / out
+    std::vector<int32_t> point_ref;                // [m] the reference keyframe's vertex (mnCorrectedReference where
+                                                   // mnCorrectedByKF == pCurKF->mnId), -1: leave the point
+    // outputs
+    std::vector<float> poses;                      // [n][7] the SE3f of SetPose: unit quaternion (x y z w), translation
+    std::vector<double> vertices;                  // [n][8 or 24] the final estimates
+    double err = 0, err_end = 0;
+    int iterations = 0, trials = 0, solver_failed = 0;
+};
+
+inline void OptimizeEssentialGraphImpl(int kind, int mode, EssentialGraphInput &g, bool bFixScale, omv_essgraph *h) {
+    const int n = (int)g.fixed.size(), E = (int)g.edge_i.size(), m = (int)g.point_ref.size();
+    const bool sim3 = kind == OMV_ESSGRAPH_SIM3;
+    if (g.vScw.size() != (size_t)8 * n || g.vSnc.size() != (size_t)8 * n || g.edge_j.size() != (size_t)E ||
+        g.edge_table.size() != (size_t)E || g.points.size() != (size_t)3 * m || (!sim3 && g.pose4.size() != (size_t)24 * n))
+        throw Error("OptimizeEssentialGraph: array lengths differ");
+    omv_essgraph *own = nullptr;
+    if (!h) {
+        check(omv_essgraph_create(kind, std::max(n, 1), E, &own), "omv_essgraph_create");
+        h = own;
+    }
+    omv_essgraph_problem p{};
+    p.n_vertices = n, p.vertices = sim3 ? g.vScw.data() : g.pose4.data(), p.fixed = g.fixed.data();
+    p.S_a = g.vScw.data(), p.S_b = g.vSnc.data();
+    p.n_edges = E, p.edge_i = g.edge_i.data(), p.edge_j = g.edge_j.data(), p.edge_table = g.edge_table.data();
+    p.fix_scale = bFixScale ? 1 : 0, p.Rcb = g.Rcb, p.tcb = g.tcb;
+    g.vertices.assign((size_t)(sim3 ? 8 : 24) * n, 0.0), g.poses.assign((size_t)7 * n, 0.f);
+    omv_essgraph_result r{};
+    r.vertices = g.vertices.data();
+    omv_status rc = omv_essgraph_set_problem(h, &p);
+    if (rc == OMV_OK) rc = omv_essgraph_optimize(h, 20, 10, &r);   // optimizer.optimize(20), maxTrialsAfterFailure 10
+    if (rc == OMV_OK) rc = omv_essgraph_recover(h, mode, g.poses.data(), m, g.points.data(), g.point_ref.data());
+    if (own) (void)omv_essgraph_destroy(own);
+    check(rc, "omv_essgraph_set_problem / optimize / recover");
+    g.err = r.err, g.err_end = r.err_end, g.iterations = r.iterations, g.trials = r.trials, g.solver_failed = r.solver_failed;
+}
+
+// void Optimizer::OptimizeEssentialGraph(Map *pMap, KeyFrame *pLoopKF, KeyFrame *pCurKF, NonCorrectedSim3, CorrectedSim3,
+// LoopConnections, const bool &bFixScale): `g` stands for the map and the three containers.  g.poses[k] is what the
+// caller hands to vpKFs[k]->SetPose, g.points the corrected SetWorldPos values (UpdateNormalAndDepth:
+// omv_mappoint_normal_depth); IncreaseChangeIndex and the map mutex stay with the caller.
+inline void OptimizeEssentialGraph(EssentialGraphInput &g, bool bFixScale, omv_essgraph *h = nullptr) {
+    OptimizeEssentialGraphImpl(OMV_ESSGRAPH_SIM3, OMV_ESSGRAPH_RECOVER_LOOP, g, bFixScale, h);
+}
+// void Optimizer::OptimizeEssentialGraph4DoF(Map *pMap, KeyFrame *pLoopKF, KeyFrame *pCurKF, NonCorrectedSim3,
+// CorrectedSim3, LoopConnections)
+inline void OptimizeEssentialGraph4DoF(EssentialGraphInput &g, omv_essgraph *h = nullptr) {
+    OptimizeEssentialGraphImpl(OMV_ESSGRAPH_4DOF, OMV_ESSGRAPH_RECOVER_4DOF, g, false, h);
+}
+
 }  // namespace omv_adapt
 
 #endif  // OMV_ADAPTERS_HPP

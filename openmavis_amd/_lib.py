@@ -272,6 +272,24 @@ class FibaResult(ctypes.Structure):
                 ("stereo_chi2", ctypes.c_void_p)]
 
 
+class EssGraphProblem(ctypes.Structure):
+    """omv_essgraph_problem (include/omv.h)."""
+    _fields_ = [("n_vertices", ctypes.c_int), ("vertices", ctypes.c_void_p), ("fixed", ctypes.c_void_p),
+                ("S_a", ctypes.c_void_p), ("S_b", ctypes.c_void_p), ("n_edges", ctypes.c_int),
+                ("edge_i", ctypes.c_void_p), ("edge_j", ctypes.c_void_p), ("edge_table", ctypes.c_void_p),
+                ("fix_scale", ctypes.c_int), ("Rcb", ctypes.c_void_p), ("tcb", ctypes.c_void_p)]
+
+
+class EssGraphResult(ctypes.Structure):
+    _fields_ = [("err", ctypes.c_double), ("err_end", ctypes.c_double), ("iterations", ctypes.c_int),
+                ("trials", ctypes.c_int), ("solver_failed", ctypes.c_int), ("lambda_", ctypes.c_double),
+                ("vertices", ctypes.c_void_p)]
+
+
+ESSGRAPH_SIM3, ESSGRAPH_4DOF = 0, 1
+ESSGRAPH_RECOVER_LOOP, ESSGRAPH_RECOVER_MERGE, ESSGRAPH_RECOVER_4DOF = 0, 1, 2
+
+
 # numpy dtype with the omv_kp layout (24 bytes)
 try:
     import numpy as _np
@@ -425,6 +443,17 @@ SIGNATURES = {
     "omv_fiba_debug_solve": (_I, [_VP, ctypes.c_double, _VP, _VP, _VP, ctypes.POINTER(_I), _VP, _I]),
     "omv_fiba_enable_timing": (_I, [_VP, _I]),
     "omv_fiba_stage_ms": (_I, [_VP, _VP, ctypes.POINTER(_I)]),
+    "omv_essgraph_create": (_I, [_I, _I, _I, ctypes.POINTER(_VP)]),
+    "omv_essgraph_destroy": (_I, [_VP]),
+    "omv_essgraph_set_problem": (_I, [_VP, ctypes.POINTER(EssGraphProblem)]),
+    "omv_essgraph_optimize": (_I, [_VP, _I, _I, ctypes.POINTER(EssGraphResult)]),
+    "omv_essgraph_evaluate": (_I, [_VP] + [_VP] * 5),
+    "omv_essgraph_reset": (_I, [_VP]),
+    "omv_essgraph_debug_solve": (_I, [_VP, ctypes.c_double, _VP, _VP, _VP, ctypes.POINTER(_I), _VP, _I]),
+    "omv_essgraph_blocks": (_I, [_VP, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "omv_essgraph_recover": (_I, [_VP, _I, _VP, _I, _VP, _VP]),
+    "omv_essgraph_set_comm": (_I, [_VP, _I, _I, _VP, _VP]),
+    "omv_essgraph_last_ms": (_I, [_VP, ctypes.POINTER(ctypes.c_double)]),
     "omv_debug_live_allocations": (_I, [ctypes.POINTER(ctypes.c_int64)]),
     "omv_debug_fail_allocation": (_I, [_I]),
 }

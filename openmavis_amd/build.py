@@ -17,7 +17,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("OMV_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["orb_extract.hip", "match.hip", "lba.hip", "pose.hip", "tri.hip", "frame.hip", "imu.hip", "bow.hip", "bowmatch.hip",
-               "mappoint.hip", "fuse.hip", "sim3.hip", "pnp.hip", "optsim3.hip", "kfdb.hip", "inertial.hip", "selftest_math.hip", "omv_host.hip"]
+               "mappoint.hip", "fuse.hip", "sim3.hip", "pnp.hip", "optsim3.hip", "kfdb.hip", "inertial.hip", "essgraph.hip", "selftest_math.hip",
+               "omv_host.hip"]
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
              f"--offload-arch={ARCH}", "-Wno-unused-result"]
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
@@ -92,6 +93,8 @@ VBA_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "vba_consumer.cpp")
 VBA_CONSUMER_BIN = os.path.join(PKG, "bin", "vba_consumer")
 FIBA_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "fiba_consumer.cpp")
 FIBA_CONSUMER_BIN = os.path.join(PKG, "bin", "fiba_consumer")
+ESSGRAPH_CONSUMER_SRC = os.path.join(ROOT, "tests", "cpp", "essgraph_consumer.cpp")
+ESSGRAPH_CONSUMER_BIN = os.path.join(PKG, "bin", "essgraph_consumer")
 
 
 def build_consumer(verbose=True, src=CONSUMER_SRC, out=CONSUMER_BIN):
@@ -125,6 +128,7 @@ def build_all(force=False, verbose=True):
     build_consumer(verbose, INERTIAL_CONSUMER_SRC, INERTIAL_CONSUMER_BIN)
     build_consumer(verbose, VBA_CONSUMER_SRC, VBA_CONSUMER_BIN)
     build_consumer(verbose, FIBA_CONSUMER_SRC, FIBA_CONSUMER_BIN)
+    build_consumer(verbose, ESSGRAPH_CONSUMER_SRC, ESSGRAPH_CONSUMER_BIN)
     return lib
 
 

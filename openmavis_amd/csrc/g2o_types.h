@@ -1262,4 +1262,191 @@ __device__ inline void gs_jacobian(const float *p, const double *Rwb1, const GsS
         for (int r = 0; r < 3; ++r) J[(3 + r) * ld + 14] = dvw[r], J[(6 + r) * ld + 14] = dpw[r];
 }
 
+// ---- g2o::Sim3 (Thirdparty/g2o/g2o/types/sim3.h): the group helpers of OptimizeSim3 (optsim3.hip) and of the pose
+// graph (essgraph.hip) ----------------------------------------------------------------------------------------------
+struct Sim3d {
+    double q[4], t[3], s;
+};
+
+// Eigen::Quaterniond(Matrix3d): q_from_mat's arithmetic with the three cases of its largest-diagonal branch spelled
+// out, so that no array is indexed at run time (q_from_mat's q[i] / m[4 * i] put q and m into scratch)
+template <int I>
+__device__ __forceinline__ void os3_q_from_mat_diag(const double *m, double *q) {
+    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
+    double t = sqrt(m[4 * I] - m[4 * J] - m[4 * K] + 1.0);
+    q[I] = 0.5 * t;
+    t = 0.5 / t;
+    q[3] = (m[3 * K + J] - m[3 * J + K]) * t;
+    q[J] = (m[3 * J + I] + m[3 * I + J]) * t;
+    q[K] = (m[3 * K + I] + m[3 * I + K]) * t;
+}
+__device__ __forceinline__ void os3_q_from_mat(const double *m, double *q) {
+    double t = m[0] + m[4] + m[8];
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t, q[1] = (m[2] - m[6]) * t, q[2] = (m[3] - m[1]) * t;
+    } else if (m[4] > m[0]) {
+        if (m[8] > m[4]) os3_q_from_mat_diag<2>(m, q);
+        else os3_q_from_mat_diag<1>(m, q);
+    } else {
+        if (m[8] > m[0]) os3_q_from_mat_diag<2>(m, q);
+        else os3_q_from_mat_diag<0>(m, q);
+    }
+}
+
+// Sim3(const Vector7d &update) (Thirdparty/g2o/g2o/types/sim3.h:70-142)
+__device__ __forceinline__ Sim3d sim3_exp(const double *u) {
+    const double sigma = u[6];
+    const double theta = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    double O[9], O2[9], R[9], W[9];
+    hat3(u, O);
+    Sim3d r;
+    r.s = exp(sigma);
+    mm3(O, O, O2);
+    const double eps = 0.00001;
+    double A, B, C;
+    if (fabs(sigma) < eps) {
+        C = 1;
+        if (theta < eps) {
+            A = 1. / 2., B = 1. / 6.;
+            for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + O[k] + O2[k];
+        } else {
+            double sn, cs;
+            sincos_d(theta, sn, cs);
+            const double theta2 = theta * theta;
+            A = (1 - cs) / theta2;
+            B = (theta - sn) / (theta2 * theta);
+            const double a = sn / theta, b = (1 - cs) / (theta * theta);
+            for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + a * O[k] + b * O2[k];
+        }
+    } else {
+        C = (r.s - 1) / sigma;
+        if (theta < eps) {
+            const double sigma2 = sigma * sigma;
+            A = ((sigma - 1) * r.s + 1) / sigma2;
+            B = ((0.5 * sigma2 - sigma + 1) * r.s) / (sigma2 * sigma);
+            for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + O[k] + O2[k];
+        } else {
+            double sn, cs;
+            sincos_d(theta, sn, cs);
+            const double ra = sn / theta, rb = (1 - cs) / (theta * theta);
+            for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + ra * O[k] + rb * O2[k];
+            const double a = r.s * sn, b = r.s * cs;
+            const double theta2 = theta * theta, sigma2 = sigma * sigma;
+            const double c = theta2 + sigma2;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
+        }
+    }
+    os3_q_from_mat(R, r.q);
+    for (int k = 0; k < 9; ++k) W[k] = A * O[k] + B * O2[k] + ((k % 4 == 0) ? C : 0.0);
+    mv3(W, u + 3, r.t);
+    return r;
+}
+// Sim3::operator* (r is not renormalised), inverse and map
+__device__ __forceinline__ Sim3d sim3_mul(const Sim3d &a, const Sim3d &b) {
+    Sim3d r;
+    double rt[3];
+    q_mul(a.q, b.q, r.q);
+    q_rot(a.q, b.t, rt);
+    for (int i = 0; i < 3; ++i) r.t[i] = a.s * rt[i] + a.t[i];
+    r.s = a.s * b.s;
+    return r;
+}
+__device__ __forceinline__ Sim3d sim3_inverse(const Sim3d &a) {
+    Sim3d r;
+    r.q[0] = -a.q[0], r.q[1] = -a.q[1], r.q[2] = -a.q[2], r.q[3] = a.q[3];
+    const double m = -1. / a.s;
+    const double v[3] = {m * a.t[0], m * a.t[1], m * a.t[2]};
+    q_rot(r.q, v, r.t);
+    r.s = 1. / a.s;
+    return r;
+}
+__device__ __forceinline__ void sim3_map(const Sim3d &a, const double *X, double *Y) {
+    double r[3];
+    q_rot(a.q, X, r);
+    for (int i = 0; i < 3; ++i) Y[i] = a.s * r[i] + a.t[i];
+}
+
+// PartialPivLU of a 3x3 (row-major W) and its solve, Eigen's order of operations: the pivot of a column is the first
+// entry of largest magnitude at or below the diagonal, L has a unit diagonal, the substitutions run column by column.
+// Rows are swapped by selects on fixed indices (nothing is indexed at run time).
+__device__ __forceinline__ void lu3_solve(const double *W, const double *t, double *x) {
+    double a0[4] = {W[0], W[1], W[2], t[0]}, a1[4] = {W[3], W[4], W[5], t[1]}, a2[4] = {W[6], W[7], W[8], t[2]};
+    auto swp = [](double *p, double *q) {
+        for (int c = 0; c < 4; ++c) {
+            const double v = p[c];
+            p[c] = q[c], q[c] = v;
+        }
+    };
+    const bool s1 = fabs(a1[0]) > fabs(a0[0]);
+    const bool s2 = fabs(a2[0]) > (s1 ? fabs(a1[0]) : fabs(a0[0]));
+    if (s2) swp(a0, a2);
+    else if (s1) swp(a0, a1);
+    const double l10 = a1[0] / a0[0], l20 = a2[0] / a0[0];
+    for (int c = 1; c < 4; ++c) a1[c] -= l10 * a0[c], a2[c] -= l20 * a0[c];
+    if (fabs(a2[1]) > fabs(a1[1])) swp(a1, a2);
+    const double l21 = a2[1] / a1[1];
+    a2[2] -= l21 * a1[2], a2[3] -= l21 * a1[3];
+    x[2] = a2[3] / a2[2];
+    a0[3] -= x[2] * a0[2], a1[3] -= x[2] * a1[2];
+    x[1] = a1[3] / a1[1];
+    a0[3] -= x[1] * a0[1];
+    x[0] = a0[3] / a0[0];
+}
+
+// Sim3::log (Thirdparty/g2o/g2o/types/sim3.h:148-230), branch for branch: eps = 1e-5 on sigma and on d = (tr R - 1) / 2,
+// the small-angle omega = deltaR(R) / 2, W = A Omega + (B Omega) Omega + C I and upsilon = W.lu().solve(t).
+__device__ __forceinline__ void sim3_log(const Sim3d &S, double *res) {
+    const double sigma = log(S.s);
+    double R[9], O[9], BO[9], O2[9], W[9], omega[3];
+    q_to_mat(S.q, R);
+    const double d = 0.5 * (R[0] + R[4] + R[8] - 1);
+    const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+    const double eps = 0.00001;
+    double A, B, C;
+    if (fabs(sigma) < eps) {
+        C = 1;
+        if (d > 1 - eps) {
+            for (int k = 0; k < 3; ++k) omega[k] = 0.5 * dR[k];
+            A = 1. / 2., B = 1. / 6.;
+        } else {
+            const double theta = acos(d), theta2 = theta * theta;
+            const double f = theta / (2 * sqrt(1 - d * d));
+            for (int k = 0; k < 3; ++k) omega[k] = f * dR[k];
+            double sn, cs;
+            sincos_d(theta, sn, cs);
+            A = (1 - cs) / theta2;
+            B = (theta - sn) / (theta2 * theta);
+        }
+    } else {
+        C = (S.s - 1) / sigma;
+        if (d > 1 - eps) {
+            const double sigma2 = sigma * sigma;
+            for (int k = 0; k < 3; ++k) omega[k] = 0.5 * dR[k];
+            A = ((sigma - 1) * S.s + 1) / sigma2;
+            B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
+        } else {
+            const double theta = acos(d);
+            const double f = theta / (2 * sqrt(1 - d * d));
+            for (int k = 0; k < 3; ++k) omega[k] = f * dR[k];
+            const double theta2 = theta * theta;
+            double sn, cs;
+            sincos_d(theta, sn, cs);
+            const double a = S.s * sn, b = S.s * cs;
+            const double c = theta2 + sigma * sigma;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
+        }
+    }
+    hat3(omega, O);
+    for (int k = 0; k < 9; ++k) BO[k] = B * O[k];
+    mm3(BO, O, O2);
+    for (int k = 0; k < 9; ++k) W[k] = A * O[k] + O2[k] + ((k % 4 == 0) ? C : 0.0);
+    lu3_solve(W, S.t, res + 3);
+    res[0] = omega[0], res[1] = omega[1], res[2] = omega[2];
+    res[6] = sigma;
+}
 }  // namespace omv_g2o

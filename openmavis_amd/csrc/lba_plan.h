@@ -297,48 +297,29 @@ inline omv_status plan_edge_order(const omv_lba_problem &p, int rank, int world,
     return OMV_OK;
 }
 
-// Step 2: the inertial pairs checked and added to the adjacency, the elimination order (every rank of a sharded solve
-// plans from the same full pattern), its symbolic LDL^T, the stored blocks and the level schedule.
-inline omv_status plan_pattern(const omv_lba_problem &p, bool lds_ok, bool whole_map, int max_cuts, LbaPlan &P,
-                               PlanWork &W) {
-    const int nb = P.nb, n_opt = p.n_opt, K = p.n_kf, S = P.shared_blk;
-    std::vector<uint8_t> &adj = W.adj, &pat = W.pat;
-    for (int i = 0; i < p.n_imu; ++i) {
-        const int a = p.imu_kf1[i], b = p.imu_kf2[i];
-        if (a < 0 || a >= K || b < 0 || b >= K || a == b) return OMV_ERR_ARG;
-        if (a < n_opt && b < n_opt) adj[(size_t)a * nb + b] = adj[(size_t)b * nb + a] = 1;
-        if (S < 0) continue;
-        // the shared pair: vertices G and A of every EdgeInertial, which exists between two bImu keyframes only
-        // (Optimizer.cc:469, :485-486)
-        if (!p.kf_imu[a] || !p.kf_imu[b]) return OMV_ERR_ARG;
-        for (int k : {a, b})
-            if (k < n_opt) adj[(size_t)k * nb + S] = adj[(size_t)S * nb + k] = 1;
-    }
-    const size_t vec_bytes = 2 * (size_t)P.n_red * sizeof(double);
-    const int lds_slots = lds_ok && kLdltLds > vec_bytes ? (int)((kLdltLds - vec_bytes) / (256 * sizeof(double))) : 0;
-    // The whole-map entry (plan_fiba), either bias form.  A whole map's blocks rarely fit the LDS: when the
-    // keyframe order itself is past the budget the hybrid storage holds whichever order wins, so the budget no longer
-    // picks among them (fewest levels, then fewest blocks).  plan_lba keeps its budget.
-    auto whole_map_budget = [&](int n, const std::vector<uint8_t> &a, int budget) {
-        if (!whole_map) return budget;
-        int ns0 = 0;
-        std::vector<int> id(n), lev;
-        std::iota(id.begin(), id.end(), 0);
-        symbolic_ldlt(n, a, id, pat, lev, ns0);
-        return ns0 > budget ? std::numeric_limits<int>::max() : budget;
-    };
-    if (S < 0) {
-        P.perm = plan_order(nb, adj, whole_map_budget(nb, adj, std::max(lds_slots, 1)), max_cuts);
-    } else {
-        // The pair's block borders every keyframe with an inertial edge: counted into a dissection it would sit in every
-        // separator and plan_order would reject every cut.  The keyframes are dissected without it (its row of at most
-        // nb blocks taken off the LDS budget) and it is eliminated last.
-        std::vector<uint8_t> sub((size_t)n_opt * n_opt);
-        for (int i = 0; i < n_opt; ++i)
-            for (int j = 0; j < n_opt; ++j) sub[(size_t)i * n_opt + j] = adj[(size_t)i * nb + j];
-        P.perm = plan_order(n_opt, sub, whole_map_budget(n_opt, sub, std::max(lds_slots - nb, 1)), max_cuts);
-        P.perm.push_back(S);
-    }
+// plan_order's block budget for a whole map (plan_fiba, either bias form, and the pose graph).  A whole map's blocks
+// rarely fit the LDS: when the keyframe order itself is past the budget the hybrid storage holds whichever order wins,
+// so the budget no longer picks among them (fewest levels, then fewest blocks).
+inline int whole_map_slot_budget(int n, const std::vector<uint8_t> &adj, int budget) {
+    int ns0 = 0;
+    std::vector<uint8_t> pat;
+    std::vector<int> id(n), lev;
+    std::iota(id.begin(), id.end(), 0);
+    symbolic_ldlt(n, adj, id, pat, lev, ns0);
+    return ns0 > budget ? std::numeric_limits<int>::max() : budget;
+}
+// The blocks the solver's LDS holds beside its two vectors of n_red rows (0 without the LDS attribute).
+inline int lds_slot_budget(bool lds_ok, int n_red) {
+    const size_t vec_bytes = 2 * (size_t)n_red * sizeof(double);
+    return lds_ok && kLdltLds > vec_bytes ? (int)((kLdltLds - vec_bytes) / (256 * sizeof(double))) : 0;
+}
+
+// The stored blocks and the level schedule of the block LDL^T of `nb` blocks with adjacency `adj` in the elimination
+// order P.perm (position -> block): the filled pattern, the slots column-major in positions, each level's columns, its
+// trailing updates grouped by target block, the inverse records and the row / column structures of the substitutions.
+// What the solver (omv_ldlt.h) reads; plan_pattern and the pose graph's plan (essgraph_plan.h) both end here.
+inline void plan_schedule(int nb, const std::vector<uint8_t> &adj, LbaPlan &P, PlanWork &W) {
+    std::vector<uint8_t> &pat = W.pat;
     const std::vector<int> &perm = P.perm;
     W.ipos.resize(nb);
     for (int q = 0; q < nb; ++q) W.ipos[perm[q]] = q;
@@ -409,6 +390,42 @@ inline omv_status plan_pattern(const omv_lba_problem &p, bool lds_ok, bool whole
             if (pat[(size_t)i * nb + k]) P.cs.push_back(Int2{slot[(size_t)i * nb + k], i});
         P.cs_start[k + 1] = (int)P.cs.size();
     }
+}
+
+// Step 2: the inertial pairs checked and added to the adjacency, the elimination order (every rank of a sharded solve
+// plans from the same full pattern), its symbolic LDL^T, the stored blocks and the level schedule.
+inline omv_status plan_pattern(const omv_lba_problem &p, bool lds_ok, bool whole_map, int max_cuts, LbaPlan &P,
+                               PlanWork &W) {
+    const int nb = P.nb, n_opt = p.n_opt, K = p.n_kf, S = P.shared_blk;
+    std::vector<uint8_t> &adj = W.adj;
+    for (int i = 0; i < p.n_imu; ++i) {
+        const int a = p.imu_kf1[i], b = p.imu_kf2[i];
+        if (a < 0 || a >= K || b < 0 || b >= K || a == b) return OMV_ERR_ARG;
+        if (a < n_opt && b < n_opt) adj[(size_t)a * nb + b] = adj[(size_t)b * nb + a] = 1;
+        if (S < 0) continue;
+        // the shared pair: vertices G and A of every EdgeInertial, which exists between two bImu keyframes only
+        // (Optimizer.cc:469, :485-486)
+        if (!p.kf_imu[a] || !p.kf_imu[b]) return OMV_ERR_ARG;
+        for (int k : {a, b})
+            if (k < n_opt) adj[(size_t)k * nb + S] = adj[(size_t)S * nb + k] = 1;
+    }
+    const int lds_slots = lds_slot_budget(lds_ok, P.n_red);
+    auto whole_map_budget = [&](int n, const std::vector<uint8_t> &a, int budget) {
+        return whole_map ? whole_map_slot_budget(n, a, budget) : budget;   // plan_lba keeps its budget
+    };
+    if (S < 0) {
+        P.perm = plan_order(nb, adj, whole_map_budget(nb, adj, std::max(lds_slots, 1)), max_cuts);
+    } else {
+        // The pair's block borders every keyframe with an inertial edge: counted into a dissection it would sit in every
+        // separator and plan_order would reject every cut.  The keyframes are dissected without it (its row of at most
+        // nb blocks taken off the LDS budget) and it is eliminated last.
+        std::vector<uint8_t> sub((size_t)n_opt * n_opt);
+        for (int i = 0; i < n_opt; ++i)
+            for (int j = 0; j < n_opt; ++j) sub[(size_t)i * n_opt + j] = adj[(size_t)i * nb + j];
+        P.perm = plan_order(n_opt, sub, whole_map_budget(n_opt, sub, std::max(lds_slots - nb, 1)), max_cuts);
+        P.perm.push_back(S);
+    }
+    plan_schedule(nb, adj, P, W);
     return OMV_OK;
 }
 

@@ -1,5 +1,6 @@
 // g2o's Levenberg-Marquardt step control (Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-185), stated
-// once for the solvers that run it: optimize_sim3_kernel (optsim3.hip) and both Local BA drivers (lba.hip);
+// once for the solvers that run it: optimize_sim3_kernel (optsim3.hip), both Local BA drivers (lba.hip) and the pose
+// graphs' device control (essgraph.hip);
 // pose_only_kernel (pose.hip) and inertial_opt_kernel (inertial.hip) follow it written out.  Only the arithmetic and
 // the decisions are here; a site keeps its loops, its build / solve / oplus / chi2 / computeScale reductions and where
 // the state lives.  One text for hipcc (both sides) and a plain C++ compiler (tests/cpp/lm_host.cpp); tests/lm_ref.py

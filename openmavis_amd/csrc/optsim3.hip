@@ -54,111 +54,8 @@ struct OptSim3Args {
     int32_t *n_in;
     OptSim3Debug *dbg;
 };
-struct Sim3d {
-    double q[4], t[3], s;
-};
+// Sim3d, sim3_exp, sim3_mul, sim3_inverse and sim3_map: g2o_types.h (the pose graph shares them).
 
-// Eigen::Quaterniond(Matrix3d): q_from_mat's arithmetic with the three cases of its largest-diagonal branch spelled
-// out, so that no array is indexed at run time (q_from_mat's q[i] / m[4 * i] put q and m into scratch)
-template <int I>
-__device__ __forceinline__ void os3_q_from_mat_diag(const double *m, double *q) {
-    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
-    double t = sqrt(m[4 * I] - m[4 * J] - m[4 * K] + 1.0);
-    q[I] = 0.5 * t;
-    t = 0.5 / t;
-    q[3] = (m[3 * K + J] - m[3 * J + K]) * t;
-    q[J] = (m[3 * J + I] + m[3 * I + J]) * t;
-    q[K] = (m[3 * K + I] + m[3 * I + K]) * t;
-}
-__device__ __forceinline__ void os3_q_from_mat(const double *m, double *q) {
-    double t = m[0] + m[4] + m[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[7] - m[5]) * t, q[1] = (m[2] - m[6]) * t, q[2] = (m[3] - m[1]) * t;
-    } else if (m[4] > m[0]) {
-        if (m[8] > m[4]) os3_q_from_mat_diag<2>(m, q);
-        else os3_q_from_mat_diag<1>(m, q);
-    } else {
-        if (m[8] > m[0]) os3_q_from_mat_diag<2>(m, q);
-        else os3_q_from_mat_diag<0>(m, q);
-    }
-}
-
-// Sim3(const Vector7d &update) (Thirdparty/g2o/g2o/types/sim3.h:70-142)
-__device__ __forceinline__ Sim3d sim3_exp(const double *u) {
-    const double sigma = u[6];
-    const double theta = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    double O[9], O2[9], R[9], W[9];
-    hat3(u, O);
-    Sim3d r;
-    r.s = exp(sigma);
-    mm3(O, O, O2);
-    const double eps = 0.00001;
-    double A, B, C;
-    if (fabs(sigma) < eps) {
-        C = 1;
-        if (theta < eps) {
-            A = 1. / 2., B = 1. / 6.;
-            for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + O[k] + O2[k];
-        } else {
-            double sn, cs;
-            sincos_d(theta, sn, cs);
-            const double theta2 = theta * theta;
-            A = (1 - cs) / theta2;
-            B = (theta - sn) / (theta2 * theta);
-            const double a = sn / theta, b = (1 - cs) / (theta * theta);
-            for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + a * O[k] + b * O2[k];
-        }
-    } else {
-        C = (r.s - 1) / sigma;
-        if (theta < eps) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1) * r.s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * r.s) / (sigma2 * sigma);
-            for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + O[k] + O2[k];
-        } else {
-            double sn, cs;
-            sincos_d(theta, sn, cs);
-            const double ra = sn / theta, rb = (1 - cs) / (theta * theta);
-            for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + ra * O[k] + rb * O2[k];
-            const double a = r.s * sn, b = r.s * cs;
-            const double theta2 = theta * theta, sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
-        }
-    }
-    os3_q_from_mat(R, r.q);
-    for (int k = 0; k < 9; ++k) W[k] = A * O[k] + B * O2[k] + ((k % 4 == 0) ? C : 0.0);
-    mv3(W, u + 3, r.t);
-    return r;
-}
-// Sim3::operator* (r is not renormalised), inverse and map
-__device__ __forceinline__ Sim3d sim3_mul(const Sim3d &a, const Sim3d &b) {
-    Sim3d r;
-    double rt[3];
-    q_mul(a.q, b.q, r.q);
-    q_rot(a.q, b.t, rt);
-    for (int i = 0; i < 3; ++i) r.t[i] = a.s * rt[i] + a.t[i];
-    r.s = a.s * b.s;
-    return r;
-}
-__device__ __forceinline__ Sim3d sim3_inverse(const Sim3d &a) {
-    Sim3d r;
-    r.q[0] = -a.q[0], r.q[1] = -a.q[1], r.q[2] = -a.q[2], r.q[3] = a.q[3];
-    const double m = -1. / a.s;
-    const double v[3] = {m * a.t[0], m * a.t[1], m * a.t[2]};
-    q_rot(r.q, v, r.t);
-    r.s = 1. / a.s;
-    return r;
-}
-__device__ __forceinline__ void sim3_map(const Sim3d &a, const double *X, double *Y) {
-    double r[3];
-    q_rot(a.q, X, r);
-    for (int i = 0; i < 3; ++i) Y[i] = a.s * r[i] + a.t[i];
-}
 __device__ __forceinline__ void os3_project(int model, const float *k, const double *X, double &u, double &v) {
     if (model == OMV_CAM_PINHOLE) pinhole_project(k, X, u, v);
     else kb8_project(k, X, u, v);

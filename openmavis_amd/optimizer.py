@@ -631,3 +631,144 @@ def OptimizeSim3(jobs, vpMatches1=None, optimizer=None):
         m[idx[status[j] >= OPTSIM3_REMOVED_1]] = False
         out.append((int(n_in[j]), dict(q=q[j].copy(), t=t[j].copy(), s=float(s[j])), m))
     return out
+
+
+class EssentialGraph:
+    """The pose graphs of loop closing and map merging (Optimizer::OptimizeEssentialGraph, src/Optimizer.cc:1826-2119, its
+    merge overload :2121-2458, and OptimizeEssentialGraph4DoF :6171-6480) on the device (omv_essgraph,
+    openmavis_amd/csrc/essgraph.hip): g2o's Levenberg-Marquardt with the edges' numeric Jacobians on the block LDL^T of
+    the bundle-adjustment solver.  The flattened graph is a problem dict (openmavis_amd.synth_essgraph):
+
+        g = EssentialGraph("sim3", max_vertices=2000, max_edges=20000)        # or "4dof"
+        g.set_problem(prob)            # vertices, fixed, S_a, S_b, edge_i, edge_j, edge_table, fix_scale [, Rcb, tcb]
+        res = g.optimize(iterations=20, max_trials=10)
+        poses, points = g.recover("loop", prob["points"], prob["point_ref"])
+
+    `res`: err / err_end, iterations, trials, solver_failed, lambda_ and the final vertices.  The state stays on the
+    device between calls.  One rank; no CPU fallback."""
+
+    KINDS = {"sim3": _lib.ESSGRAPH_SIM3, "4dof": _lib.ESSGRAPH_4DOF}
+    MODES = {"loop": _lib.ESSGRAPH_RECOVER_LOOP, "merge": _lib.ESSGRAPH_RECOVER_MERGE, "4dof": _lib.ESSGRAPH_RECOVER_4DOF}
+
+    def __init__(self, kind="sim3", max_vertices=2000, max_edges=20000):
+        lib = _lib.load()
+        h = ctypes.c_void_p()
+        self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind)
+        _lib.check(lib.omv_essgraph_create(self.kind, int(max_vertices), int(max_edges), ctypes.byref(h)),
+                   "omv_essgraph_create")
+        self._lib, self._h = lib, h
+        self._s = self._keep = None
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.omv_essgraph_destroy(self._h)
+            self._h = None
+
+    @property
+    def _sim3(self):
+        return self.kind == _lib.ESSGRAPH_SIM3
+
+    def set_problem(self, prob):
+        s, keep = essgraph_struct(prob)
+        _lib.check(self._lib.omv_essgraph_set_problem(self._h, ctypes.byref(s)), "omv_essgraph_set_problem")
+        self._s, self._keep = s, keep
+        return self
+
+    def _need(self, what):
+        if self._s is None:
+            raise _lib.OmvError(f"EssentialGraph.{what}: no problem set")
+
+    def optimize(self, iterations=20, max_trials=10):
+        self._need("optimize")
+        v = np.zeros((self._s.n_vertices, 8 if self._sim3 else 24))
+        r = _lib.EssGraphResult()
+        r.vertices = _lib.ptr(v)
+        _lib.check(self._lib.omv_essgraph_optimize(self._h, int(iterations), int(max_trials), ctypes.byref(r)),
+                   "omv_essgraph_optimize")
+        return dict(err=r.err, err_end=r.err_end, iterations=r.iterations, trials=r.trials,
+                    solver_failed=r.solver_failed, lambda_=r.lambda_, vertices=v)
+
+    def evaluate(self):
+        """Per edge at the device state: err, g2o's numeric jac_i / jac_j (rows x variables), the composed measurement
+        and chi2."""
+        self._need("evaluate")
+        E = self._s.n_edges
+        D, V, M = (7, 7, 8) if self._sim3 else (6, 4, 12)
+        out = dict(err=np.zeros((E, D)), jac_i=np.zeros((E, D, V)), jac_j=np.zeros((E, D, V)), meas=np.zeros((E, M)),
+                   chi2=np.zeros(E))
+        _lib.check(self._lib.omv_essgraph_evaluate(self._h, *[_lib.ptr(v) for v in out.values()]), "omv_essgraph_evaluate")
+        return out
+
+    def reset(self):
+        """The state uploaded by set_problem again (device copy)."""
+        self._need("reset")
+        _lib.check(self._lib.omv_essgraph_reset(self._h), "omv_essgraph_reset")
+        return self
+
+    def debug_solve(self, lambda_):
+        """One linear solve at the device state (omv_essgraph_debug_solve): the n x n system, rhs, x, the failure flag
+        and the plan (storage mode, stored blocks, blocks in LDS, levels, columns per level)."""
+        self._need("debug_solve")
+        nb, nl = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(self._lib.omv_essgraph_blocks(self._h, ctypes.byref(nb), ctypes.byref(nl)), "omv_essgraph_blocks")
+        n = 16 * nb.value
+        S, rhs, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
+        plan = np.full(4 + nl.value, -1, np.int32)
+        fail = ctypes.c_int(-1)
+        _lib.check(self._lib.omv_essgraph_debug_solve(self._h, ctypes.c_double(lambda_), _lib.ptr(S), _lib.ptr(rhs),
+                                                      _lib.ptr(x), ctypes.byref(fail), _lib.ptr(plan), len(plan)),
+                   "omv_essgraph_debug_solve")
+        n_lev = int(plan[3])
+        return dict(S=S, rhs=rhs, x=x, fail=fail.value, mode=int(plan[0]), n_slots=int(plan[1]), n_lds=int(plan[2]),
+                    n_lev=n_lev, cols=[int(v) for v in plan[4:4 + n_lev]])
+
+    def recover(self, mode, points=None, point_ref=None):
+        """The epilogue: the SE3f of every keyframe's SetPose as [n][7] (unit quaternion x y z w, translation) and the
+        corrected map points (a copy; point_ref -1 leaves a point as it was)."""
+        self._need("recover")
+        m = self.MODES[mode] if isinstance(mode, str) else int(mode)
+        poses = np.zeros((self._s.n_vertices, 7), np.float32)
+        pts = np.ascontiguousarray(points, np.float32).copy() if points is not None else np.zeros((0, 3), np.float32)
+        ref = np.ascontiguousarray(point_ref, np.int32) if point_ref is not None else np.zeros(0, np.int32)
+        _lib.check(self._lib.omv_essgraph_recover(self._h, m, _lib.ptr(poses), len(pts), _lib.ptr(pts), _lib.ptr(ref)),
+                   "omv_essgraph_recover")
+        return poses, pts
+
+    def last_ms(self):
+        ms = ctypes.c_double(0)
+        _lib.check(self._lib.omv_essgraph_last_ms(self._h, ctypes.byref(ms)), "omv_essgraph_last_ms")
+        return ms.value
+
+
+def essgraph_struct(prob):
+    """A problem dict as omv_essgraph_problem and the arrays it points into."""
+    keep = dict(vertices=np.ascontiguousarray(prob["vertices"], np.float64),
+                fixed=np.ascontiguousarray(prob["fixed"], np.uint8),
+                S_a=np.ascontiguousarray(prob["S_a"], np.float64), S_b=np.ascontiguousarray(prob["S_b"], np.float64),
+                edge_i=np.ascontiguousarray(prob["edge_i"], np.int32), edge_j=np.ascontiguousarray(prob["edge_j"], np.int32),
+                edge_table=np.ascontiguousarray(prob["edge_table"], np.int32))
+    for k in ("Rcb", "tcb"):
+        keep[k] = np.ascontiguousarray(prob[k], np.float64) if prob.get(k) is not None else None
+    s = _lib.EssGraphProblem()
+    s.n_vertices, s.n_edges, s.fix_scale = len(keep["vertices"]), len(keep["edge_i"]), int(prob.get("fix_scale", 0))
+    for k, v in keep.items():
+        setattr(s, k, _lib.ptr(v))
+    return s, keep
+
+
+def _optimize_essential_graph(kind, mode, prob, iterations, max_trials, handle):
+    g = handle or EssentialGraph(kind, max_vertices=len(prob["vertices"]), max_edges=max(len(prob["edge_i"]), 1))
+    res = g.set_problem(prob).optimize(iterations, max_trials)
+    poses, points = g.recover(mode, prob.get("points"), prob.get("point_ref"))
+    return dict(res, poses=poses, points=points)
+
+
+def OptimizeEssentialGraph(prob, iterations=20, max_trials=10, merge=False, handle=None):
+    """Optimizer::OptimizeEssentialGraph on a flat problem dict: optimize(20) and the epilogue (SetPose's SE3f per
+    keyframe, the corrected map points).  merge: the map-merging overload's pose recovery (t / s in double)."""
+    return _optimize_essential_graph("sim3", "merge" if merge else "loop", prob, iterations, max_trials, handle)
+
+
+def OptimizeEssentialGraph4DoF(prob, iterations=20, max_trials=10, handle=None):
+    """Optimizer::OptimizeEssentialGraph4DoF on a flat problem dict (vertices [Rcw | tcw | Rwb | twb], Rcb, tcb)."""
+    return _optimize_essential_graph("4dof", "4dof", prob, iterations, max_trials, handle)
