@@ -33,6 +33,7 @@
 #include "omv_camera.h"
 #include "omv_device.h"
 #include "omv_host.h"
+#include "omv_topk.h"
 
 namespace {
 
@@ -246,10 +247,11 @@ struct TopSeq {
     }
 };
 
-// The same list for the lanes that share one window of a camera staged in LDS: 32-bit keys dist << 16 | p, p the
-// entry's position in the camera's cell-sorted keypoints.  A window walks its columns in ascending order and a
-// column's cells are one ascending run of p, so p ascends in window order: keys are unique and sort by (distance,
-// window order), the strict `<` scans' tie rule, whichever lane inserts them and in whatever order.
+// The same list for the windows of a camera staged in LDS, one lane's or the lanes' that share one: 32-bit keys
+// dist << 16 | p, p the entry's position in the camera's cell-sorted keypoints.  A window walks its columns in
+// ascending order and a column's cells are one ascending run of p, so p ascends in window order: keys are unique and
+// sort by (distance, window order), the strict `<` scans' tie rule, whichever lane inserts them and in whatever order.
+// Unique keys in full 32-bit order are what omv::topk_insert asks for: one v_med3_u32 per slot.
 struct TopPos {
     uint32_t key[kTop];
     int count;
@@ -259,10 +261,7 @@ struct TopPos {
         count = 0;
     }
     __device__ __forceinline__ void insert(int p, int dist) {
-        const uint32_t k = ((uint32_t)dist << 16) | (uint32_t)p;
-#pragma unroll
-        for (int q = kTop - 1; q > 0; --q) key[q] = k < key[q - 1] ? key[q - 1] : min(k, key[q]);
-        key[0] = min(k, key[0]);
+        omv::topk_insert<kTop>(key, ((uint32_t)dist << 16) | (uint32_t)p);
     }
     // The kTop smallest keys of a G-lane group (G a power of two, the same for the whole wavefront) into every lane of
     // it, counts summed: log2 G rounds in which a lane and its partner lane ^ s exchange their sorted lists.
@@ -504,8 +503,8 @@ __global__ void __launch_bounds__(256, 4) cand_kernel(FrameArgs f, MpArgs m, int
 
 // ---------------------------------------------------------------------------------------------
 // The same candidates with the camera's keypoints staged in LDS.  One 512-thread workgroup per (frame, camera,
-// chunk of 8 * pw map points): the camera's grid-ordered keypoints (CSR position p -> x, y, octave | index |
-// blocked bit, 32-B descriptor) and its cell starts are copied into LDS once, then every in-view slot of the
+// chunk of 8 * pw map points): the camera's grid-ordered keypoints (CSR position p -> x, y, octave | index,
+// 32-B descriptor) and its cell starts are copied into LDS once, then every in-view slot of the
 // chunk walks its window there.  The global-memory version pays one dependent L2/HBM gather per window entry
 // (cell index -> keypoint and descriptor) per (map point, camera); here a window step is two LDS reads, the
 // descriptor only for entries that pass the level / radius / blocked tests, and the cell-index hop is gone
@@ -515,7 +514,14 @@ __global__ void __launch_bounds__(256, 4) cand_kernel(FrameArgs f, MpArgs m, int
 // entries (OMV_CAND_SPLIT) is dealt to several lanes (TopPos, scan_window_lds_coop).  -DOMV_STAGE_PROFILE prints the
 // phases' times of one frame's workgroups.
 constexpr int kStageThreads = 512;
-constexpr uint32_t kStageBlocked = 1u << 31;
+// A staged entry's meta word: keypoint index | octave << 16 (7 bits), nothing above.  A window of predicted level
+// lvl takes the octaves lvl - 1 and lvl: meta - ((lvl - 1) << 16) < 2 << 16 as unsigned, whatever the index in the low
+// half.  At lvl = 0 the bound wraps to 0xffff0000 and the difference is meta + (1 << 16): octave 0 alone passes.  An
+// initially occupied keypoint is staged with kStageOctBlocked in the octave field and passes at no lvl < 0x7f
+// (windows have lvl < nlevels <= 16); no blocked entry is ever inserted, so its octave is never read back.
+constexpr uint32_t kStageOctBlocked = 0x7f;
+constexpr uint32_t kStageLevelSpan = 2u << 16;
+__device__ __forceinline__ uint32_t stage_level_lo(int lvl) { return (uint32_t)(lvl - 1) << 16; }
 constexpr size_t kStageLdsMax = 80 * 1024;   // two workgroups per CU
 constexpr int kScanGroup = 4;                 // window entries read per LDS round trip
 constexpr int kStageUnroll = 3;               // staged entries per thread per pass (1,536 per pass)
@@ -530,15 +536,14 @@ __host__ __device__ inline size_t stage_lds_bytes(int kp_cap, int pw) {
 }
 
 // One run of a staged camera's entries, pb, pb + (1 << sh), ... (cnt of them), against a window: first the cheap
-// tests (level, radius, blocked) on every entry, kScanGroup entries per LDS round trip, the passing ones marked in a
-// 32-bit mask; then the descriptor read, the distance and ins(p, meta, dist) for the marked entries alone, in
-// ascending order.  A wavefront pays the second, expensive part as often as its lane with the most passing entries
-// in the pass, not once per entry that passes on any lane.  Reads past the run repeat its first entry and are
-// masked.  Returns how many entries passed.
-template <class Ins>
-__device__ __forceinline__ int scan_run_lds(int pb, int sh, int cnt, float x, float y, float r, bool checkLevels,
-                                            int minL, int maxL, const uint64_t dmp[4], const float2 *sxy,
-                                            const uint32_t *smeta, const uint4 *sdesc, Ins ins) {
+// tests (level, radius; a blocked entry fails the level test) on every entry, kScanGroup entries per LDS round trip,
+// the passing ones marked in a 32-bit mask; then the descriptor read, the distance and t.insert(p, dist) for the marked
+// entries alone.  A wavefront pays the second, expensive part as often as its lane with the most passing entries in
+// the pass, not once per entry that passes on any lane.  Reads past the run repeat its first entry and are masked.
+// lo = stage_level_lo(level).  Returns how many entries passed.
+__device__ __forceinline__ int scan_run_lds(int pb, int sh, int cnt, float x, float y, float r, uint32_t lo,
+                                            const uint64_t dmp[4], const float2 *sxy, const uint32_t *smeta,
+                                            const uint4 *sdesc, TopPos &t) {
     int found = 0;
     for (int k0 = 0; k0 < cnt; k0 += 32) {
         const int nk = min(32, cnt - k0);
@@ -553,10 +558,10 @@ __device__ __forceinline__ int scan_run_lds(int pb, int sh, int cnt, float x, fl
             }
 #pragma unroll
             for (int u = 0; u < kScanGroup; ++u) {
-                const int oct = (int)((meta[u] >> 16) & 0x7f);
-                bool ok = u0 + u < nk;   // then omv::kp_in_window written out
-                if (checkLevels) ok = ok && oct >= minL && !(maxL >= 0 && oct > maxL);
-                ok = ok && fabsf(k[u].x - x) < r && fabsf(k[u].y - y) < r && !(meta[u] & kStageBlocked);
+                // in the run, then omv::kp_in_window written out with the level test as stage_level_lo has it.  `&`, not
+                // `&&`: as branches the tests serialize the group's LDS reads behind one another
+                const bool ok = (u0 + u < nk) & (meta[u] - lo < kStageLevelSpan) & (fabsf(k[u].x - x) < r) &
+                                (fabsf(k[u].y - y) < r);
                 mask |= (uint32_t)ok << (u0 + u);
             }
         }
@@ -564,53 +569,45 @@ __device__ __forceinline__ int scan_run_lds(int pb, int sh, int cnt, float x, fl
         while (mask) {
             const int p = pb + ((k0 + __ffs((int)mask) - 1) << sh);
             mask &= mask - 1;
-            const uint32_t meta = smeta[p];
             const uint4 a = sdesc[2 * p], b = sdesc[2 * p + 1];
             const uint64_t d[4] = {(uint64_t)a.x | ((uint64_t)a.y << 32), (uint64_t)a.z | ((uint64_t)a.w << 32),
                                    (uint64_t)b.x | ((uint64_t)b.y << 32), (uint64_t)b.z | ((uint64_t)b.w << 32)};
-            ins(p, meta, omv::hamming256(dmp, d));
+            t.insert(p, omv::hamming256(dmp, d));
         }
     }
     return found;
 }
 
-__device__ __forceinline__ void scan_window_lds(const FrameArgs &f, float x, float y, float r, int minL, int maxL,
+// One lane's window of GetFeaturesInArea(x, y, r, level - 1, level) in the staged camera, in the reference's order.
+__device__ __forceinline__ void scan_window_lds(const omv::GridRange &w, float x, float y, float r, uint32_t lo,
                                                 const uint64_t dmp[4], const int *scs, const float2 *sxy,
-                                                const uint32_t *smeta, const uint4 *sdesc, TopSeq &t) {
-    t.reset();
-    omv::GridRange w;
-    OMV_GRID_WINDOW_OR(x, y, r, f.min_x, f.min_y, f.invW, f.invH, w, return)
-    const bool checkLevels = (minL > 0) || (maxL >= 0);
+                                                const uint32_t *smeta, const uint4 *sdesc, TopPos &t) {
     for (int ix = w.x0; ix <= w.x1; ++ix) {
         const int b = scs[ix * kGridRows + w.y0], e = scs[ix * kGridRows + w.y1 + 1];
-        t.count += scan_run_lds(b, 0, e - b, x, y, r, checkLevels, minL, maxL, dmp, sxy, smeta, sdesc,
-                                [&](int, uint32_t meta, int dist) {
-                                    t.insert((int)(meta & 0xffff), dist, (int)((meta >> 16) & 0x7f));
-                                });
+        t.count += scan_run_lds(b, 0, e - b, x, y, r, lo, dmp, sxy, smeta, sdesc, t);
     }
 }
 
 // scan_window_lds over G = 1 << sh cooperating lanes (g = the lane's rank in its group): lane g walks window
 // positions g, g + G, ... in the reference's order (columns ascending, each column's CSR run) with the same tests;
 // TopPos keys make the group's merged list the one lane's list.
-__device__ __forceinline__ void scan_window_lds_coop(const omv::GridRange &w, float x, float y, float r, int minL, int maxL,
+__device__ __forceinline__ void scan_window_lds_coop(const omv::GridRange &w, float x, float y, float r, uint32_t lo,
                                                      const uint64_t dmp[4], const int *scs, const float2 *sxy,
                                                      const uint32_t *smeta, const uint4 *sdesc, TopPos &t, int g, int sh) {
-    const bool checkLevels = (minL > 0) || (maxL >= 0);
     int pos = g, acc = 0;   // this lane's next window position; window positions before the current column
     for (int ix = w.x0; ix <= w.x1; ++ix) {
         const int b = scs[ix * kGridRows + w.y0], end = acc + scs[ix * kGridRows + w.y1 + 1] - b;
         if (pos < end) {
             const int cnt = (end - pos + (1 << sh) - 1) >> sh;   // this lane's entries of the column
-            t.count += scan_run_lds(b + pos - acc, sh, cnt, x, y, r, checkLevels, minL, maxL, dmp, sxy, smeta, sdesc,
-                                    [&](int p, uint32_t, int dist) { t.insert(p, dist); });
+            t.count += scan_run_lds(b + pos - acc, sh, cnt, x, y, r, lo, dmp, sxy, smeta, sdesc, t);
             pos += cnt << sh;
         }
         acc = end;
     }
 }
 
-// The merged list of a split window as a record: the keypoint index and octave of entry p come from its meta word.
+// A staged window's list (one lane's, or the merged list of a split window) as a record: the keypoint index and
+// octave of entry p come from its meta word.
 __device__ __forceinline__ void store_record_pos(Rec *dst, const TopPos &t, const uint32_t *smeta) {
     uint4 *o4 = reinterpret_cast<uint4 *>(dst);
     uint32_t w[kTop];
@@ -724,7 +721,7 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
             const int p = s0 + u * kStageThreads + tid;
             if (idx[u] < 0) continue;
             sxy[p] = make_float2(x[u], y[u]);
-            smeta[p] = (uint32_t)idx[u] | ((uint32_t)(oct[u] & 0x7f) << 16) | (bl[u] ? kStageBlocked : 0u);
+            smeta[p] = (uint32_t)idx[u] | ((bl[u] ? kStageOctBlocked : (uint32_t)(oct[u] & 0x7f)) << 16);
             sdesc[2 * p] = da[u], sdesc[2 * p + 1] = db[u];
         }
     }
@@ -801,17 +798,16 @@ __global__ void __launch_bounds__(kStageThreads) cand_stage_kernel(FrameArgs f, 
         omv::load_desc(m.desc + fm * 32, dmp);
         const float r = window_radius(f, m, bc, cam, th, th != 1.0f);
         const float x = m.proj_x[bc], y = m.proj_y[bc];
-        const int lvl = m.level[bc];
+        const uint32_t lo = stage_level_lo(m.level[bc]);
+        TopPos t;
+        t.reset();
+        omv::GridRange w;
+        const bool on_grid = omv::grid_window(x, y, r, f.min_x, f.min_y, f.invW, f.invH, w);
         if (cls == 0) {
-            TopSeq t;
-            scan_window_lds(f, x, y, r, lvl - 1, lvl, dmp, scs, sxy, smeta, sdesc, t);
-            store_record(&recs[bc], t);
+            if (on_grid) scan_window_lds(w, x, y, r, lo, dmp, scs, sxy, smeta, sdesc, t);
+            store_record_pos(&recs[bc], t, smeta);
         } else {
-            TopPos t;
-            t.reset();
-            omv::GridRange w;
-            if (omv::grid_window(x, y, r, f.min_x, f.min_y, f.invW, f.invH, w))
-                scan_window_lds_coop(w, x, y, r, lvl - 1, lvl, dmp, scs, sxy, smeta, sdesc, t, lane & (G - 1), cls);
+            if (on_grid) scan_window_lds_coop(w, x, y, r, lo, dmp, scs, sxy, smeta, sdesc, t, lane & (G - 1), cls);
             t.merge(G);
             if ((lane & (G - 1)) == 0) store_record_pos(&recs[bc], t, smeta);
         }
