@@ -21,15 +21,13 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/omv.h"
 #include "essgraph_plan.h"
 #include "g2o_types.h"
 #include "omv_device.h"
-#include "omv_host.h"
-#include "omv_ldlt.h"
+#include "omv_ldlt_host.h"
 #include "omv_lm.h"
 
 namespace {
@@ -512,7 +510,7 @@ struct omv_essgraph {
     EssPlan plan;
     EssGraph G{};
     EssGather A{};
-    BlockPat BP{};
+    LdltSolver ldlt{};   // the uploaded pattern (ldlt.pat) and the solver's launch on it
     double *d_init = nullptr;    // the uploaded state (reset)
     double *d_rec = nullptr, *d_chi2 = nullptr, *d_chi2_trial = nullptr, *d_H = nullptr, *d_S = nullptr, *d_b = nullptr;
     double *d_zero = nullptr, *d_x = nullptr, *d_scratch = nullptr, *d_diag = nullptr, *d_scale = nullptr;
@@ -531,7 +529,7 @@ void free_problem(omv_essgraph *h) {
     h->prob.reset();
     h->has = false;
     h->plan = EssPlan{};
-    h->G = EssGraph{}, h->A = EssGather{}, h->BP = BlockPat{};
+    h->G = EssGraph{}, h->A = EssGather{}, h->ldlt = LdltSolver{};
 }
 
 size_t state_doubles(const omv_essgraph *h) { return (size_t)h->G.n_v * (h->kind == OMV_ESSGRAPH_SIM3 ? 8 : 33); }
@@ -543,17 +541,7 @@ omv_status upload_problem(omv_essgraph *h, const omv_essgraph_problem *p) {
     const LbaPlan &L = pl.L;
     const int n_v = pl.n_v, n_e = pl.n_e, nb = L.nb, nred = L.n_red, n_slots = L.n_slots;
     const bool sim3 = h->kind == OMV_ESSGRAPH_SIM3;
-    omv::DeviceArena &mem = h->prob;
-    bool ok = true;
-    auto upn = [&](const auto *src, size_t n) {
-        using T = std::remove_const_t<std::remove_pointer_t<decltype(src)>>;
-        T *d = nullptr;
-        if (ok && (!mem.alloc(&d, n) || (n > 0 && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)))
-            ok = false, d = nullptr;
-        return d;
-    };
-    auto upv = [&](const auto &v) { return upn(v.data(), v.size()); };
-    auto buf = [&](auto **d, size_t n) { ok = ok && mem.alloc(d, n); };
+    omv::Uploader up{h->prob};
     EssGraph &G = h->G;
     G.n_v = n_v, G.n_e = n_e, G.n_opt = pl.n_opt, G.fix_scale = sim3 && p->fix_scale ? 1 : 0;
     std::vector<double> init, rwb0;
@@ -570,29 +558,26 @@ omv_status upload_problem(omv_essgraph *h, const omv_essgraph_problem *p) {
         }
         for (int q = 0; q < 9; ++q) G.Rcb[q] = p->Rcb[q];
         for (int q = 0; q < 3; ++q) G.tcb[q] = p->tcb[q];
-        G.Rwb0 = upv(rwb0);
+        G.Rwb0 = up.copy(rwb0);
     }
-    G.st[0] = upv(init), G.st[1] = upv(init), h->d_init = upv(init);
-    G.ei = upn(p->edge_i, (size_t)n_e), G.ej = upn(p->edge_j, (size_t)n_e), G.et = upn(p->edge_table, (size_t)n_e);
-    G.row_of = upv(pl.row_of), G.opt_v = upv(pl.opt_v);
-    G.Sa = upn(p->S_a, 8 * (size_t)n_v), G.Sb = upn(p->S_b, 8 * (size_t)n_v);
-    buf(&G.meas, (size_t)n_e * 12);
-    h->A = EssGather{upv(pl.cb_start), (const int4 *)upv(pl.cb), upv(pl.cv_start), (const int4 *)upv(pl.cv), upv(pl.real_row)};
-    {
-        const int *kr = upv(L.slot_kr), *kc = upv(L.slot_kc), *d = upv(L.blob);
-        if (!ok) return OMV_ERR_HIP;
-        const LbaPlan::BlobOff &o = L.off;
-        h->BP = BlockPat{nb, n_slots, L.n_lev, L.n_lds, d + o.perm, kr, kc, d + o.dslot, d + o.lev_start, d + o.lev_col,
-                         d + o.ug_start, d + o.ug_split, d + o.crit_grp, d + o.ug_task_start, (const int4 *)(d + o.ug),
-                         (const int4 *)(d + o.inv_rec), d + o.rs_start, (const int2 *)(d + o.rs), d + o.cs_start,
-                         (const int2 *)(d + o.cs), d, L.blob_ints};
-    }
+    G.st[0] = up.copy(init), G.st[1] = up.copy(init), h->d_init = up.copy(init);
+    G.ei = up.copy(p->edge_i, (size_t)n_e), G.ej = up.copy(p->edge_j, (size_t)n_e);
+    G.et = up.copy(p->edge_table, (size_t)n_e);
+    G.row_of = up.copy(pl.row_of), G.opt_v = up.copy(pl.opt_v);
+    G.Sa = up.copy(p->S_a, 8 * (size_t)n_v), G.Sb = up.copy(p->S_b, 8 * (size_t)n_v);
+    up.buffer(&G.meas, (size_t)n_e * 12);
+    h->A = EssGather{up.copy(pl.cb_start), (const int4 *)up.copy(pl.cb), up.copy(pl.cv_start), (const int4 *)up.copy(pl.cv),
+                     up.copy(pl.real_row)};
+    h->ldlt = LdltSolver::upload(L, up);
+    if (!up.ok) return OMV_ERR_HIP;
     const size_t rec = sim3 ? Kd<0>::REC : Kd<1>::REC;
-    buf(&h->d_rec, (size_t)n_e * rec), buf(&h->d_chi2, n_e), buf(&h->d_chi2_trial, n_e);
-    buf(&h->d_H, (size_t)n_slots * 256), buf(&h->d_S, (size_t)n_slots * 256), buf(&h->d_b, nred), buf(&h->d_zero, nred);
-    buf(&h->d_x, nred), buf(&h->d_scratch, L.use_lds == 1 ? 8 : L.n_reduce + 8), buf(&h->d_fail, 1), buf(&h->d_any_fail, 1);
-    buf(&h->d_diag, nb), buf(&h->d_scale, pl.n_opt), buf(&h->d_stage, caller_doubles(h));
-    if (!ok || !mem.alloc_pinned(&h->h_stage, caller_doubles(h)) || !mem.alloc_pinned(&h->h_any_fail, 1)) return OMV_ERR_HIP;
+    up.buffer(&h->d_rec, (size_t)n_e * rec), up.buffer(&h->d_chi2, n_e), up.buffer(&h->d_chi2_trial, n_e);
+    up.buffer(&h->d_H, (size_t)n_slots * 256), up.buffer(&h->d_S, (size_t)n_slots * 256), up.buffer(&h->d_b, nred);
+    up.buffer(&h->d_zero, nred), up.buffer(&h->d_x, nred), up.buffer(&h->d_scratch, LdltSolver::scratch_doubles(L));
+    up.buffer(&h->d_fail, 1), up.buffer(&h->d_any_fail, 1);
+    up.buffer(&h->d_diag, nb), up.buffer(&h->d_scale, pl.n_opt), up.buffer(&h->d_stage, caller_doubles(h));
+    if (!up.ok || !h->prob.alloc_pinned(&h->h_stage, caller_doubles(h)) || !h->prob.alloc_pinned(&h->h_any_fail, 1))
+        return OMV_ERR_HIP;
     HIP_OK(hipMemset(h->d_zero, 0, nred * sizeof(double)));
     HIP_OK(hipMemset(h->d_fail, 0, sizeof(int)));
     if (n_e > 0) {
@@ -620,23 +605,16 @@ omv_status launch_linearise(omv_essgraph *h, const LmCtl *c, int gate, double *e
     const EssGraph &G = h->G;
     if (G.n_e > 0)
         ESS_KIND(h, (lin_kernel<K><<<(G.n_e + 3) / 4, 256, 0, h->stream>>>(G, c, gate, h->d_rec, h->d_chi2, err, ji, jj)));
-    ESS_KIND(h, (ess_assemble_kernel<K><<<h->BP.n_slots, 256, 0, h->stream>>>(h->A, h->BP, h->d_rec, h->d_H, h->d_b, h->d_diag,
-                                                                              c, gate)));
+    const BlockPat &BP = h->ldlt.pat;
+    ESS_KIND(h, (ess_assemble_kernel<K><<<BP.n_slots, 256, 0, h->stream>>>(h->A, BP, h->d_rec, h->d_H, h->d_b, h->d_diag, c,
+                                                                           gate)));
     HIP_OK(hipGetLastError());
     return OMV_OK;
 }
 
 omv_status launch_solve(omv_essgraph *h, const LmCtl *c, double lambda) {
-    const LbaPlan &L = h->plan.L;
-    ess_damp_kernel<<<h->BP.n_slots, 256, 0, h->stream>>>(h->A, h->BP, h->d_H, h->d_S, lambda, c);
-    if (L.use_lds == 1)
-        ldlt_kernel<0><<<1, kLdltThreads, L.ldlt_lds, h->stream>>>(h->d_S, h->BP, h->d_b, h->d_zero, h->d_x, h->d_scratch,
-                                                                  h->d_fail, c);
-    else if (L.use_lds == 2)
-        ldlt_kernel<2><<<1, kLdltThreads, L.ldlt_lds, h->stream>>>(h->d_S, h->BP, h->d_b, h->d_zero, h->d_x, h->d_scratch,
-                                                                  h->d_fail, c);
-    else
-        ldlt_kernel<1><<<1, kLdltThreads, 0, h->stream>>>(h->d_S, h->BP, h->d_b, h->d_zero, h->d_x, h->d_scratch, h->d_fail, c);
+    ess_damp_kernel<<<h->ldlt.pat.n_slots, 256, 0, h->stream>>>(h->A, h->ldlt.pat, h->d_H, h->d_S, lambda, c);
+    h->ldlt.launch(h->stream, h->d_S, h->d_b, h->d_zero, h->d_x, h->d_scratch, h->d_fail, c);
     HIP_OK(hipGetLastError());
     return OMV_OK;
 }
@@ -647,7 +625,7 @@ omv_status launch_step(omv_essgraph *h) {
     const EssGraph &G = h->G;
     omv_status rs;
     if ((rs = launch_linearise(h, c, kGateBuild, nullptr, nullptr, nullptr)) != OMV_OK) return rs;
-    ess_begin_kernel<<<1, 256, 0, h->stream>>>(c, h->d_chi2, G.n_e, h->d_diag, h->BP.nb, 0);
+    ess_begin_kernel<<<1, 256, 0, h->stream>>>(c, h->d_chi2, G.n_e, h->d_diag, h->ldlt.pat.nb, 0);
     if ((rs = launch_solve(h, c, 0.0)) != OMV_OK) return rs;
     ESS_KIND(h, (ess_oplus_kernel<K><<<(G.n_opt + 63) / 64, 64, 0, h->stream>>>(G, c, h->d_x, h->d_b, h->d_scale)));
     if (G.n_e > 0) ESS_KIND(h, (ess_err_kernel<K><<<(G.n_e + 63) / 64, 64, 0, h->stream>>>(G, c, h->d_chi2_trial)));
@@ -670,11 +648,7 @@ omv_status omv_essgraph_create(int kind, int max_vertices, int max_edges, omv_es
     HIP_OK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     for (auto &e : h->ev) HIP_OK(hipEventCreate(&e));
     if (!h->mem.alloc_pinned(&h->h_ctl, 1) || !h->mem.alloc(&h->d_ctl, 1)) return OMV_ERR_HIP;
-    h->lds_ok = hipFuncSetAttribute((const void *)ldlt_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)omv_lba_plan::kLdltLds) == hipSuccess &&
-                hipFuncSetAttribute((const void *)ldlt_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)omv_lba_plan::kLdltLds) == hipSuccess;
-    (void)hipGetLastError();
+    h->lds_ok = LdltSolver::opt_in_lds();
     *out = h.release();
     return OMV_OK;
 }
@@ -719,7 +693,7 @@ omv_status omv_essgraph_optimize(omv_essgraph *h, int iterations, int max_trials
     omv_status rs;
     if (iterations == 0) {   // the initial chi alone
         if ((rs = launch_linearise(h, nullptr, kGateAlways, nullptr, nullptr, nullptr)) != OMV_OK) return rs;
-        ess_begin_kernel<<<1, 256, 0, st>>>(c, h->d_chi2, G.n_e, h->d_diag, h->BP.nb, 1);
+        ess_begin_kernel<<<1, 256, 0, st>>>(c, h->d_chi2, G.n_e, h->d_diag, h->ldlt.pat.nb, 1);
         HIP_OK(hipGetLastError());
     }
     const long long steps = (long long)iterations * max_trials;
@@ -776,42 +750,20 @@ omv_status omv_essgraph_reset(omv_essgraph *h) {
 
 omv_status omv_essgraph_blocks(omv_essgraph *h, int *n_blocks, int *n_levels) {
     if (!h || !n_blocks || !n_levels) return OMV_ERR_ARG;
-    *n_blocks = h->has ? h->BP.nb : 0, *n_levels = h->has ? h->BP.n_lev : 0;
+    *n_blocks = h->has ? h->ldlt.pat.nb : 0, *n_levels = h->has ? h->ldlt.pat.n_lev : 0;
     return OMV_OK;
 }
 
 omv_status omv_essgraph_debug_solve(omv_essgraph *h, double lambda, double *S, double *rhs, double *x, int32_t *fail,
                                     int32_t *plan, int plan_cap) {
     if (!h || !S || !rhs || !x || !fail || !plan || !(lambda > 0.0) || !std::isfinite(lambda) || !h->has) return OMV_ERR_ARG;
-    const BlockPat &B = h->BP;
-    const LbaPlan &L = h->plan.L;
-    const int n = 16 * B.nb;
-    if (plan_cap < 4 + B.n_lev) return OMV_ERR_ARG;
+    if (plan_cap < 4 + h->ldlt.pat.n_lev) return OMV_ERR_ARG;
     omv_status rs;
     if ((rs = launch_linearise(h, nullptr, kGateAlways, nullptr, nullptr, nullptr)) != OMV_OK) return rs;
     if ((rs = launch_solve(h, nullptr, lambda)) != OMV_OK) return rs;
     HIP_OK(hipStreamSynchronize(h->stream));
-    std::vector<double> blocks((size_t)B.n_slots * 256);
-    HIP_OK(hipMemcpy(blocks.data(), h->d_S, blocks.size() * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(rhs, h->d_b, n * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(x, h->d_x, n * sizeof(double), hipMemcpyDeviceToHost));
-    int f = 0;
-    HIP_OK(hipMemcpy(&f, h->d_fail, sizeof(int), hipMemcpyDeviceToHost));
-    *fail = f;
-    std::fill(S, S + (size_t)n * n, 0.0);
-    for (int t = 0; t < B.n_slots; ++t) {
-        const int kr = L.slot_kr[t], kc = L.slot_kc[t];
-        for (int r = 0; r < 16; ++r)
-            for (int c = 0; c < 16; ++c) {
-                if (kr == kc && c > r) continue;   // the solver reads a diagonal block's lower triangle
-                const double v = blocks[(size_t)t * 256 + sw16(r, c)];
-                S[(size_t)(16 * kr + r) * n + 16 * kc + c] = v;
-                S[(size_t)(16 * kc + c) * n + 16 * kr + r] = v;
-            }
-    }
-    plan[0] = L.use_lds, plan[1] = B.n_slots, plan[2] = B.n_lds, plan[3] = B.n_lev;
-    for (int l = 0; l < B.n_lev; ++l) plan[4 + l] = L.lev_start[l + 1] - L.lev_start[l];
-    return OMV_OK;
+    HIP_OK(hipMemcpy(rhs, h->d_b, 16 * (size_t)h->ldlt.pat.nb * sizeof(double), hipMemcpyDeviceToHost));
+    return h->ldlt.read_solved(h->plan.L, h->d_S, h->d_x, h->d_fail, S, x, fail, plan);
 }
 
 omv_status omv_essgraph_recover(omv_essgraph *h, int mode, float *poses, int n_points, float *points,

@@ -36,15 +36,13 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/omv.h"
 #include "g2o_types.h"
 #include "lba_plan.h"
 #include "omv_device.h"
-#include "omv_host.h"
-#include "omv_ldlt.h"
+#include "omv_ldlt_host.h"
 #include "omv_lm.h"
 
 namespace {
@@ -1575,6 +1573,17 @@ __global__ void __launch_bounds__(256) vis_lambda_kernel(const double *part, int
 }  // namespace
 
 // =============================================================================================
+// The single-rank epilogue's staging block, on the device and in pinned memory alike, in doubles:
+// [state without points (head) | P points | E outlier flags, padded to 8 bytes | E chi2], edges and points in the
+// caller's order.
+struct StageLayout {
+    size_t head, P, E;
+    size_t pts() const { return head; }
+    size_t flags() const { return head + 3 * P; }
+    size_t chi2() const { return flags() + (E + 7) / 8; }
+    size_t bytes(bool with_chi2) const { return (chi2() + (with_chi2 ? E : 0)) * sizeof(double); }
+};
+
 // What omv_lba_set_problem fills: the host plan, the counts and every pointer into the problem arena.  One value, so
 // that a handle without a problem is this struct's default.
 struct LbaDeviceProblem {
@@ -1589,7 +1598,7 @@ struct LbaDeviceProblem {
     Land L{};
     Red R{};
     Imu I{};
-    BlockPat BP{};
+    LdltSolver ldlt{};   // the uploaded block pattern (ldlt.pat) and the solver's launch on it
     Gather G{};
     SharedB sb{-1, -1, 0.0, 0.0, {nullptr, nullptr}, {nullptr, nullptr}};   // the shared bias pair (omv_fiba's bInit form)
     // omv_fiba: the caller's edges in the graph (a map point seen by fixed keyframes only is no vertex, its edges are
@@ -1601,11 +1610,10 @@ struct LbaDeviceProblem {
     const int *d_lkf_kf = nullptr;      // per (group, local keyframe): the keyframe
     const int *d_big = nullptr;
     // device epilogue (single rank): the plan's perm_edge / order / track_depth on the device, one staging block
-    // [state without points | points in caller order | chi2 in caller order | outlier flags in caller order]
     int *d_perm_edge = nullptr, *d_perm_pt = nullptr;
     float *d_track_depth = nullptr;
     double *d_stage = nullptr, *h_stage = nullptr;
-    size_t stage_bytes = 0;
+    StageLayout stage() const { return StageLayout{(size_t)(st[0].pts - st[0].Rwb), (size_t)n_pts, (size_t)n_mono}; }
     bool epi_ready = false;    // the staging block holds this optimize()'s final result
     bool epi_chi2 = false;     //   including the chi2
     int *d_offP = nullptr, *d_offV = nullptr, *d_offG = nullptr, *d_offA = nullptr;
@@ -1678,6 +1686,17 @@ static void free_problem(omv_lba *h) {
     }
 }
 
+// Both state buffers hold the uploaded state (st[2]) again and the first is the current one; waits for the copies.
+// omv_lba_reset, and the end of vba_upload, where `cur` is 0 already (free_problem) and setting it changes nothing.
+static omv_status restore_uploaded_state(omv_lba *h) {
+    for (int b = 0; b < 2; ++b)
+        HIP_OK(hipMemcpyAsync(h->st[b].Rwb, h->st[2].Rwb, h->state_doubles() * sizeof(double), hipMemcpyDeviceToDevice,
+                              h->stream));
+    h->cur = 0;
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return OMV_OK;
+}
+
 omv_lba::~omv_lba() {   // `mem` frees h_out, h_ctl and d_ctl after this body
     free_problem(this);
     for (auto &e : ev)
@@ -1704,17 +1723,7 @@ static omv_status upload_problem(omv_lba *h, const omv_lba_problem *p) {
         for (int q = 0; q < 9; ++q) rig.Rcb[c][q] = p->Rcb[9 * c + q], rig.Rbc[c][q] = p->Rbc[9 * c + q];
         for (int q = 0; q < 3; ++q) rig.tcb[c][q] = p->tcb[3 * c + q], rig.tbc[c][q] = p->tbc[3 * c + q];
     }
-    omv::DeviceArena &mem = h->prob;
-    bool ok = true;   // cleared by the first allocation or copy that fails
-    auto upn = [&](const auto *src, size_t n) {   // a device copy of n host elements; null on failure
-        using T = std::remove_const_t<std::remove_pointer_t<decltype(src)>>;
-        T *d = nullptr;
-        if (ok && (!mem.alloc(&d, n) || (n > 0 && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)))
-            ok = false, d = nullptr;
-        return d;
-    };
-    auto upv = [&](const auto &v) { return upn(v.data(), v.size()); };   // a host vector's device copy
-    auto buf = [&](auto **d, size_t n) { ok = ok && mem.alloc(d, n); };  // an uninitialised work buffer
+    omv::Uploader up{h->prob};
     {   // one contiguous block per state: Rwb | twb | Rcw | tcw | vel | bg | ba | pts (device order): one copy to read back
         std::vector<double> init;
         auto add = [&](const double *src, size_t n) { init.insert(init.end(), src, src + n); };
@@ -1723,64 +1732,59 @@ static omv_status upload_problem(omv_lba *h, const omv_lba_problem *p) {
         for (int q : pl.order) add(p->pts + 3 * (size_t)q, 3);
         init.resize(h->state_doubles());
         for (State &s : h->st) {
-            s.Rwb = upv(init);
-            if (!ok) return OMV_ERR_HIP;
+            s.Rwb = up.copy(init);
+            if (!up.ok) return OMV_ERR_HIP;
             s.twb = s.Rwb + 9 * K, s.Rcw = s.twb + 3 * K, s.tcw = s.Rcw + 9 * K * C;
             s.vel = s.tcw + 3 * K * C, s.bg = s.vel + 3 * K, s.ba = s.bg + 3 * K, s.pts = s.ba + 3 * K;
         }
     }
-    h->E = Edges{upv(pl.e_pt), upv(pl.e_kf), upv(pl.e_cam), upv(pl.e_slot), upv(pl.e_obs), upv(pl.e_w), upv(pl.e_ur), E};
+    h->E = Edges{up.copy(pl.e_pt),  up.copy(pl.e_kf), up.copy(pl.e_cam), up.copy(pl.e_slot),
+                 up.copy(pl.e_obs), up.copy(pl.e_w),  up.copy(pl.e_ur),  E};
     {
         Land &L = h->L;
-        L.edge_start = upv(pl.pt_edge), L.slot_start = upv(pl.pt_slot), L.slot_kf = upv(pl.slot_kf);
-        L.slot_edge = upv(pl.slot_edge), L.slot_lkf = upv(pl.slot_lkf);
-        buf(&L.lnd, 12 * (size_t)P), buf(&L.M, 18 * (size_t)pl.n_pt_slots);
-        buf(&L.rec, 36 * (size_t)pl.blk_start[n_slots]), buf(&L.rec_rhs, 12 * (size_t)pl.rhs_start[nb]);
+        L.edge_start = up.copy(pl.pt_edge), L.slot_start = up.copy(pl.pt_slot), L.slot_kf = up.copy(pl.slot_kf);
+        L.slot_edge = up.copy(pl.slot_edge), L.slot_lkf = up.copy(pl.slot_lkf);
+        up.buffer(&L.lnd, 12 * (size_t)P), up.buffer(&L.M, 18 * (size_t)pl.n_pt_slots);
+        up.buffer(&L.rec, 36 * (size_t)pl.blk_start[n_slots]), up.buffer(&L.rec_rhs, 12 * (size_t)pl.rhs_start[nb]);
         L.n = P;
-        L.grp_pt = upv(pl.grp_pt), L.grp_w = upv(pl.grp_w), L.grp_tp = upv(pl.grp_tp), L.tp = upv(pl.tp);
-        L.grp_blk = upv(pl.grp_blk), L.blkoff = upv(pl.blkoff), L.grp_kf = upv(pl.grp_kf), L.rhsoff = upv(pl.rhsoff);
-        h->d_big = upv(pl.big_grp), h->d_e_lkf = upv(pl.e_lkf), h->d_lkf_kf = upv(pl.lkf_kf);
+        L.grp_pt = up.copy(pl.grp_pt), L.grp_w = up.copy(pl.grp_w), L.grp_tp = up.copy(pl.grp_tp), L.tp = up.copy(pl.tp);
+        L.grp_blk = up.copy(pl.grp_blk), L.blkoff = up.copy(pl.blkoff), L.grp_kf = up.copy(pl.grp_kf);
+        L.rhsoff = up.copy(pl.rhsoff);
+        h->d_big = up.copy(pl.big_grp), h->d_e_lkf = up.copy(pl.e_lkf), h->d_lkf_kf = up.copy(pl.lkf_kf);
     }
-    h->d_offP = upv(pl.offP), h->d_offV = upv(pl.offV), h->d_offG = upv(pl.offG), h->d_offA = upv(pl.offA);
+    h->d_offP = up.copy(pl.offP), h->d_offV = up.copy(pl.offV), h->d_offG = up.copy(pl.offG), h->d_offA = up.copy(pl.offA);
     h->R = Red{nred, h->d_offP, K};
     h->sb.blk = pl.shared_blk, h->sb.kf = pl.shared_kf;   // (the priors: omv_fiba_set_problem)
     // inertial edges, then the reduction work lists
     std::vector<uint8_t> rob(ni, 0);
     if (p->imu_robust) std::copy(p->imu_robust, p->imu_robust + ni, rob.begin());
-    h->I = Imu{NI, upn(p->imu_kf1, ni), upn(p->imu_kf2, ni), upn(p->preint, ni * kPF), upv(pl.info9), upv(pl.infoG),
-               upv(pl.infoA), upv(rob), h->d_offP, h->d_offV, h->d_offG, h->d_offA};
-    buf(&h->d_imu_contrib, ni * kImuContrib);
-    h->G = Gather{upv(pl.blk_start), upv(pl.rhs_start), (const int4 *)upv(pl.imu_blk), upv(pl.ib_start),
-                  (const int2 *)upv(pl.imu_vec), upv(pl.iv_start), h->d_imu_contrib};
-    {   // block pattern + level schedule (one blob: LbaPlan::blob)
-        const int *kr = upv(pl.slot_kr), *kc = upv(pl.slot_kc), *d = upv(pl.blob);
-        if (!ok) return OMV_ERR_HIP;
-        const LbaPlan::BlobOff &o = pl.off;
-        h->BP = BlockPat{nb, n_slots, pl.n_lev, pl.n_lds, d + o.perm, kr, kc, d + o.dslot, d + o.lev_start, d + o.lev_col,
-                         d + o.ug_start, d + o.ug_split, d + o.crit_grp, d + o.ug_task_start, (const int4 *)(d + o.ug),
-                         (const int4 *)(d + o.inv_rec), d + o.rs_start, (const int2 *)(d + o.rs), d + o.cs_start,
-                         (const int2 *)(d + o.cs), d, pl.blob_ints};
-    }
+    h->I = Imu{NI, up.copy(p->imu_kf1, ni), up.copy(p->imu_kf2, ni), up.copy(p->preint, ni * kPF), up.copy(pl.info9),
+               up.copy(pl.infoG), up.copy(pl.infoA), up.copy(rob), h->d_offP, h->d_offV, h->d_offG, h->d_offA};
+    up.buffer(&h->d_imu_contrib, ni * kImuContrib);
+    h->G = Gather{up.copy(pl.blk_start), up.copy(pl.rhs_start), (const int4 *)up.copy(pl.imu_blk), up.copy(pl.ib_start),
+                  (const int2 *)up.copy(pl.imu_vec), up.copy(pl.iv_start), h->d_imu_contrib};
+    h->ldlt = LdltSolver::upload(pl, up);   // block pattern + level schedule
+    if (!up.ok) return OMV_ERR_HIP;
     // work buffers
     // d_err9: [9n errors | n chi2 | 9n rotation errors eR]; the *_b set: the device driver's second (double-buffered) one
     // d_S: [packed blocks | b | coef], contiguous, the one buffer a sharded solve all-reduces per trial
-    buf(&h->d_err, 2 * (size_t)E), buf(&h->d_chi2, E), buf(&h->d_err3, E), buf(&h->d_err9, 19 * ni);
-    buf(&h->d_err_b, 2 * (size_t)E), buf(&h->d_chi2_b, E), buf(&h->d_err3_b, E), buf(&h->d_err9_b, 19 * ni);
-    buf(&h->d_partial, pl.n_lgrp), buf(&h->d_imu_partial, 1), buf(&h->d_partial0, pl.n_lgrp), buf(&h->d_imu_partial0, 1);
-    buf(&h->d_scale_partial, pl.n_lgrp + 1), buf(&h->d_out, 4), buf(&h->d_S, pl.n_reduce), buf(&h->d_x, nred);
-    buf(&h->d_scratch, pl.use_lds == 1 ? 8 : pl.n_reduce + 8), buf(&h->d_fail, 1);
-    if (!ok) return OMV_ERR_HIP;
+    up.buffer(&h->d_err, 2 * (size_t)E), up.buffer(&h->d_chi2, E), up.buffer(&h->d_err3, E), up.buffer(&h->d_err9, 19 * ni);
+    up.buffer(&h->d_err_b, 2 * (size_t)E), up.buffer(&h->d_chi2_b, E), up.buffer(&h->d_err3_b, E);
+    up.buffer(&h->d_err9_b, 19 * ni), up.buffer(&h->d_partial, pl.n_lgrp), up.buffer(&h->d_imu_partial, 1);
+    up.buffer(&h->d_partial0, pl.n_lgrp), up.buffer(&h->d_imu_partial0, 1), up.buffer(&h->d_scale_partial, pl.n_lgrp + 1);
+    up.buffer(&h->d_out, 4), up.buffer(&h->d_S, pl.n_reduce), up.buffer(&h->d_x, nred);
+    up.buffer(&h->d_scratch, LdltSolver::scratch_doubles(pl)), up.buffer(&h->d_fail, 1);
+    if (!up.ok) return OMV_ERR_HIP;
     h->d_bb = h->d_S + (size_t)n_slots * 256;
     h->d_coef = h->d_bb + nred;
     HIP_OK(hipMemset(h->d_imu_partial, 0, sizeof(double)));
     HIP_OK(hipMemset(h->d_imu_partial0, 0, sizeof(double)));
     // device epilogue (single rank): caller-order permutations, trackDepth in device order, the staging block
     if (h->world == 1) {
-        const size_t head = (size_t)(h->st[0].pts - h->st[0].Rwb);
-        h->stage_bytes = (head + 3 * (size_t)P + ((size_t)E + 7) / 8 + (size_t)E) * sizeof(double);
-        h->d_perm_edge = upv(pl.perm_edge), h->d_perm_pt = upv(pl.order), h->d_track_depth = upv(pl.track_depth);
-        buf(&h->d_stage, (h->stage_bytes + 7) / 8);
-        if (!ok || !mem.alloc_pinned(&h->h_stage, h->stage_bytes / sizeof(double))) return OMV_ERR_HIP;
+        const size_t stage_doubles = h->stage().bytes(true) / sizeof(double);
+        h->d_perm_edge = up.copy(pl.perm_edge), h->d_perm_pt = up.copy(pl.order), h->d_track_depth = up.copy(pl.track_depth);
+        up.buffer(&h->d_stage, stage_doubles);
+        if (!up.ok || !h->prob.alloc_pinned(&h->h_stage, stage_doubles)) return OMV_ERR_HIP;
     }
     return OMV_OK;
 }
@@ -1799,10 +1803,7 @@ omv_status omv_lba_create(int max_kf, int max_cams, int max_pts, int max_mono, i
     if (!h->mem.alloc_pinned(&h->h_out, 4) || !h->mem.alloc_pinned(&h->h_ctl, 1) || !h->mem.alloc(&h->d_ctl, 1))
         return OMV_ERR_HIP;
     // the reduced-system factorisation stages its nonzero blocks in up to 150 KB of LDS
-    h->lds_ok = hipFuncSetAttribute((const void *)ldlt_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kLdltLds) == hipSuccess &&
-                hipFuncSetAttribute((const void *)ldlt_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kLdltLds) == hipSuccess;
+    h->lds_ok = LdltSolver::opt_in_lds();
     // the landmark groups of the build take ~77 KB of LDS (two workgroups per CU)
     for (const void *k : {(const void *)build_all_kernel<false>, (const void *)build_big_kernel<false>,
                           (const void *)build_all_kernel<true>, (const void *)build_big_kernel<true>})
@@ -1995,22 +1996,10 @@ static omv_status launch_build(omv_lba *h, const State &A, const State &B, const
 static omv_status launch_assemble(omv_lba *h, const State &A, const State &B, double lambda, const LmCtl *c) {
     SharedB sb = h->sb;   // the priors' gradient reads the current state's pair (A; by the control block's `cur`: A or B)
     sb.bg[0] = A.bg, sb.ba[0] = A.ba, sb.bg[1] = B.bg, sb.ba[1] = B.ba;
-    assemble_kernel<<<h->BP.n_slots, 256, 0, h->stream>>>(h->G, h->I, h->BP, sb, h->L.rec, h->L.rec_rhs, lambda,
+    assemble_kernel<<<h->ldlt.pat.n_slots, 256, 0, h->stream>>>(h->G, h->I, h->ldlt.pat, sb, h->L.rec, h->L.rec_rhs, lambda,
                                                           h->rank == 0 ? 1 : 0, h->d_S, h->d_bb, h->d_coef, c);
     HIP_OK(hipGetLastError());
     return OMV_OK;
-}
-
-static void launch_ldlt(omv_lba *h, const LmCtl *c) {
-    if (h->plan.use_lds == 1)
-        ldlt_kernel<0><<<1, kLdltThreads, h->plan.ldlt_lds, h->stream>>>(h->d_S, h->BP, h->d_bb, h->d_coef, h->d_x,
-                                                                    h->d_scratch, h->d_fail, c);
-    else if (h->plan.use_lds == 2)
-        ldlt_kernel<2><<<1, kLdltThreads, h->plan.ldlt_lds, h->stream>>>(h->d_S, h->BP, h->d_bb, h->d_coef, h->d_x,
-                                                                    h->d_scratch, h->d_fail, c);
-    else
-        ldlt_kernel<1><<<1, kLdltThreads, 0, h->stream>>>(h->d_S, h->BP, h->d_bb, h->d_coef, h->d_x, h->d_scratch,
-                                                          h->d_fail, c);
 }
 
 // One LM step of the device driver: the gated kernel sequence (see LmCtl).  The state and error buffers are
@@ -2035,7 +2024,7 @@ static omv_status lba_step(omv_lba *h, hipEvent_t *ev) {
     // sharded: one in-place SUM of this rank's partial reduced system [blocks | b | Schur rhs], ordered on the stream
     if ((rs = lba_allreduce(h, h->d_S, h->plan.n_reduce)) != OMV_OK) return rs;
     if (ev) HIP_OK(hipEventRecord(ev[2], st));
-    launch_ldlt(h, c);
+    h->ldlt.launch(st, h->d_S, h->d_bb, h->d_coef, h->d_x, h->d_scratch, h->d_fail, c);
     if (ev) HIP_OK(hipEventRecord(ev[3], st));
     if ((rs = lba_trial_errors(h, c)) != OMV_OK) return rs;
     const int nmb = n_grp_err(h), nsc = 1 + h->plan.n_lgrp;
@@ -2233,7 +2222,7 @@ omv_status omv_lba_optimize(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *
             // one exchange: sum the partial reduced systems [blocks | b | Schur rhs] of the landmark shards
             if ((rs = lba_allreduce(h, h->d_S, h->plan.n_reduce)) != OMV_OK) return rs;
             HIP_OK(hipEventRecord(h->ev[3], st));
-            launch_ldlt(h, nullptr);
+            h->ldlt.launch(st, h->d_S, h->d_bb, h->d_coef, h->d_x, h->d_scratch, h->d_fail, nullptr);
             HIP_OK(hipEventRecord(h->ev[4], st));
             // the keyframe update and the landmarks' back-substitution A -> B, the trial's errors (one launch, this
             // driver's one error buffer)
@@ -2288,10 +2277,10 @@ static omv_status lba_enqueue_epilogue(omv_lba *h, bool want_chi2) {
     hipStream_t st = h->stream;
     const State &s = h->st[0];
     const int P = h->n_pts, E = h->n_mono;
-    const size_t head = (size_t)(s.pts - s.Rwb), fl = ((size_t)E + 7) / 8;
-    double *d_pts = h->d_stage + head;
-    uint8_t *d_flags = (uint8_t *)(d_pts + 3 * (size_t)P);
-    double *d_chi2 = d_pts + 3 * (size_t)P + fl;
+    const StageLayout L = h->stage();
+    const size_t head = L.head;
+    double *d_pts = h->d_stage + L.pts(), *d_chi2 = h->d_stage + L.chi2();
+    uint8_t *d_flags = (uint8_t *)(h->d_stage + L.flags());
     const int n = std::max(std::max(E, P), (int)head);
     auto launch = [&](auto kernel) {
         kernel<<<(n + 255) / 256, 256, 0, st>>>(h->rig, s, h->st[1], h->state_doubles(), h->E, h->d_perm_edge,
@@ -2302,10 +2291,33 @@ static omv_status lba_enqueue_epilogue(omv_lba *h, bool want_chi2) {
     if (h->visual) launch(epilogue_kernel<true>);
     else launch(epilogue_kernel<false>);
     HIP_OK(hipGetLastError());
-    const size_t bytes = (head + 3 * (size_t)P + fl + (want_chi2 ? (size_t)E : 0)) * sizeof(double);
-    HIP_OK(hipMemcpyAsync(h->h_stage, h->d_stage, bytes, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(h->h_stage, h->d_stage, L.bytes(want_chi2), hipMemcpyDeviceToHost, st));
     h->epi_ready = true, h->epi_chi2 = want_chi2;
     return OMV_OK;
+}
+// The pinned staging block holds this optimize()'s result, with the chi2 when wanted: already in flight with the LM
+// control's last read-back when the device driver ran, else enqueued and waited for here.
+static omv_status lba_await_epilogue(omv_lba *h, bool want_chi2) {
+    if (!h->epi_ready || (want_chi2 && !h->epi_chi2)) {
+        const omv_status rs = lba_enqueue_epilogue(h, want_chi2);
+        if (rs != OMV_OK) return rs;
+        HIP_OK(hipStreamSynchronize(h->stream));
+    }
+    h->epi_ready = false;
+    return OMV_OK;
+}
+// The points and the per-edge results a caller asked for (null: not wanted) out of the pinned block.
+static void take_staged(const omv_lba *h, double *pts, double *mono_chi2, double *stereo_chi2, uint8_t *mono_outlier,
+                        uint8_t *stereo_outlier) {
+    const StageLayout L = h->stage();
+    const double *hs = h->h_stage, *hc = hs + L.chi2();
+    const uint8_t *hf = (const uint8_t *)(hs + L.flags());
+    const size_t EM = h->n_mono_all, ES = h->n_stereo_all;
+    if (L.P > 0) std::memcpy(pts, hs + L.pts(), 3 * sizeof(double) * L.P);
+    if (mono_chi2) std::memcpy(mono_chi2, hc, sizeof(double) * EM);
+    if (stereo_chi2) std::memcpy(stereo_chi2, hc + EM, sizeof(double) * ES);
+    if (mono_outlier) std::memcpy(mono_outlier, hf, EM);
+    if (stereo_outlier) std::memcpy(stereo_outlier, hf + EM, ES);
 }
 
 static omv_status lba_finish_result(omv_lba *h, const omv_lba_opts *o, omv_lba_problem *p, omv_lba_result *res) {
@@ -2325,23 +2337,10 @@ static omv_status lba_finish_result(omv_lba *h, const omv_lba_opts *o, omv_lba_p
     if (lba_epilogue_ok(h)) {
         // device epilogue: outlier flags / chi2 / points in the caller's order, one staging read-back (already in
         // flight with the LM control's last read-back when the device driver ran)
-        const bool want_chi2 = res->mono_chi2 || res->stereo_chi2;
-        if (!h->epi_ready || (want_chi2 && !h->epi_chi2)) {
-            omv_status rs = lba_enqueue_epilogue(h, want_chi2);
-            if (rs != OMV_OK) return rs;
-            HIP_OK(hipStreamSynchronize(st));
-        }
-        h->epi_ready = false;
-        const size_t head = (size_t)(s.pts - s.Rwb);
+        const omv_status rs = lba_await_epilogue(h, res->mono_chi2 || res->stereo_chi2);
+        if (rs != OMV_OK) return rs;
         take_head(h->h_stage);
-        std::memcpy(p->pts, h->h_stage + head, 3 * sizeof(double) * (size_t)P);
-        const uint8_t *hf = (const uint8_t *)(h->h_stage + head + 3 * (size_t)P);
-        const double *hc = h->h_stage + head + 3 * (size_t)P + ((size_t)E + 7) / 8;
-        const int EM = h->n_mono_all, ES = h->n_stereo_all;
-        if (res->mono_chi2) std::memcpy(res->mono_chi2, hc, sizeof(double) * EM);
-        if (res->stereo_chi2) std::memcpy(res->stereo_chi2, hc + EM, sizeof(double) * ES);
-        if (res->mono_outlier) std::memcpy(res->mono_outlier, hf, EM);
-        if (res->stereo_outlier) std::memcpy(res->stereo_outlier, hf + EM, ES);
+        take_staged(h, p->pts, res->mono_chi2, res->stereo_chi2, res->mono_outlier, res->stereo_outlier);
         return OMV_OK;
     }
     // sharded rank: this rank's landmarks and edges only, on the host
@@ -2381,12 +2380,7 @@ static omv_status lba_finish_result(omv_lba *h, const omv_lba_opts *o, omv_lba_p
 
 omv_status omv_lba_reset(omv_lba *h) {
     if (!h || !has_problem(h)) return OMV_ERR_ARG;
-    for (int b = 0; b < 2; ++b)
-        HIP_OK(hipMemcpyAsync(h->st[b].Rwb, h->st[2].Rwb, h->state_doubles() * sizeof(double), hipMemcpyDeviceToDevice,
-                              h->stream));
-    h->cur = 0;
-    HIP_OK(hipStreamSynchronize(h->stream));
-    return OMV_OK;
+    return restore_uploaded_state(h);
 }
 
 omv_status omv_lba_set_comm(omv_lba *h, int rank, int world, omv_allreduce_fn allreduce, void *ctx) {
@@ -2458,41 +2452,22 @@ omv_status omv_selftest_inv16(int batch, const double *D, double *Dinv, int32_t 
 omv_status omv_lba_debug_solve(omv_lba *h, const omv_lba_opts *o, double lambda, double *S, double *rhs, double *x,
                                int32_t *fail, int32_t *plan, int plan_cap) {
     if (!h || !o || !S || !rhs || !x || !fail || !plan || !(lambda > 0.0) || !std::isfinite(lambda)) return OMV_ERR_ARG;
-    const BlockPat &B = h->BP;
-    const int nb = B.nb, n = 16 * nb;
+    const BlockPat &B = h->ldlt.pat;
+    const int n = 16 * B.nb;
     if (!has_problem(h) || h->world != 1 || plan_cap < 4 + B.n_lev) return OMV_ERR_ARG;
     const State &A = h->st[h->cur];
     omv_status rs;
     if ((rs = lba_errors(h, A)) != OMV_OK) return rs;
     if ((rs = launch_build(h, A, A, nullptr, lambda)) != OMV_OK) return rs;
     if ((rs = launch_assemble(h, A, A, lambda, nullptr)) != OMV_OK) return rs;
-    launch_ldlt(h, nullptr);
+    h->ldlt.launch(h->stream, h->d_S, h->d_bb, h->d_coef, h->d_x, h->d_scratch, h->d_fail, nullptr);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(h->stream));
-    std::vector<double> blocks((size_t)B.n_slots * 256), bb(n), coef(n);
-    const std::vector<int> &kr = h->plan.slot_kr, &kc = h->plan.slot_kc, &lev = h->plan.lev_start;
-    HIP_OK(hipMemcpy(blocks.data(), h->d_S, blocks.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<double> bb(n), coef(n);
     HIP_OK(hipMemcpy(bb.data(), h->d_bb, n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(coef.data(), h->d_coef, n * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(x, h->d_x, n * sizeof(double), hipMemcpyDeviceToHost));
-    int f = 0;
-    HIP_OK(hipMemcpy(&f, h->d_fail, sizeof(int), hipMemcpyDeviceToHost));
-    *fail = f;
-    std::fill(S, S + (size_t)n * n, 0.0);
-    for (int t = 0; t < B.n_slots; ++t) {
-        const bool diag = kr[t] == kc[t];
-        for (int r = 0; r < 16; ++r)
-            for (int c = 0; c < 16; ++c) {
-                if (diag && c > r) continue;   // a diagonal block stores its lower triangle
-                const double v = blocks[(size_t)t * 256 + sw16(r, c)];
-                S[(size_t)(16 * kr[t] + r) * n + 16 * kc[t] + c] = v;
-                S[(size_t)(16 * kc[t] + c) * n + 16 * kr[t] + r] = v;
-            }
-    }
     for (int q = 0; q < n; ++q) rhs[q] = bb[q] - coef[q];
-    plan[0] = h->plan.use_lds, plan[1] = B.n_slots, plan[2] = B.n_lds, plan[3] = B.n_lev;
-    for (int l = 0; l < B.n_lev; ++l) plan[4 + l] = lev[l + 1] - lev[l];
-    return OMV_OK;
+    return h->ldlt.read_solved(h->plan, h->d_S, h->d_x, h->d_fail, S, x, fail, plan);
 }
 
 }  // extern "C"
@@ -2569,11 +2544,7 @@ static omv_status vba_upload(omv_lba *h, const omv_vba_problem *p) {
     const int n = h->n_kf * p->n_cams;
     vis_cams_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(h->rig, v, h->st[2], h->n_kf);
     HIP_OK(hipGetLastError());
-    for (int b = 0; b < 2; ++b)
-        HIP_OK(hipMemcpyAsync(h->st[b].Rwb, h->st[2].Rwb, h->state_doubles() * sizeof(double), hipMemcpyDeviceToDevice,
-                              h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
-    return OMV_OK;
+    return restore_uploaded_state(h);
 }
 
 static omv_status vba_set_huber(omv_lba *h, const omv_vba_opts *o) {
@@ -2651,28 +2622,16 @@ omv_status omv_vba_optimize(omv_vba *hv, const omv_vba_opts *o, omv_vba_problem 
     const LmCtl &c = *h->h_ctl;
     r->err = c.err0, r->err_end = c.errors_chi, r->iterations = c.its, r->trials = c.trials, r->lambda = c.lm.lambda;
     r->lambda_init = c.lambda_init;
-    // the epilogue's staging block: [state head | points | flags | chi2] in the caller's order
-    const bool want_chi2 = r->mono_chi2 || r->stereo_chi2;
+    // the epilogue's staging block: q in the keyframe's Rwb slot and t in twb (vba_translate), then the shared part
     if (!lba_epilogue_ok(h)) return OMV_ERR_HIP;
-    if (!h->epi_ready || (want_chi2 && !h->epi_chi2)) {
-        if ((rs = lba_enqueue_epilogue(h, want_chi2)) != OMV_OK) return rs;
-        HIP_OK(hipStreamSynchronize(h->stream));
-    }
-    h->epi_ready = false;
-    const int K = h->n_kf, P = h->n_pts, E = h->n_mono, EM = h->n_mono_all, ES = h->n_stereo_all;
-    const size_t head = (size_t)(h->st[0].pts - h->st[0].Rwb);
+    if ((rs = lba_await_epilogue(h, r->mono_chi2 || r->stereo_chi2)) != OMV_OK) return rs;
+    const int K = h->n_kf;
     const double *hs = h->h_stage;
     for (int k = 0; k < K; ++k) {
         std::memcpy(p->q_cw + 4 * (size_t)k, hs + 9 * (size_t)k, 4 * sizeof(double));
         std::memcpy(p->t_cw + 3 * (size_t)k, hs + 9 * (size_t)K + 3 * (size_t)k, 3 * sizeof(double));
     }
-    if (P > 0) std::memcpy(p->pts, hs + head, 3 * sizeof(double) * (size_t)P);
-    const uint8_t *hf = (const uint8_t *)(hs + head + 3 * (size_t)P);
-    const double *hc = hs + head + 3 * (size_t)P + ((size_t)E + 7) / 8;
-    if (r->mono_chi2) std::memcpy(r->mono_chi2, hc, sizeof(double) * EM);
-    if (r->stereo_chi2) std::memcpy(r->stereo_chi2, hc + EM, sizeof(double) * ES);
-    if (r->mono_outlier) std::memcpy(r->mono_outlier, hf, EM);
-    if (r->stereo_outlier) std::memcpy(r->stereo_outlier, hf + EM, ES);
+    take_staged(h, p->pts, r->mono_chi2, r->stereo_chi2, r->mono_outlier, r->stereo_outlier);
     return OMV_OK;
 }
 

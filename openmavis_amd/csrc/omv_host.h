@@ -117,4 +117,22 @@ private:
     std::vector<Block> blocks_;
 };
 
+// A problem's upload into an arena, one allocation per array.  The first allocation or copy that fails clears `ok`;
+// every later call then allocates nothing and returns null, so the caller checks `ok` where it must and at the end.
+struct Uploader {
+    DeviceArena &mem;
+    bool ok = true;
+    template <class T>
+    T *copy(const T *src, size_t n) {   // a device copy of n host elements
+        T *d = nullptr;
+        if (ok && (!mem.alloc(&d, n) || (n > 0 && hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)))
+            ok = false, d = nullptr;
+        return d;
+    }
+    template <class T>
+    T *copy(const std::vector<T> &v) { return copy(v.data(), v.size()); }
+    template <class T>
+    void buffer(T **d, size_t n) { ok = ok && mem.alloc(d, n); }   // an uninitialised work buffer
+};
+
 }  // namespace omv

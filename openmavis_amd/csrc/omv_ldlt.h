@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "omv_blk16.h"
 #include "omv_device.h"
 #include "omv_lm.h"
 #include "omv_math.h"
@@ -52,9 +53,7 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 // pj, row-major 16x16 each, holding H's block (perm[pi], perm[pj]).  Padding rows have zero gradient and
 // lambda on the diagonal, so they solve to exactly zero and add nothing to computeScale.  b and the Schur
 // right-hand side stay in keyframe order (16 k + r).
-// Entry (r, c) of a 16x16 block sits at 16 r + (c ^ r): a column read by 16 lanes (one per row), as the MFMA
-// A operands and the pivot columns are, touches 16 distinct LDS banks instead of two (rows are 32 banks apart).
-__host__ __device__ __forceinline__ int sw16(int r, int c) { return 16 * r + (c ^ r); }
+// Entry (r, c) of a block: sw16(r, c), omv_blk16.h.
 
 struct BlockPat {
     int nb, n_slots, n_lev;

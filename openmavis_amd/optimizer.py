@@ -31,11 +31,63 @@ def lba_options(large):
     return dict(opt_it=4, lambda_init=1e-2) if large else dict(opt_it=10, lambda_init=1e0)
 
 
-class LocalInertialBA:
+class _BlockSolverHandle:
+    """What the handles on the block LDL^T solver share (LocalInertialBA, LocalBundleAdjustment, FullInertialBA,
+    EssentialGraph): a subclass names its symbol prefix and sets _lib, _h and, with a problem, _s."""
+
+    _PREFIX = None   # "omv_lba": omv_lba_destroy, omv_lba_debug_solve, ...
+    _h = _s = None
+
+    def _call(self, name, *args):
+        sym = f"{self._PREFIX}_{name}"
+        _lib.check(getattr(self._lib, sym)(self._h, *args), sym)
+
+    def __del__(self):
+        if self._h:
+            getattr(self._lib, f"{self._PREFIX}_destroy")(self._h)
+            self._h = None
+
+    def _need(self, what):
+        if self._s is None:
+            raise _lib.OmvError(f"{type(self).__name__}.{what}: no problem set")
+
+    def _read_solve(self, call, nb, n_plan):
+        """debug_solve's result for `nb` blocks and a plan of `n_plan` entries; call(S, rhs, x, fail, plan, n_plan)
+        is the handle's omv_*_debug_solve behind its own leading arguments."""
+        n = 16 * nb
+        S, rhs, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
+        plan = np.full(n_plan, -1, np.int32)
+        fail = ctypes.c_int(-1)
+        call(_lib.ptr(S), _lib.ptr(rhs), _lib.ptr(x), ctypes.byref(fail), _lib.ptr(plan), len(plan))
+        n_lev = int(plan[3])
+        return dict(S=S, rhs=rhs, x=x, fail=fail.value, mode=int(plan[0]), n_slots=int(plan[1]), n_lds=int(plan[2]),
+                    n_lev=n_lev, cols=[int(v) for v in plan[4:4 + n_lev]])
+
+
+class _StagedBA(_BlockSolverHandle):
+    """The three bundle adjustments (omv_lba and its kinds omv_vba, omv_fiba): the stage events of their LM step.  The
+    pose graphs time a whole optimize() instead (EssentialGraph.last_ms)."""
+
+    def enable_timing(self, on=True):
+        """Per-stage events on the next optimize() calls (direct launches instead of the captured LM step)."""
+        self._call("enable_timing", int(bool(on)))
+        return self
+
+    def stage_ms(self):
+        """Device ms of the last optimize: build, schur, solve, update+errors; and the trial count."""
+        ms = np.zeros(4)
+        t = ctypes.c_int(0)
+        self._call("stage_ms", _lib.ptr(ms), ctypes.byref(t))
+        return dict(build=ms[0], schur=ms[1], solve=ms[2], update=ms[3], trials=t.value)
+
+
+class LocalInertialBA(_StagedBA):
     """`rank`, `world`, `allreduce`: landmark sharding (omv_lba_set_comm).  Every rank
     passes the same full problem; `allreduce(ptr, count, stream)` sums `count` doubles of device
     memory in place over the ranks (openmavis_amd.dist.LbaAllReduce).  After optimize() a rank's
     result holds its own landmarks / edges (`shard()` names them) and every keyframe."""
+
+    _PREFIX = "omv_lba"
 
     def __init__(self, max_kf=64, max_cams=5, max_pts=40000, max_mono=400000, max_imu=64, rank=0, world=1,
                  allreduce=None):
@@ -62,11 +114,6 @@ class LocalInertialBA:
             _lib.check(lib.omv_lba_set_comm(h, int(rank), int(world), ctypes.cast(self._cb, ctypes.c_void_p), None),
                        "omv_lba_set_comm")
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.omv_lba_destroy(self._h)
-            self._h = None
-
     def set_problem(self, prob):
         s, keep = as_struct(prob, _lib.LbaProblem)
         _lib.check(self._lib.omv_lba_set_problem(self._h, ctypes.byref(s)), "omv_lba_set_problem")
@@ -78,8 +125,7 @@ class LocalInertialBA:
         The optimised state is written back into the problem's host arrays (as the reference writes its keyframes and
         map points); state_copy=False returns those arrays themselves instead of copies (the next optimize() of this
         problem overwrites them)."""
-        if self._s is None:
-            raise _lib.OmvError("LocalInertialBA.optimize: no problem set")
+        self._need("optimize")
         o = _lib.LbaOpts(int(opt_it), float(lambda_init), int(max_trials), int(bool(large)))
         E, S = self._s.n_mono, self._s.n_stereo
         want = bool(chi2)
@@ -119,20 +165,11 @@ class LocalInertialBA:
         """One reduced-system solve at the uploaded state with damping `lambda_` (omv_lba_debug_solve; a test hook):
         S [n][n] dense in keyframe order (n = 16 n_opt, padding rows included), rhs [n], x [n], the fail flag and the
         solver's plan: mode (1 all blocks in LDS, 2 hybrid, 0 global), n_slots, n_lds, n_lev, cols (per level)."""
-        if self._s is None:
-            raise _lib.OmvError("LocalInertialBA.debug_solve: no problem set")
+        self._need("debug_solve")
         o = _lib.LbaOpts(10, 1e0, 10, 0)   # validated only: no option changes the robust kernels
         nb = int(self._s.n_opt)
-        n = 16 * nb
-        S, rhs, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
-        plan = np.full(4 + nb, -1, np.int32)
-        fail = ctypes.c_int(-1)
-        _lib.check(self._lib.omv_lba_debug_solve(self._h, ctypes.byref(o), ctypes.c_double(lambda_), _lib.ptr(S),
-                                                 _lib.ptr(rhs), _lib.ptr(x), ctypes.byref(fail), _lib.ptr(plan),
-                                                 len(plan)), "omv_lba_debug_solve")
-        n_lev = int(plan[3])
-        return dict(S=S, rhs=rhs, x=x, fail=fail.value, mode=int(plan[0]), n_slots=int(plan[1]), n_lds=int(plan[2]),
-                    n_lev=n_lev, cols=[int(v) for v in plan[4:4 + n_lev]])
+        return self._read_solve(lambda *out: self._call("debug_solve", ctypes.byref(o), ctypes.c_double(lambda_), *out),
+                                nb, 4 + nb)
 
     def shard(self):
         """(caller indices of the landmarks this rank owns, number of its visual edges)."""
@@ -141,11 +178,6 @@ class LocalInertialBA:
         idx = np.zeros(n_p.value, np.int32)
         _lib.check(self._lib.omv_lba_shard(self._h, None, None, _lib.ptr(idx)), "omv_lba_shard")
         return idx, n_e.value
-
-    def enable_timing(self, on=True):
-        """Per-stage events on the next optimize() calls (direct launches instead of the captured LM step)."""
-        _lib.check(self._lib.omv_lba_enable_timing(self._h, int(bool(on))), "omv_lba_enable_timing")
-        return self
 
     def set_driver(self, host_driven):
         """True: g2o's LM decisions on the host (read-back per trial); False (default): on the device."""
@@ -158,19 +190,12 @@ class LocalInertialBA:
         _lib.check(self._lib.omv_lba_host_syncs(self._h, ctypes.byref(n), ctypes.byref(t)), "omv_lba_host_syncs")
         return n.value, t.value
 
-    def stage_ms(self):
-        """Device ms of the last optimize: build, schur, solve, update+errors; and the trial count."""
-        ms = np.zeros(4)
-        t = ctypes.c_int(0)
-        _lib.check(self._lib.omv_lba_stage_ms(self._h, _lib.ptr(ms), ctypes.byref(t)), "omv_lba_stage_ms")
-        return dict(build=ms[0], schur=ms[1], solve=ms[2], update=ms[3], trials=t.value)
-
 
 HUBER_MONO = float(np.float32(np.sqrt(5.991)))     # thHuberMono / thHuberStereo are floats (Optimizer.cc:1469-1470)
 HUBER_STEREO = float(np.float32(np.sqrt(7.815)))
 
 
-class LocalBundleAdjustment:
+class LocalBundleAdjustment(_StagedBA):
     """Optimizer::LocalBundleAdjustment's optimisation (src/Optimizer.cc:1357-1785) on the visual kind of the device
     bundle-adjustment solver (omv_vba, openmavis_amd/csrc/lba.hip).  The flattened graph is a problem dict (field list:
     openmavis_amd.synth_vba.make_vba_problem, which is omv_vba_problem's):
@@ -184,6 +209,7 @@ class LocalBundleAdjustment:
     merge overload's two rounds are optimize(5), set_levels(...) and optimize(10, huber_mono=0, huber_stereo=0);
     BundleAdjustment is optimize(nIterations, huber_mono=sqrt(5.99) if bRobust else 0, ...).  No CPU fallback."""
 
+    _PREFIX = "omv_vba"
     STATE = ("q_cw", "t_cw", "pts")
 
     def __init__(self, max_kf=80, max_cams=4, max_pts=40000, max_edges=400000):
@@ -194,21 +220,12 @@ class LocalBundleAdjustment:
         self._lib, self._h = lib, h
         self._s = self._keep = None
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.omv_vba_destroy(self._h)
-            self._h = None
-
     def set_problem(self, prob):
         from .synth_vba import as_vba_struct
         s, keep = as_vba_struct(prob, _lib.VbaProblem)
         _lib.check(self._lib.omv_vba_set_problem(self._h, ctypes.byref(s)), "omv_vba_set_problem")
         self._s, self._keep = s, keep
         return self
-
-    def _need(self, what):
-        if self._s is None:
-            raise _lib.OmvError(f"LocalBundleAdjustment.{what}: no problem set")
 
     def set_levels(self, mono_level=None, stereo_level=None):
         """Per-edge levels in the caller's order (0 active, 1 excluded); None: every edge of that kind active."""
@@ -261,29 +278,11 @@ class LocalBundleAdjustment:
         self._need("debug_solve")
         o = self._opts(1, 0.0, 10, huber_mono, huber_stereo)
         nb = int(self._s.n_opt)
-        n = 16 * nb
-        S, rhs, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
-        plan = np.full(4 + nb, -1, np.int32)
-        fail = ctypes.c_int(-1)
-        _lib.check(self._lib.omv_vba_debug_solve(self._h, ctypes.byref(o), ctypes.c_double(lambda_), _lib.ptr(S),
-                                                 _lib.ptr(rhs), _lib.ptr(x), ctypes.byref(fail), _lib.ptr(plan),
-                                                 len(plan)), "omv_vba_debug_solve")
-        n_lev = int(plan[3])
-        return dict(S=S, rhs=rhs, x=x, fail=fail.value, mode=int(plan[0]), n_slots=int(plan[1]), n_lds=int(plan[2]),
-                    n_lev=n_lev, cols=[int(v) for v in plan[4:4 + n_lev]])
-
-    def enable_timing(self, on=True):
-        _lib.check(self._lib.omv_vba_enable_timing(self._h, int(bool(on))), "omv_vba_enable_timing")
-        return self
-
-    def stage_ms(self):
-        ms = np.zeros(4)
-        t = ctypes.c_int(0)
-        _lib.check(self._lib.omv_vba_stage_ms(self._h, _lib.ptr(ms), ctypes.byref(t)), "omv_vba_stage_ms")
-        return dict(build=ms[0], schur=ms[1], solve=ms[2], update=ms[3], trials=t.value)
+        return self._read_solve(lambda *out: self._call("debug_solve", ctypes.byref(o), ctypes.c_double(lambda_), *out),
+                                nb, 4 + nb)
 
 
-class FullInertialBA:
+class FullInertialBA(_StagedBA):
     """Optimizer::FullInertialBA's optimisation (src/Optimizer.cc:368-853) on the full inertial kind of the device
     bundle-adjustment solver (omv_fiba, openmavis_amd/csrc/lba.hip): the whole map, every EdgeInertial Huber at its
     full information, no outlier round.  The flattened map is a problem dict (openmavis_amd.synth_fiba.make_fiba_problem:
@@ -297,6 +296,8 @@ class FullInertialBA:
     keyframes see: it is no vertex); `state`: Rwb, twb, Rcw, tcw, vel, bg, ba, pts -- with shared_bias every bImu keyframe
     holds the pair.  The state stays on the device between calls.  One rank; no CPU fallback."""
 
+    _PREFIX = "omv_fiba"
+
     def __init__(self, max_kf=200, max_cams=5, max_pts=40000, max_edges=400000, max_imu=200):
         lib = _lib.load()
         h = ctypes.c_void_p()
@@ -305,21 +306,12 @@ class FullInertialBA:
         self._lib, self._h = lib, h
         self._s = self._keep = None
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.omv_fiba_destroy(self._h)
-            self._h = None
-
     def set_problem(self, prob):
         from .synth_fiba import as_fiba_struct
         s, keep = as_fiba_struct(prob, _lib.FibaProblem, _lib.LbaProblem)
         _lib.check(self._lib.omv_fiba_set_problem(self._h, ctypes.byref(s)), "omv_fiba_set_problem")
         self._s, self._keep = s, keep
         return self
-
-    def _need(self, what):
-        if self._s is None:
-            raise _lib.OmvError(f"FullInertialBA.{what}: no problem set")
 
     def optimize(self, iterations=100, lambda_init=1e-5, max_trials=10, chi2=True):
         self._need("optimize")
@@ -356,26 +348,7 @@ class FullInertialBA:
         n = 16 (n_opt + shared_bias): the shared pair is the last block, rows 9..14 of it."""
         self._need("debug_solve")
         nb = int(self._s.base.n_opt) + int(self._s.shared_bias != 0)
-        n = 16 * nb
-        S, rhs, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
-        plan = np.full(4 + nb, -1, np.int32)
-        fail = ctypes.c_int(-1)
-        _lib.check(self._lib.omv_fiba_debug_solve(self._h, ctypes.c_double(lambda_), _lib.ptr(S), _lib.ptr(rhs),
-                                                  _lib.ptr(x), ctypes.byref(fail), _lib.ptr(plan), len(plan)),
-                   "omv_fiba_debug_solve")
-        n_lev = int(plan[3])
-        return dict(S=S, rhs=rhs, x=x, fail=fail.value, mode=int(plan[0]), n_slots=int(plan[1]), n_lds=int(plan[2]),
-                    n_lev=n_lev, cols=[int(v) for v in plan[4:4 + n_lev]])
-
-    def enable_timing(self, on=True):
-        _lib.check(self._lib.omv_fiba_enable_timing(self._h, int(bool(on))), "omv_fiba_enable_timing")
-        return self
-
-    def stage_ms(self):
-        ms = np.zeros(4)
-        t = ctypes.c_int(0)
-        _lib.check(self._lib.omv_fiba_stage_ms(self._h, _lib.ptr(ms), ctypes.byref(t)), "omv_fiba_stage_ms")
-        return dict(build=ms[0], schur=ms[1], solve=ms[2], update=ms[3], trials=t.value)
+        return self._read_solve(lambda *out: self._call("debug_solve", ctypes.c_double(lambda_), *out), nb, 4 + nb)
 
 
 class PoseInertialOptimizer:
@@ -633,7 +606,7 @@ def OptimizeSim3(jobs, vpMatches1=None, optimizer=None):
     return out
 
 
-class EssentialGraph:
+class EssentialGraph(_BlockSolverHandle):
     """The pose graphs of loop closing and map merging (Optimizer::OptimizeEssentialGraph, src/Optimizer.cc:1826-2119, its
     merge overload :2121-2458, and OptimizeEssentialGraph4DoF :6171-6480) on the device (omv_essgraph,
     openmavis_amd/csrc/essgraph.hip): g2o's Levenberg-Marquardt with the edges' numeric Jacobians on the block LDL^T of
@@ -647,6 +620,7 @@ class EssentialGraph:
     `res`: err / err_end, iterations, trials, solver_failed, lambda_ and the final vertices.  The state stays on the
     device between calls.  One rank; no CPU fallback."""
 
+    _PREFIX = "omv_essgraph"
     KINDS = {"sim3": _lib.ESSGRAPH_SIM3, "4dof": _lib.ESSGRAPH_4DOF}
     MODES = {"loop": _lib.ESSGRAPH_RECOVER_LOOP, "merge": _lib.ESSGRAPH_RECOVER_MERGE, "4dof": _lib.ESSGRAPH_RECOVER_4DOF}
 
@@ -659,11 +633,6 @@ class EssentialGraph:
         self._lib, self._h = lib, h
         self._s = self._keep = None
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self._lib.omv_essgraph_destroy(self._h)
-            self._h = None
-
     @property
     def _sim3(self):
         return self.kind == _lib.ESSGRAPH_SIM3
@@ -673,10 +642,6 @@ class EssentialGraph:
         _lib.check(self._lib.omv_essgraph_set_problem(self._h, ctypes.byref(s)), "omv_essgraph_set_problem")
         self._s, self._keep = s, keep
         return self
-
-    def _need(self, what):
-        if self._s is None:
-            raise _lib.OmvError(f"EssentialGraph.{what}: no problem set")
 
     def optimize(self, iterations=20, max_trials=10):
         self._need("optimize")
@@ -711,16 +676,8 @@ class EssentialGraph:
         self._need("debug_solve")
         nb, nl = ctypes.c_int(0), ctypes.c_int(0)
         _lib.check(self._lib.omv_essgraph_blocks(self._h, ctypes.byref(nb), ctypes.byref(nl)), "omv_essgraph_blocks")
-        n = 16 * nb.value
-        S, rhs, x = np.zeros((n, n)), np.zeros(n), np.zeros(n)
-        plan = np.full(4 + nl.value, -1, np.int32)
-        fail = ctypes.c_int(-1)
-        _lib.check(self._lib.omv_essgraph_debug_solve(self._h, ctypes.c_double(lambda_), _lib.ptr(S), _lib.ptr(rhs),
-                                                      _lib.ptr(x), ctypes.byref(fail), _lib.ptr(plan), len(plan)),
-                   "omv_essgraph_debug_solve")
-        n_lev = int(plan[3])
-        return dict(S=S, rhs=rhs, x=x, fail=fail.value, mode=int(plan[0]), n_slots=int(plan[1]), n_lds=int(plan[2]),
-                    n_lev=n_lev, cols=[int(v) for v in plan[4:4 + n_lev]])
+        return self._read_solve(lambda *out: self._call("debug_solve", ctypes.c_double(lambda_), *out), nb.value,
+                                4 + nl.value)
 
     def recover(self, mode, points=None, point_ref=None):
         """The epilogue: the SE3f of every keyframe's SetPose as [n][7] (unit quaternion x y z w, translation) and the
